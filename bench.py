@@ -1,9 +1,14 @@
 #!/usr/bin/env python3
 """Benchmark of the TSDF hot path: depth frames/s -> 32^3 TSDF (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
+
+A plain run sets up, warms up, times the K steps and prints the line; `--full` adds everything else below (the one-batch
+pass, the single-launch spread, configs[3]_sharded, the PMC traffic passes, the CPU baseline and the extras).
+`--dump-outputs DIR` writes what the last timed step computed as DIR/*.npy (see dump_outputs): with the same arguments
+the inputs are the same seeded frames on every run, so two builds can be compared output for output.
 
 One "step" = LAUNCHES_PER_STEP (16) back-to-back fused launches of the voxelizer, each over the rank's batch of
 1024 synthetic 320x240 full-frame depth crops (BASELINE.json configs[1]), inputs already resident in HBM: 16,384
@@ -19,12 +24,12 @@ Extra objects on that line:
   roofline     the fused kernel against the HBM roofline: algorithmic bytes per launch
                (24 + 4*N_px + 12*R^3 + 16 (+8 offsets) per frame) divided by
                the mean launch duration over the timed region, measured with a HIP event pair on
-               the launch stream (it includes the ~2 us launch-to-launch gap; the spread of single
-               launches comes from a separate pass with per-launch event pairs).
-  cpu_baseline the oracle (C restatement of the reference math, oracle/tsdf_oracle.c) timed on
+               the launch stream (it includes the ~2 us launch-to-launch gap; with --full, the spread of
+               single launches comes from a separate pass with per-launch event pairs).
+  cpu_baseline (--full) the oracle (C restatement of the reference math, oracle/tsdf_oracle.c) timed on
                this box's host cores on a bounded sample of the same frames (rank 0, N=1 only).
   per_rank     event-timed ms per step, frames/s and CPU mask of every rank.
-  extras       "configs[3]_sharded" at every N: the 76,500-crop set split by pixel-balanced contiguous shards, every
+  extras       (--full) "configs[3]_sharded" at every N: the 76,500-crop set split by pixel-balanced contiguous shards, every
                rank voxelizing its own (per-rank and aggregate frames/s); the other BASELINE configs, the loaders and
                the latency table at N=1.
 
@@ -992,11 +997,42 @@ def extras(pkg, synth, dev, batches, offsets):
     return ex
 
 
+DUMP_SAMPLE_FRAMES = 20     # TSDF volumes kept per batch by --dump-outputs: 6 x 20 x 384 KiB = 47 MB of the 2.4 GB
+DUMP_SAMPLE_SEED = 20261016
+
+
+def dump_outputs(batches, outdir):
+    """--dump-outputs: what the timed path handed back in its last step.  Every one of the ROTATION output sets was last
+    written by a launch of that step (LAUNCHES_PER_STEP >= ROTATION), so batch k's TsdfBatch is what a caller of the k-th
+    launch would receive.  Written as float32 / float64 .npy, leading axis = batch in rotation order:
+      max_l [ROTATION, 1024] f32, mid_p [ROTATION, 1024, 3] f32, status [ROTATION, 1024] f64 (the int32 codes, exact),
+      tsdf_sample [ROTATION, DUMP_SAMPLE_FRAMES, 3, R, R, R] f32: the volumes of a fixed seeded choice of frames
+      (sorted, the same in every batch), since all 1024 x ROTATION volumes are 2.4 GB."""
+    os.makedirs(outdir, exist_ok=True)
+    frames = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(FRAMES_PER_LAUNCH, DUMP_SAMPLE_FRAMES, replace=False))
+    outs = [b[3] for b in batches]
+    idx = torch.from_numpy(frames).to(outs[0].tsdf.device)
+    arrays = {
+        "max_l": np.stack([o.max_l.cpu().numpy() for o in outs]).astype(np.float32),
+        "mid_p": np.stack([o.mid_p.cpu().numpy() for o in outs]).astype(np.float32),
+        "status": np.stack([o.status.cpu().numpy() for o in outs]).astype(np.float64),
+        "tsdf_sample": np.stack([o.tsdf.index_select(0, idx).cpu().numpy() for o in outs]).astype(np.float32),
+    }
+    for name, a in arrays.items():
+        np.save(os.path.join(outdir, name + ".npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything besides the headline: the one-batch pass, the single-launch spread, "
+                         "configs[3]_sharded, the PMC traffic passes, the CPU baseline and the extras (the --no-* options "
+                         "below leave parts of it out)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step computed to DIR/*.npy (rank 0)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-extras", action="store_true", help="skip the other configs / latency table (rank 0, N=1)")
     ap.add_argument("--no-config3", action="store_true", help="skip configs[3]_sharded (every rank, every N)")
@@ -1006,6 +1042,9 @@ def main():
     ap.add_argument("--no-live-traffic", action="store_true",
                     help="do not run the three rocprofv3 PMC child passes that measure roofline.traffic (rank 0, N=1)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("--steps must be >= 1 and --warmup >= 0")
+    full = args.full
 
     # stdout carries ONE line, the JSON: everything else that writes to file descriptor 1 during the run — RCCL prints a
     # five-line version banner there when the first communicator comes up — is sent to stderr instead
@@ -1022,6 +1061,8 @@ def main():
             raise SystemExit("--gpus N>1 must be launched with torch.distributed.run (one rank per GPU)")
         raise SystemExit(f"WORLD_SIZE={world} does not match --gpus {args.gpus}")
     dry = os.environ.get("TSDF_BENCH_DRYRUN") == "1"
+    if dry and args.dump_outputs:
+        raise SystemExit("--dump-outputs needs the GPU path: the host stub of a dry run computes nothing")
     # TSDF_BENCH_REHEARSAL=1: dry run of the N>1 code path on a box with fewer GPUs than ranks (ranks share
     # devices, the barrier / gathers go over gloo instead of RCCL, the line says "rehearsal": true).
     rehearsal = os.environ.get("TSDF_BENCH_REHEARSAL") == "1" or dry
@@ -1137,10 +1178,12 @@ def main():
 
     n_launch = args.steps * LAUNCHES_PER_STEP
     my_event_ms = be.elapsed_ms(ev0, ev1)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(batches, args.dump_outputs)     # before anything else launches into the output sets
 
     # the same number of launches over ONE batch (what rounds 1-4 reported as the headline): outside the timed region
     same_ms = float("nan")
-    if not args.no_same_batch:
+    if full and not args.no_same_batch:
         ev2, ev3 = be.event(), be.event()
         for _ in range(LAUNCHES_PER_STEP):
             be.launch(td, to, th, out)
@@ -1155,20 +1198,22 @@ def main():
     timing = gather([elapsed, my_event_ms, same_ms] + seeds)          # [world][3 + ROTATION]
     elapsed_max = float(timing[:, 0].max())
 
-    # diagnostic pass (outside the timed region): per-launch event pairs -> spread of single launches (in rotation)
-    ev = [(be.event(), be.event()) for _ in range(48)]
-    for i, (a, b) in enumerate(ev):
-        d_, o_, h_, out_ = batches[i % ROTATION]
-        be.record(a)
-        be.launch(d_, o_, h_, out_)
-        be.record(b)
-    be.sync()
-    kern_ms = np.array([be.elapsed_ms(a, b) for a, b in ev])
+    # diagnostic pass (--full, outside the timed region): per-launch event pairs -> spread of single launches (in rotation)
+    kern_ms = None
+    if full:
+        ev = [(be.event(), be.event()) for _ in range(48)]
+        for i, (a, b) in enumerate(ev):
+            d_, o_, h_, out_ = batches[i % ROTATION]
+            be.record(a)
+            be.launch(d_, o_, h_, out_)
+            be.record(b)
+        be.sync()
+        kern_ms = np.array([be.elapsed_ms(a, b) for a, b in ev])
     launch_ms = my_event_ms / n_launch  # mean launch-to-launch time over the timed region
 
     # ---- BASELINE configs[3]: every rank voxelizes its shard of the 76,500-crop set (no collective on the data path)
     c3 = None
-    if not args.no_config3:
+    if full and not args.no_config3:
         f3, px3, s3, a3 = config3_sharded(be, synth, shard, packing, rank, world)
         g3 = gather([f3, px3, s3, a3])               # [world][4]
         fr, px, sec = g3[:, 0], g3[:, 1], g3[:, 2]
@@ -1195,7 +1240,7 @@ def main():
         traffic_parts = None
         under_profiler = any(k.startswith("ROCPROF") or k.startswith("ROCP_") for k in os.environ)
         live_note = None
-        if world == 1 and not dry and not rehearsal and not args.no_live_traffic and not under_profiler:
+        if full and world == 1 and not dry and not rehearsal and not args.no_live_traffic and not under_profiler:
             traffic_parts = live_traffic()
             if traffic_parts and "hbm_bytes_per_launch" in traffic_parts:
                 traffic = traffic_parts["hbm_bytes_per_launch"]
@@ -1207,7 +1252,7 @@ def main():
             elif traffic_parts:
                 live_note = traffic_parts.get("failed")
         pmc = os.path.join(ROOT, "profiles", "pmc_traffic.json")
-        if traffic is None and os.path.exists(pmc):
+        if full and traffic is None and os.path.exists(pmc):
             try:
                 traffic = json.load(open(pmc)).get("hbm_bytes_per_launch")
                 traffic_source = ("profiles/pmc_traffic.json: rocprofv3 FETCH_SIZE/WRITE_SIZE passes of this command from the "
@@ -1268,9 +1313,10 @@ def main():
                 "frac_of_measured_copy": round(achieved / HBM_COPY_GBS, 4),
                 "kernel": be.kernel_name(FRAMES_PER_LAUNCH, RES), "algorithmic_bytes_per_launch": abytes,
                 "launch_ms_mean": round(mean_ms, 4),
-                "single_launch_ms_median": round(float(np.median(kern_ms)), 4),
-                "single_launch_ms_min": round(float(kern_ms.min()), 4),
+                "single_launch_ms_median": (round(float(np.median(kern_ms)), 4) if kern_ms is not None else None),
+                "single_launch_ms_min": (round(float(kern_ms.min()), 4) if kern_ms is not None else None),
             },
+            "full": full,
         }
         if rehearsal:
             line["rehearsal"] = True
@@ -1279,11 +1325,11 @@ def main():
         ex = {}
         if c3 is not None:
             ex["configs[3]_sharded"] = c3
-        if world == 1 and not args.no_cpu_baseline:
+        if full and world == 1 and not args.no_cpu_baseline:
             # (a dry run times the oracle on its all-background frames for a moment: the object's shape, not a number)
             line["cpu_baseline"] = (cpu_baseline(depth, offsets, headers, 0.05, 0.05, legs_override=[1, 2]) if dry
                                     else cpu_baseline(depth, offsets, headers))
-        if world == 1 and not args.no_extras and not rehearsal:
+        if full and world == 1 and not args.no_extras and not rehearsal:
             ex.update(extras(be.pkg, synth, be.dev, batches, offsets))
             sc = stream_ceilings()
             if sc:

@@ -97,8 +97,8 @@ def _free_port():
     return p
 
 
-def _run_bench(tmp_path, world, through_torchrun=True, extra_env=None, args=("--steps", "3", "--warmup", "1")):
-    """bench.py with the GPU work stubbed (TSDF_BENCH_DRYRUN=1) over a fake sysfs tree with `max(world, 2)` GPUs on two
+def _run_bench(tmp_path, world, through_torchrun=True, extra_env=None, args=("--steps", "3", "--warmup", "1", "--full")):
+    """bench.py (by default with --full) with the GPU work stubbed (TSDF_BENCH_DRYRUN=1) over a fake sysfs tree with `max(world, 2)` GPUs on two
     sockets; returns (the parsed JSON line, the fake topology's (bus, numa, cpulist) rows)."""
     cpus = sorted(os.sched_getaffinity(0))
     half = max(1, len(cpus) // 2)
@@ -192,6 +192,20 @@ def test_one_rank_through_torchrun_prints_the_plain_line(tmp_path):
     kp, kt = _keys(plain), _keys(tr)
     assert kp == kt, (kp, kt)
     assert _keys(plain["roofline"], 1) == _keys(tr["roofline"], 1)
+
+
+def test_plain_run_measures_only_the_headline(tmp_path):
+    """Without --full the line carries the headline and what the timed region itself yields — no CPU baseline, no
+    configs[3], no one-batch pass, no single-launch spread — and --steps sets the number of timed steps."""
+    j, _ = _run_bench(tmp_path, 1, through_torchrun=False, args=("--steps", "5", "--warmup", "2"))
+    assert j["full"] is False and j["steps"] == 5 and j["warmup"] == 2
+    assert j["metric"] == "depth frames/sec to 32^3 TSDF" and j["unit"] == "frames/s" and j["higher_is_better"] is True
+    assert j["dtype"] == "f64" and j["ms_per_step"] > 0
+    assert abs(j["value"] - 1024 * 16 * 5 / (j["ms_per_step"] * 5e-3)) / j["value"] < 1e-3
+    assert "cpu_baseline" not in j and "extras" not in j
+    rf = j["roofline"]
+    assert rf["frac_same_batch"] is None and rf["single_launch_ms_median"] is None and rf["traffic"] is None
+    assert rf["launch_ms_mean"] > 0 and rf["achieved"] > 0
 
 
 def test_cpu_baseline_thread_plan(tmp_path):

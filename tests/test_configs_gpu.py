@@ -232,7 +232,8 @@ def test_bench_one_rank_through_torchrun_prints_the_plain_line():
     s.bind(("127.0.0.1", 0))
     port = s.getsockname()[1]
     s.close()
-    tail = [os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "4", "--warmup", "2", "--no-extras", "--no-live-traffic"]
+    tail = [os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "4", "--warmup", "2", "--full", "--no-extras",
+            "--no-live-traffic"]
     env = {k: v for k, v in os.environ.items() if k not in ("TORCHELASTIC_RUN_ID", "RANK", "WORLD_SIZE", "LOCAL_RANK")}
     lines = []
     for cmd in ([sys.executable] + tail,
@@ -253,3 +254,46 @@ def test_bench_one_rank_through_torchrun_prints_the_plain_line():
         assert j["extras"]["configs[3]_sharded"]["per_rank_frames"] == [N_ALL]
     assert set(plain) == set(tr) and set(plain["roofline"]) == set(tr["roofline"]) and set(plain["cpu_baseline"]) == set(tr["cpu_baseline"])
     assert abs(plain["value"] - tr["value"]) / plain["value"] < 0.05
+
+
+def test_bench_dump_outputs_hold_what_the_last_step_computed(synth, tmp_path):
+    """A plain `bench.py --dump-outputs DIR` run on the real GPU: the line is the lean one (no --full parts), the dump is
+    float32 / float64 .npy within 64 MB, and what it holds for the first and the last batch of the rotation — the
+    sampled volumes, max_l, mid_p, status — is the oracle's result on the same seeded frames."""
+    import importlib.util
+    import json
+    import os
+    import subprocess
+    import sys
+
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    spec = importlib.util.spec_from_file_location("bench_under_test", os.path.join(root, "bench.py"))
+    b = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(b)
+    dump = tmp_path / "dump"
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1",
+           "--dump-outputs", str(dump)]
+    env = {k: v for k, v in os.environ.items() if k not in ("TORCHELASTIC_RUN_ID", "RANK", "WORLD_SIZE", "LOCAL_RANK")}
+    r = subprocess.run(cmd, cwd=root, env=env, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, (r.stdout + r.stderr)[-3000:]
+    js = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert len(js) == 1
+    j = json.loads(js[0])
+    assert j["full"] is False and j["steps"] == 2 and "cpu_baseline" not in j and "extras" not in j and j["ms_per_step"] > 0
+    assert sorted(os.listdir(dump)) == ["max_l.npy", "mid_p.npy", "status.npy", "tsdf_sample.npy"]
+    assert sum(os.path.getsize(dump / f) for f in os.listdir(dump)) <= 64e6
+    got = {f[:-4]: np.load(dump / f) for f in os.listdir(dump)}
+    assert all(a.dtype in (np.float32, np.float64) for a in got.values())
+    R, S, K = b.RES, b.DUMP_SAMPLE_FRAMES, b.ROTATION
+    assert got["max_l"].shape == (K, 1024) and got["mid_p"].shape == (K, 1024, 3) and got["status"].shape == (K, 1024)
+    assert got["tsdf_sample"].shape == (K, S, 3, R, R, R)
+    assert (got["status"] == 0).all()
+    frames = np.sort(np.random.default_rng(b.DUMP_SAMPLE_SEED).choice(1024, S, replace=False))
+    for k in (0, K - 1):
+        fs = [synth.synth_frame(k * 1024 + int(i), "full") for i in frames]
+        off = np.zeros(S + 1, np.int64)
+        np.cumsum([d.size for _, d in fs], out=off[1:])
+        ref = oracle.voxelize(np.concatenate([d for _, d in fs]), off, np.stack([h for h, _ in fs]), R=R, n_threads=4)
+        np.testing.assert_array_equal(got["max_l"][k, frames], ref["max_l"])
+        np.testing.assert_array_equal(got["mid_p"][k, frames], ref["mid_p"])
+        assert np.abs(got["tsdf_sample"][k] - ref["tsdf"]).max() <= TOL

@@ -1,9 +1,11 @@
-"""CPU tier, build container only: the oracle against the reference RUN LIVE on frames that are NOT among the committed
-fixtures.  tests/golden/ pins 22 frames; this runs the reference's own loop (pre/tsdf_for.py::tsdf_f / tsdf_cal through
-tools/make_goldens.run_reference: as it runs today and on float64-typed parameters = the numba typing) on 33 more seeded
-frames of every family — benchmark distributions, near / far hands, corner bboxes, sparse, dense, negative and mixed-sign
-depths — and asks the oracle for the same bits.  Skipped where /root/reference does not exist (the GPU box: nothing there may
-read it); nothing here touches a GPU."""
+"""CPU tier: the oracle against the reference's own loop on frames that are NOT among the volume fixtures.  tests/golden/
+pins 22 frames in its *.npz volumes; tests/golden/unseen_ref_<k>.npz hold what the reference's loop (pre/tsdf_for.py::
+tsdf_f / tsdf_cal through tools/make_goldens.run_reference: as it runs today and on float64-typed parameters = the numba
+typing) computed for 33 more seeded frames of every family — benchmark distributions, near / far hands, corner bboxes,
+sparse, dense, negative and mixed-sign depths (tools/make_goldens.unseen_frames) — and the oracle must give the same
+bits.  The depths are made again by the seeded generator and checked against the sha256 the fixtures recorded; nothing
+here touches a GPU."""
+import glob
 import importlib
 import os
 import sys
@@ -12,43 +14,43 @@ import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-pytestmark = pytest.mark.skipif(not os.path.isdir("/root/reference/pre"), reason="the reference is only in the build container")
 
 
 @pytest.fixture(scope="module")
 def mg():
     sys.path.insert(0, os.path.join(ROOT, "tools"))
     try:
-        return importlib.import_module("make_goldens")     # imports /root/reference/pre/{tsdf_for,process,joint_nor}.py
+        return importlib.import_module("make_goldens")     # its frame list and loop32_emulation; not the reference
     finally:
         sys.path.pop(0)
 
 
-def _frames(mg, synth):
-    out = []
-    for s in (40, 41):
-        out.append((f"full_{s}", *synth.synth_frame(s, "full")))
-    for s in (60, 61, 62, 63):
-        out.append((f"crop_{s}", *synth.synth_frame(s, "crop")))
-    for name, _, kw in mg.VARIANTS:                        # two unseen seeds of every family the fixtures hold
-        for s in (200, 201):
-            out.append((f"{name}#{s}", *synth.synth_variant(s, **kw)))
-    # mixed signs at two different distances: the camera plane off the grid's centre
-    h, d = synth.synth_variant(202, bbox=(60, 30, 260, 210), base=500.0, rad=80.0)
-    xs = np.arange(d.size) % 200
-    out.append(("mixed_two_distances", h, np.where(xs < 100, -0.3 * d, d).astype(np.float32)))
+def _recorded(golden_dir):
+    """name -> what the reference computed for that frame (loop32 rebuilt from loop64 and the recorded differences)."""
+    out = {}
+    for fn in sorted(glob.glob(os.path.join(golden_dir, "unseen_ref_*.npz"))):
+        z = np.load(fn)
+        for i, name in enumerate(z["names"]):
+            g = {k[len(f"f{i}_"):]: z[k] for k in z.files if k.startswith(f"f{i}_")}
+            loop32 = g["loop64"].copy()
+            loop32.reshape(-1)[g["loop32_diff_index"]] = g["loop32_diff_value"]
+            g["loop32"] = loop32
+            out[str(name)] = g
     return out
 
 
-def test_oracle_equals_the_reference_loop_on_unseen_frames(mg, synth):
+def test_oracle_equals_the_reference_loop_on_unseen_frames(mg, golden_dir):
     import oracle
 
     n_flip_frames = 0
-    frames = _frames(mg, synth)
+    frames = mg.unseen_frames()
+    rec = _recorded(golden_dir)
     assert len(frames) >= 33
+    assert sorted(rec) == sorted(name for name, _, _ in frames)
     for name, h, d in frames:
-        with np.errstate(all="ignore"):
-            g = mg.run_reference(h, d)
+        g = rec[name]
+        assert str(g["depth_sha256"]) == mg.depth_digest(d), f"{name}: the generator no longer makes the recorded frame"
+        np.testing.assert_array_equal(h, g["header"], err_msg=name)
         out, pm = oracle.voxels(d, h, g["vox_ori"], g["voxel_len"], g["trunc"], R=32, layout=0, want_pixmap=True)
         np.testing.assert_array_equal(out, g["loop64"], err_msg=name)                 # a4, numba typing: bit for bit
         bad = (np.abs(out - g["loop32"]) > 1e-5).any(axis=0)
@@ -64,4 +66,5 @@ def test_oracle_equals_the_reference_loop_on_unseen_frames(mg, synth):
         np.testing.assert_allclose(mx, g["pc_max"], rtol=3e-7, atol=0, err_msg=name)
         # the search emulation of tools/make_goldens.py stays the reference's float32 loop
         np.testing.assert_array_equal(mg.loop32_emulation(d, h, g["vox_ori"], g["voxel_len"], g["trunc"]), g["loop32"])
-    print(f"{len(frames)} unseen frames through the reference loop; {n_flip_frames} of them with float32/float64 flips")
+    print(f"{len(frames)} unseen frames against the reference loop's recorded results; {n_flip_frames} of them with "
+          "float32/float64 flips")

@@ -31,6 +31,8 @@ What each fixture pins:
           x 2-frame synthetic MSRA tree (synth.synth_msra_tree, regenerated from its seed by the tests) exported in the
           reference's on-disk schema with the ORACLE as the voxelizer (no GPU here): length, item order, dtypes, shapes,
           gt / max_l / mid_p of every item, the volumes of a few.  Pins row f1 to the class instead of to a reading of it.
+  unseen_ref_<k>  run_reference on 33 more seeded frames that no volume fixture holds (unseen_frames): what the
+          reference computed for them, for tests/test_reference_live.py.
   aabb_*  the numba-typing AABB (pre/tsdf_numba.py:84-96,140-141) from
           oracle/tsdf_oracle_np.py — a restatement, not a run (min_max_kernel cannot
           be executed here: no usable numba, no params.py).
@@ -46,14 +48,20 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 REF_PRE = "/root/reference/pre"
 sys.path.insert(0, ROOT)
-sys.path.insert(0, REF_PRE)
-
-import tsdf_for  # noqa: E402  (the reference)
-import process as ref_process  # noqa: E402  (the reference)
-import joint_nor as ref_joint_nor  # noqa: E402  (the reference)
 
 synth = importlib.import_module("handposeestimation-with-3d-cnns_amd.synth")
 from oracle import tsdf_oracle_np as onp  # noqa: E402
+
+
+def _reference():
+    """The reference's own pre/tsdf_for.py, pre/process.py and pre/joint_nor.py, imported by the steps that run them and
+    by nothing else: the tests import this module for its frame lists and loop32_emulation, without the reference."""
+    if REF_PRE not in sys.path:
+        sys.path.insert(0, REF_PRE)
+    import joint_nor as ref_joint_nor
+    import process as ref_process
+    import tsdf_for
+    return tsdf_for, ref_process, ref_joint_nor
 
 
 def special_frames():
@@ -77,6 +85,7 @@ def special_frames():
 
 
 def run_reference(header, depth):
+    tsdf_for, ref_process, _ = _reference()
     nv, mn, mx = onp.aabb(depth, header)
     assert nv > 0
     data32 = {"header": header, "depth": depth}
@@ -126,6 +135,7 @@ def run_reference_aug(outdir):
     the one input shape it does not raise AxisError on — with np.random seeded.  Stores the
     inputs, the seeds and what the reference returned; nothing else (the draws are not observable from outside:
     tests re-draw them with augment.reference_draw and must reproduce these outputs)."""
+    _, ref_process, _ = _reference()
     rng = np.random.default_rng(4242)
     seeds = np.array([0, 1, 7, 12345, 20261004], np.int64)
     M = 64
@@ -152,6 +162,7 @@ def run_reference_joint_nor(outdir, golden_scales):
     MANIFEST.txt), the rest seeded scales; some joints lie outside the cube so that the clamp of
     3D_CNN/train.py:241-242 (applied by the test to these reference values) has something to do.  The reference
     stores its float32 results in a float64 array; they are kept as float64 here, untouched."""
+    _, _, ref_joint_nor = _reference()
     rng = np.random.default_rng(777)
     n_extra = 24
     max_l = np.concatenate([np.array([g[0] for g in golden_scales], np.float32),
@@ -381,10 +392,60 @@ def run_volumes(outdir):
             f.write(n + "\n")
 
 
+def unseen_frames():
+    """33 seeded frames that are NOT among the volume fixtures, of every family — benchmark distributions, near / far
+    hands, corner bboxes, sparse, dense, negative and mixed-sign depths: (name, header, depth)."""
+    out = []
+    for s in (40, 41):
+        out.append((f"full_{s}", *synth.synth_frame(s, "full")))
+    for s in (60, 61, 62, 63):
+        out.append((f"crop_{s}", *synth.synth_frame(s, "crop")))
+    for name, _, kw in VARIANTS:                        # two unseen seeds of every family the fixtures hold
+        for s in (200, 201):
+            out.append((f"{name}#{s}", *synth.synth_variant(s, **kw)))
+    # mixed signs at two different distances: the camera plane off the grid's centre
+    h, d = synth.synth_variant(202, bbox=(60, 30, 260, 210), base=500.0, rad=80.0)
+    xs = np.arange(d.size) % 200
+    out.append(("mixed_two_distances", h, np.where(xs < 100, -0.3 * d, d).astype(np.float32)))
+    return out
+
+
+UNSEEN_PER_FILE = 6     # unseen_ref_<k>.npz: frames [6k, 6k+6) of unseen_frames(), each file well under 1 MiB
+
+
+def depth_digest(depth):
+    import hashlib
+    return hashlib.sha256(np.ascontiguousarray(depth, np.float32).tobytes()).hexdigest()
+
+
+def run_unseen(outdir):
+    """unseen_ref_<k>.npz: run_reference on unseen_frames(), for tests/test_reference_live.py.  The depths are not stored
+    (the seeded generator makes them again; their sha256 is kept so that a drift of the generator is caught); loop64 is
+    stored whole, loop32 as the voxels where its bits differ from loop64 (flat index + value)."""
+    frames = unseen_frames()
+    for k in range(0, len(frames), UNSEEN_PER_FILE):
+        out = {"names": np.array([f[0] for f in frames[k:k + UNSEEN_PER_FILE]])}
+        for i, (name, h, d) in enumerate(frames[k:k + UNSEEN_PER_FILE]):
+            with np.errstate(all="ignore"):
+                g = run_reference(h, d)
+            emu = loop32_emulation(d, h, g["vox_ori"], g["voxel_len"], g["trunc"])
+            assert np.array_equal(emu, g["loop32"]), f"{name}: the search emulation is not the reference's loop32"
+            diff = np.flatnonzero(g["loop32"].view(np.uint32) != g["loop64"].view(np.uint32))
+            rec = {key: g[key] for key in ("header", "aabb_min", "aabb_max", "n_valid", "pc_min", "pc_max", "pc_n", "max_l",
+                                           "mid_p", "vox_ori", "voxel_len", "trunc", "loop64", "n_flip")}
+            rec.update(depth_sha256=np.array(depth_digest(d)), loop32_diff_index=diff.astype(np.int64),
+                       loop32_diff_value=g["loop32"].reshape(-1)[diff])
+            out.update({f"f{i}_{key}": v for key, v in rec.items()})
+        fn = os.path.join(outdir, f"unseen_ref_{k // UNSEEN_PER_FILE}.npz")
+        np.savez_compressed(fn, **out)
+        print(f"{os.path.basename(fn)}: {len(out['names'])} frames, {os.path.getsize(fn)} bytes")
+
+
 def main(only=None):
     outdir = os.path.join(ROOT, "tests", "golden")
     os.makedirs(outdir, exist_ok=True)
-    steps = {"aug": run_reference_aug, "io": run_reference_io, "dataset": run_reference_dataset, "volumes": run_volumes}
+    steps = {"aug": run_reference_aug, "io": run_reference_io, "dataset": run_reference_dataset, "volumes": run_volumes,
+             "unseen": run_unseen}
     for name in (only or list(steps)):   # --only: some of the fixtures, the others untouched (npz files carry time stamps)
         steps[name](outdir)
 
@@ -394,5 +455,5 @@ if __name__ == "__main__":
 
     ap = argparse.ArgumentParser(description="Regenerate tests/golden/*.npz by running the reference's own code "
                                              "(needs /root/reference).")
-    ap.add_argument("--only", default="", help="comma list of aug,io,dataset,volumes: just these fixtures")
+    ap.add_argument("--only", default="", help="comma list of aug,io,dataset,volumes,unseen: just these fixtures")
     main([x for x in ap.parse_args().only.split(",") if x])

@@ -18,8 +18,8 @@ OUT=$PWD/gpurun_out/profiles_$TAG
 rm -rf $OUT; mkdir -p $OUT
 # (a step is 16 launches, each over the next of six resident batches: 6 steps + 1 warm-up + the 48 single launches of the
 # spread pass = 160 launches per pass, all of them launches of the rotation; the one-batch pass is skipped)
-BENCH="python3 bench.py --steps 6 --warmup 1 --no-extras --no-config3 --no-live-traffic --no-same-batch"
-python3 bench.py > $OUT/bench_unprofiled.json 2> $OUT/bench_unprofiled.err || exit 1
+BENCH="python3 bench.py --steps 6 --warmup 1 --full --no-extras --no-config3 --no-live-traffic --no-same-batch"
+python3 bench.py --full > $OUT/bench_unprofiled.json 2> $OUT/bench_unprofiled.err || exit 1
 tail -1 $OUT/bench_unprofiled.json | cut -c1-300
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -- $BENCH > $OUT/trace.log 2>&1 || { tail -5 $OUT/trace.log; exit 1; }
 rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $OUT/pmc_fetch -- $BENCH --no-cpu-baseline > $OUT/pmc_fetch.log 2>&1 || { tail -5 $OUT/pmc_fetch.log; exit 1; }
