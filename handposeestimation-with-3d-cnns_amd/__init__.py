@@ -9,12 +9,16 @@ Reference-signature shims:               tsdf_numba.cal_tsdf_cuda, tsdf_for.tsdf
                                          process.DataProcess
 Host side:                               packing (MSRA .bin reader / batch packer), shard, synth,
                                          dataset (on-the-fly MSRADepthDataset / VoxelLoader / ResidentLoader, label normalisation)
+Full mode and evaluation:                pca (JointPCA, fit_joint_pca), project_joints, pose_error, joints_within,
+                                         frames_within
 """
 from . import _lib  # noqa: F401
 from ._lib import TsdfCam, TsdfError, default_cam  # noqa: F401
-from .voxelize import (AabbBatch, TsdfBatch, aabb, denormalize_joints, normalize_joints, release_stream,  # noqa: F401
-                       voxel_pixels, voxelize, voxelize_aug, voxelize_grid, voxelize_indexed, voxelize_labels)
-from . import augment, dataset, export, packing, shard, synth  # noqa: F401
+from .voxelize import (AabbBatch, PoseError, TsdfBatch, aabb, denormalize_joints, frames_within,  # noqa: F401
+                       joints_within, normalize_joints, pose_error, project_joints, release_stream, voxel_pixels,
+                       voxelize, voxelize_aug, voxelize_grid, voxelize_indexed, voxelize_labels)
+from .pca import JointPCA, fit_joint_pca  # noqa: F401
+from . import augment, dataset, export, packing, pca, shard, synth  # noqa: F401
 from .dataset import MSRA_Dataset, MSRADepthDataset, ResidentLoader, VoxelBatch, VoxelLoader  # noqa: F401
 from .tsdf_numba import cal_tsdf_cuda  # noqa: F401
 from .tsdf_for import tsdf_cal, tsdf_f  # noqa: F401
@@ -22,4 +26,5 @@ from .process import DataProcess  # noqa: F401
 
 __all__ = ["voxelize", "voxelize_labels", "voxelize_indexed", "ResidentLoader", "voxel_pixels", "release_stream", "voxelize_grid", "voxelize_aug", "augment", "aabb", "TsdfBatch", "AabbBatch", "TsdfCam", "TsdfError",
            "default_cam", "cal_tsdf_cuda", "tsdf_f", "tsdf_cal", "DataProcess", "packing", "shard",
-           "synth", "dataset", "MSRADepthDataset", "MSRA_Dataset", "VoxelLoader", "VoxelBatch", "normalize_joints", "denormalize_joints"]
+           "synth", "dataset", "MSRADepthDataset", "MSRA_Dataset", "VoxelLoader", "VoxelBatch", "normalize_joints", "denormalize_joints",
+           "pca", "JointPCA", "fit_joint_pca", "project_joints", "pose_error", "PoseError", "joints_within", "frames_within"]

@@ -67,6 +67,17 @@ class TsdfLabels(ctypes.Structure):
     ]
 
 
+class TsdfPca(ctypes.Structure):
+    """``tsdf_pca`` of include/tsdf.h: the joint-PCA basis (device pointers) and the projection's output."""
+
+    _fields_ = [
+        ("d_mean", ctypes.c_void_p),
+        ("d_coeff", ctypes.c_void_p),
+        ("n_components", ctypes.c_int),
+        ("d_out_gt_pca", ctypes.c_void_p),
+    ]
+
+
 ABI_VERSION = 7
 INLINE_INDEX_MAX = 32   # TSDF_INLINE_INDEX_MAX of include/tsdf.h
 
@@ -127,6 +138,17 @@ def _bind(L, path: str):
     L.tsdf_denormalize_joints_hip.argtypes = [vp, vp, vp, ctypes.c_int, ctypes.c_int, vp, vp]
     L.tsdf_stream_release.restype = ctypes.c_int
     L.tsdf_stream_release.argtypes = [vp]
+    pca_p = ctypes.POINTER(TsdfPca)
+    L.tsdf_voxelize_labels_pca_hip.restype = ctypes.c_int
+    L.tsdf_voxelize_labels_pca_hip.argtypes = L.tsdf_voxelize_aug_hip.argtypes + [lab_p, pca_p]
+    L.tsdf_voxelize_indexed_pca_hip.restype = ctypes.c_int
+    L.tsdf_voxelize_indexed_pca_hip.argtypes = L.tsdf_voxelize_indexed_aug_hip.argtypes + [pca_p]
+    L.tsdf_voxelize_indexed_host_pca_hip.restype = ctypes.c_int
+    L.tsdf_voxelize_indexed_host_pca_hip.argtypes = L.tsdf_voxelize_indexed_hip.argtypes + [pca_p]
+    L.tsdf_project_joints_hip.restype = ctypes.c_int
+    L.tsdf_project_joints_hip.argtypes = [vp, vp, vp, ctypes.c_int, ctypes.c_int, pca_p, vp]
+    L.tsdf_pose_error_hip.restype = ctypes.c_int
+    L.tsdf_pose_error_hip.argtypes = [vp, pca_p, vp, vp, vp, ctypes.c_int, ctypes.c_int, vp, vp, vp, vp, vp]
     L.tsdf_describe_launch.restype = ctypes.c_int
     L.tsdf_describe_launch.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_char_p, ctypes.c_int]
     return L

@@ -139,6 +139,78 @@ int tsdf_denormalize_joints_hip(const float *d_pred, const float *d_max_l, const
   return run_normalize(d_pred, d_max_l, d_mid_p, n, n_joints, 0, 1, hip_stream, d_out_joints);
 }
 
+// ---- joint PCA and pose error: every argument is checked here, before run() looks at the device ----
+static int pca_entry_args(int n, const tsdf_labels *labels, const tsdf_pca *pca) {
+  if (!labels || !pca) return TSDF_ERR_INVALID_ARG;
+  return tsdf_host::check_pca(pca, n, labels->n_joints, true);
+}
+
+int tsdf_voxelize_labels_pca_hip(const float *d_depth, int64_t depth_len, const int64_t *d_offsets,
+                                 const int32_t *d_headers, int n, int R, const tsdf_cam *cam, int layout,
+                                 void *hip_stream, const double *d_xforms, float *d_out_tsdf, float *d_out_max_l,
+                                 float *d_out_mid_p, int32_t *d_out_status, const tsdf_labels *labels,
+                                 const tsdf_pca *pca) {
+  if (n > 0 && (!d_out_tsdf || !d_out_max_l || !d_out_mid_p)) return TSDF_ERR_INVALID_ARG;
+  if (reinterpret_cast<uintptr_t>(d_xforms) & 7) return TSDF_ERR_INVALID_ARG;
+  const int chk = pca_entry_args(n, labels, pca);
+  if (chk != TSDF_OK) return chk;
+  RunOpts o;
+  o.xforms = d_xforms;
+  o.labels = labels;
+  o.pca = pca;
+  return run(d_depth, depth_len, d_offsets, d_headers, n, R, cam, layout, hip_stream, d_out_tsdf, d_out_max_l,
+             d_out_mid_p, d_out_status, o);
+}
+
+int tsdf_voxelize_indexed_pca_hip(const float *d_depth, int64_t depth_len, const int64_t *d_offsets,
+                                  const int32_t *d_headers, int64_t n_pack, const int64_t *d_index, int n, int R,
+                                  const tsdf_cam *cam, int layout, void *hip_stream, const double *d_xforms,
+                                  float *d_out_tsdf, float *d_out_max_l, float *d_out_mid_p, int32_t *d_out_status,
+                                  const tsdf_labels *labels, const tsdf_pca *pca) {
+  if (n > 0 && (!d_out_tsdf || !d_out_max_l || !d_out_mid_p || !d_index)) return TSDF_ERR_INVALID_ARG;
+  if (n_pack < 0 || (n > 0 && n_pack == 0) || (reinterpret_cast<uintptr_t>(d_xforms) & 7)) return TSDF_ERR_INVALID_ARG;
+  const int chk = pca_entry_args(n, labels, pca);
+  if (chk != TSDF_OK) return chk;
+  RunOpts o;
+  o.labels = labels;
+  o.index = d_index;
+  o.n_src = n_pack;
+  o.xforms = d_xforms;
+  o.pca = pca;
+  return run(d_depth, depth_len, d_offsets, d_headers, n, R, cam, layout, hip_stream, d_out_tsdf, d_out_max_l,
+             d_out_mid_p, d_out_status, o);
+}
+
+int tsdf_voxelize_indexed_host_pca_hip(const float *d_depth, int64_t depth_len, const int64_t *d_offsets,
+                                       const int32_t *d_headers, int64_t n_pack, const int64_t *h_index, int n, int R,
+                                       const tsdf_cam *cam, int layout, void *hip_stream, float *d_out_tsdf,
+                                       float *d_out_max_l, float *d_out_mid_p, int32_t *d_out_status,
+                                       const tsdf_labels *labels, const tsdf_pca *pca) {
+  if (n > 0 && (!d_out_tsdf || !d_out_max_l || !d_out_mid_p || !h_index)) return TSDF_ERR_INVALID_ARG;
+  if (n_pack < 0 || (n > 0 && n_pack == 0) || n > TSDF_INLINE_INDEX_MAX) return TSDF_ERR_INVALID_ARG;
+  const int chk = pca_entry_args(n, labels, pca);
+  if (chk != TSDF_OK) return chk;
+  RunOpts o;
+  o.labels = labels;
+  o.h_index = h_index;
+  o.n_src = n_pack;
+  o.pca = pca;
+  return run(d_depth, depth_len, d_offsets, d_headers, n, R, cam, layout, hip_stream, d_out_tsdf, d_out_max_l,
+             d_out_mid_p, d_out_status, o);
+}
+
+int tsdf_project_joints_hip(const float *d_gt, const float *d_max_l, const float *d_mid_p, int n, int n_joints,
+                            const tsdf_pca *pca, void *hip_stream) {
+  return run_project(d_gt, d_max_l, d_mid_p, n, n_joints, pca, hip_stream);
+}
+
+int tsdf_pose_error_hip(const float *d_pred, const tsdf_pca *pca, const float *d_max_l, const float *d_mid_p,
+                        const float *d_gt, int n, int n_joints, void *hip_stream, float *d_out_err,
+                        float *d_out_frame_mean, float *d_out_frame_max, float *d_out_joints) {
+  return run_pose_error(d_pred, pca, d_max_l, d_mid_p, d_gt, n, n_joints, hip_stream, d_out_err, d_out_frame_mean,
+                        d_out_frame_max, d_out_joints);
+}
+
 #ifdef TSDF_DEBUG_HOOKS   // the debug build only (make debug -> build/libtsdf_hip_debug.so): include/tsdf_debug.h
 int tsdf_debug_pixmap_hip(const float *d_depth, int64_t depth_len, const int64_t *d_offsets, const int32_t *d_headers,
                           int n, int R, const tsdf_cam *cam, int layout, void *hip_stream, const float *d_grid,

@@ -30,6 +30,9 @@ struct KArgs {
   unsigned int seq;       // ... and the number this launch tags them with
   int polls;              // ... and the bound of the wait for them (kXchgPolls; tests set TSDF_XCHG_POLLS=0 to
                           // force every workgroup onto the fallback)
+  const float *pca_mean, *pca_coeff;  // joint PCA (tsdf_pca; with labels only): mu[C], W[C][C]
+  float *gt_pca;                      // ... out [n][pca_k]
+  int pca_k;                          // ... K, or 0: no projection
 };
 
 // ---- synchronisation inside one half-workgroup (group) -------------------------------------------
@@ -239,10 +242,67 @@ __device__ __forceinline__ void write_frame_outputs(const KArgs &a, int frame, c
 // Labels: pre/joint_nor.py:8-18 + the clamp of 3D_CNN/train.py:241-242, float32, three separately rounded
 // operations; AUG maps the joints with the frame's forward map first (pre/process.py:232-249 does it with the
 // cloud's S and R).  Frames that are not OK get 0.5 (see include/tsdf.h).
+// Joint PCA projection of one frame (include/tsdf.h, tsdf_pca items 1 and 3).  Each wave whose first thread index is
+// below K owns 64 components (lane i: k = 64w + i).  The coordinates go 64 at a time: lane i normalises coordinate c0 + i
+// (all lanes in parallel: one division each), then the wave walks them in ascending order, broadcasting t_j with
+// v_readlane, and every lane adds t_j * W[j][k] to its float64 sum — the contract's order, with no LDS and no barrier.
+// gj: the frame's joints (mm), xf: its forward map or null, ok: the frame is TSDF_FRAME_OK (max_l > 0).
+// Wave-uniform control flow throughout (tid & ~63 and the loop bounds are the same for every lane of a wave).
+__device__ __forceinline__ void pca_project(const float *__restrict__ gj, const double *xf, const float mid[3],
+                                            float max_l, bool ok, const float *__restrict__ mean,
+                                            const float *__restrict__ W, int nc, int K, float *__restrict__ out,
+                                            int tid, int T) {
+  const int lane = tid & 63;
+  for (int k0 = tid & ~63; k0 < K; k0 += T) {
+    const int k = k0 + lane;
+    const bool kin = k < K;
+    const int kc = kin ? k : K - 1;   // (lanes past K read a valid column and discard it)
+    double p = 0.0;
+    for (int c0 = 0; c0 < nc; c0 += 64) {
+      const int e = c0 + lane;
+      float t = 0.f;
+      if (e < nc) {
+        const int c = e % 3;
+        const float *g3 = gj + (e - c);
+        float v = g3[c];
+        if (xf) v = (float)affine_row(xf + 4 * c, (double)g3[0], (double)g3[1], (double)g3[2]);
+        const float m = c == 0 ? mid[0] : (c == 1 ? mid[1] : mid[2]);
+        const float u = ok ? __fadd_rn(__fdiv_rn(__fsub_rn(v, m), max_l), 0.5f) : 0.5f;
+        t = __fsub_rn(u, mean[e]);
+      }
+      const int cnt = nc - c0 < 64 ? nc - c0 : 64;
+      const float *w = W + (int64_t)c0 * nc + kc;
+      // 16 coefficients are loaded before the 16 dependent adds that use them, by UNCONDITIONAL loads of clamped (valid)
+      // addresses: a guarded load becomes a branch with its own vmcnt(0) wait, one L2 round trip per coordinate.  Fixed
+      // trip counts around the convergent v_readlane; past cnt the term is +0 * +0, which leaves p unchanged (p is
+      // never -0).
+      for (int i0 = 0; i0 < 64; i0 += 16) {
+        float wv[16];
+#pragma unroll
+        for (int q = 0; q < 16; ++q) {
+          const int i = i0 + q < cnt ? i0 + q : cnt - 1;
+          const float v = w[(int64_t)i * nc];
+          wv[q] = i0 + q < cnt ? v : 0.f;
+        }
+#pragma unroll
+        for (int q = 0; q < 16; ++q) {
+          const float ti = __uint_as_float(__builtin_amdgcn_readlane(__float_as_uint(t), i0 + q));
+          p = __dadd_rn(p, __dmul_rn((double)ti, (double)wv[q]));   // exact product, one rounding
+        }
+      }
+    }
+    if (kin) out[k] = (float)p;
+  }
+}
+
+template <bool PCA>
 __device__ __forceinline__ void write_labels(const KArgs &a, int frame, int64_t src, const Grid &g, int status,
                                              const double *xf, int tid, int T) {
   if (!a.gt) return;
   const int nc = 3 * a.n_joints;
+  if constexpr (PCA)   // (the projection uses the unclamped labels, whatever a.clamp says)
+    pca_project(a.gt + src * nc, xf, g.mid, g.max_l, status == TSDF_FRAME_OK, a.pca_mean, a.pca_coeff, nc, a.pca_k,
+                a.gt_pca + (int64_t)frame * a.pca_k, tid, T);
   for (int e = tid; e < nc; e += T) {
     const int c = e % 3;
     const float *gj = a.gt + src * nc + (e - c);

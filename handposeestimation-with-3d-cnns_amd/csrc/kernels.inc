@@ -1,5 +1,6 @@
 // kernels.inc — part of the one translation unit tsdf_hip.hip (included there, inside its anonymous namespace).
-// The kernels: tsdf_fused_kernel (persistent, one workgroup per CU), tsdf_split_kernel (small batches), tsdf_normalize_kernel (labels alone).
+// The kernels: tsdf_fused_kernel (persistent, one workgroup per CU), tsdf_split_kernel (small batches), tsdf_normalize_kernel (labels alone),
+// tsdf_project_kernel (joint-PCA projection alone), tsdf_pose_error_kernel (decode + per-joint error).
 
 // Persistent kernel, one 1024-thread workgroup per CU.  Its two 512-thread groups each walk their own
 // frames through
@@ -10,7 +11,9 @@
 // (The read-only inputs are passed as separate __restrict__ parameters as well as inside KArgs: alias information
 // does not survive a by-value struct, and without it the compiler may not use scalar loads for wave-uniform
 // reads — the per-frame transform of the augmented form became 700 vector loads in the unrolled row pass.)
-template <int RT, int LAYOUT, bool AUG, bool DBG, int GROUPS>
+// PCA: the joint-PCA projection rides on the labels (tsdf_pca) — a compile-time variant, so that the instantiations
+// without it compile to exactly what they were.
+template <int RT, int LAYOUT, bool AUG, bool DBG, int GROUPS, bool PCA>
 __global__ __launch_bounds__(kWG) void tsdf_fused_kernel(const KArgs a, const float *__restrict__ in_depth,
                                                          const int64_t *__restrict__ in_offsets,
                                                          const int32_t *__restrict__ in_headers,
@@ -122,7 +125,7 @@ __global__ __launch_bounds__(kWG) void tsdf_fused_kernel(const KArgs a, const fl
     }
 
     if (gtid == 0) write_frame_outputs(a, frame, g, ab, status);
-    write_labels(a, frame, fh.src, g, status, xf, gtid, kGW);
+    write_labels<PCA>(a, frame, fh.src, g, status, xf, gtid, kGW);
 
     if (want_vol) {
       if (status != TSDF_FRAME_OK) {
@@ -291,7 +294,7 @@ __global__ __launch_bounds__(kWG) void tsdf_fused_kernel(const KArgs a, const fl
 // L2 hits).  The mailboxes are a per-stream slice of a device global owned by the library (host: xchg_for());
 // launches that cannot have one (stream capture, too many streams) use the redundant form.
 
-template <int RT, int LAYOUT, bool AUG, bool XCHG>
+template <int RT, int LAYOUT, bool AUG, bool XCHG, bool PCA>
 __global__ __launch_bounds__(kWG) void tsdf_split_kernel(const KArgs a, const float *__restrict__ in_depth,
                                                          const int64_t *__restrict__ in_offsets,
                                                          const int32_t *__restrict__ in_headers,
@@ -416,7 +419,7 @@ __global__ __launch_bounds__(kWG) void tsdf_split_kernel(const KArgs a, const fl
   TSDF_STAMP(0, 4);
   if (part == 0) {
     if (tid == 0) write_frame_outputs(a, frame, g, ab, status);
-    write_labels(a, frame, fh.src, g, status, xf, tid, kWG);
+    write_labels<PCA>(a, frame, fh.src, g, status, xf, tid, kWG);
   }
   if (!want_vol) return;
   if (status != TSDF_FRAME_OK) {
@@ -488,3 +491,109 @@ __global__ void tsdf_normalize_kernel(const float *__restrict__ gt, const float 
 }
 
 
+
+// Joint PCA projection from labels already on the device (tsdf_project_joints_hip): one wave per (frame, 64 components),
+// the arithmetic of the fused form (pca_project); a frame with max_l == 0 is "not OK" (its labels are 0.5, include/tsdf.h).
+__global__ void __launch_bounds__(64) tsdf_project_kernel(const float *__restrict__ gt, const float *__restrict__ max_l,
+                                                          const float *__restrict__ mid_p, int nc,
+                                                          const float *__restrict__ mean, const float *__restrict__ W,
+                                                          int K, int kchunks, float *__restrict__ out) {
+  const int64_t frame = blockIdx.x / kchunks;
+  const int chunk = (int)(blockIdx.x - frame * kchunks);
+  const float ml = max_l[frame];
+  const float mid[3] = {mid_p[3 * frame], mid_p[3 * frame + 1], mid_p[3 * frame + 2]};
+  pca_project(gt + frame * nc, nullptr, mid, ml, ml > 0.f, mean, W, nc, K, out + frame * K, 64 * chunk + threadIdx.x,
+              64 * kchunks);
+}
+
+// Pose error (tsdf_pose_error_hip, include/tsdf.h item 4): one wave per frame, lane <-> joint (J <= 170: three rounds);
+// lane 0 then reduces the frame's errors from LDS in ascending joint order.  No atomics: deterministic.
+constexpr int kPoseWaves = 4;
+struct PoseArgs {
+  const float *pred, *mean, *W, *max_l, *mid_p, *gt;
+  float *err, *fmean, *fmax, *joints;
+  int64_t n;
+  int nj, K;  // K == 0: pred holds normalised coordinates
+};
+
+__global__ void __launch_bounds__(64 * kPoseWaves) tsdf_pose_error_kernel(PoseArgs a) {
+  __shared__ float s_err[kPoseWaves][170];
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int64_t frame = (int64_t)blockIdx.x * kPoseWaves + wave;
+  const bool live = frame < a.n;
+  const int nc = 3 * a.nj;
+  // (frames past n run the loops on clamped indices and store nothing: the lanes of a wave stay together for v_readlane)
+  const int64_t fr = live ? frame : a.n - 1;
+  const float ml = a.max_l[fr];
+  for (int j0 = 0; j0 < a.nj; j0 += 64) {
+    const int j = j0 + lane;
+    const bool act = live && j < a.nj;
+    const int jr = j < a.nj ? j : a.nj - 1;
+    float uh[3];
+    if (a.K) {
+      const float *p = a.pred + fr * a.K;
+      double acc[3];
+#pragma unroll
+      for (int c = 0; c < 3; ++c) acc[c] = (double)a.mean[3 * jr + c];
+      for (int k0 = 0; k0 < a.K; k0 += 64) {
+        const float pk = k0 + lane < a.K ? p[k0 + lane] : 0.f;
+        const int cnt = a.K - k0 < 64 ? a.K - k0 : 64;
+        const float *w = a.W + (int64_t)(3 * jr) * nc + k0;
+        // 8 components' coefficients are loaded before the adds that use them, by unconditional loads of clamped (valid)
+        // addresses (a guarded load becomes a branch with its own vmcnt(0) wait); fixed trip counts around the
+        // convergent v_readlane; past cnt the term is +0 * +0 (value unchanged)
+        for (int i0 = 0; i0 < 64; i0 += 8) {
+          float wv[3][8];
+#pragma unroll
+          for (int q = 0; q < 8; ++q) {
+            const int i = i0 + q < cnt ? i0 + q : cnt - 1;
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+              const float v = w[(int64_t)c * nc + i];
+              wv[c][q] = i0 + q < cnt ? v : 0.f;
+            }
+          }
+#pragma unroll
+          for (int q = 0; q < 8; ++q) {
+            const double pv = (double)__uint_as_float(__builtin_amdgcn_readlane(__float_as_uint(pk), i0 + q));
+#pragma unroll
+            for (int c = 0; c < 3; ++c) acc[c] = __dadd_rn(acc[c], __dmul_rn(pv, (double)wv[c][q]));
+          }
+        }
+      }
+#pragma unroll
+      for (int c = 0; c < 3; ++c) uh[c] = (float)acc[c];
+    } else {
+#pragma unroll
+      for (int c = 0; c < 3; ++c) uh[c] = a.pred[fr * nc + 3 * jr + c];
+    }
+    float d[3];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      const int jc = 3 * jr + c;
+      const float m = a.mid_p[3 * fr + c];
+      const float x = ml > 0.f ? __fadd_rn(__fmul_rn(__fsub_rn(uh[c], 0.5f), ml), m) : m;
+      if (act && a.joints) a.joints[fr * nc + jc] = x;
+      d[c] = __fsub_rn(x, a.gt[fr * nc + jc]);
+    }
+    // __builtin_sqrtf: correctly rounded under this build's flags (__fsqrt_rn is the native approximation here)
+    const float e = __builtin_sqrtf(__fadd_rn(__fadd_rn(__fmul_rn(d[0], d[0]), __fmul_rn(d[1], d[1])),
+                                              __fmul_rn(d[2], d[2])));
+    if (act) {
+      a.err[fr * a.nj + j] = e;
+      s_err[wave][j] = e;
+    }
+  }
+  __syncthreads();
+  if (live && lane == 0) {
+    double s = 0.0;
+    float mx = s_err[wave][0];
+    for (int j = 0; j < a.nj; ++j) {
+      const float e = s_err[wave][j];
+      s = __dadd_rn(s, (double)e);
+      mx = e > mx ? e : mx;
+    }
+    a.fmean[frame] = (float)(s / (double)a.nj);
+    a.fmax[frame] = mx;
+  }
+}

@@ -76,7 +76,7 @@ int xchg_polls() {
 #endif
 }
 
-template <int RT, int LAYOUT, bool AUG, bool DBG>
+template <int RT, int LAYOUT, bool AUG, bool DBG, bool PCA = false>
 hipError_t launch(hipStream_t s, KArgs &a, int dev) {
   const int cus = num_cus();
   if constexpr (!DBG) {
@@ -89,10 +89,10 @@ hipError_t launch(hipStream_t s, KArgs &a, int dev) {
       a.xchg = a.n <= kXchgFrames ? xchg_for(dev, s, &a.seq) : nullptr;
       a.polls = xchg_polls();
       if (a.xchg) {
-        hipLaunchKernelGGL((tsdf_split_kernel<RT, LAYOUT, AUG, true>), dim3(a.n * S), dim3(kWG), 0, s, a, a.depth,
+        hipLaunchKernelGGL((tsdf_split_kernel<RT, LAYOUT, AUG, true, PCA>), dim3(a.n * S), dim3(kWG), 0, s, a, a.depth,
                            a.offsets, a.headers, a.xforms);
       } else {
-        hipLaunchKernelGGL((tsdf_split_kernel<RT, LAYOUT, AUG, false>), dim3(a.n * S), dim3(kWG), 0, s, a, a.depth,
+        hipLaunchKernelGGL((tsdf_split_kernel<RT, LAYOUT, AUG, false, PCA>), dim3(a.n * S), dim3(kWG), 0, s, a, a.depth,
                            a.offsets, a.headers, a.xforms);
       }
       return hipGetLastError();
@@ -105,7 +105,7 @@ hipError_t launch(hipStream_t s, KArgs &a, int dev) {
   auto fused = [&](auto groups_tag) {
     constexpr int G = decltype(groups_tag)::value;
     a.queue = a.n > grid * G ? queue_word(dev, s, &a.qepoch) : nullptr;  // no dynamic frames: no word needed
-    hipLaunchKernelGGL((tsdf_fused_kernel<RT, LAYOUT, AUG, DBG, G>), dim3(grid), dim3(kWG), 0, s, a, a.depth, a.offsets,
+    hipLaunchKernelGGL((tsdf_fused_kernel<RT, LAYOUT, AUG, DBG, G, PCA>), dim3(grid), dim3(kWG), 0, s, a, a.depth, a.offsets,
                        a.headers, a.xforms);
   };
   if constexpr (RT != 0) {
@@ -119,11 +119,11 @@ hipError_t launch(hipStream_t s, KArgs &a, int dev) {
 
 // The resolutions of the BASELINE configs get instantiations of their own (R a compile-time constant), every other
 // one the generic instantiation.
-template <int LAYOUT, bool AUG>
+template <int LAYOUT, bool AUG, bool PCA = false>
 hipError_t launch_r(hipStream_t s, KArgs &a, int dev) {
-  if (a.R == 32) return launch<32, LAYOUT, AUG, false>(s, a, dev);
-  if (a.R == 64) return launch<64, LAYOUT, AUG, false>(s, a, dev);
-  return launch<0, LAYOUT, AUG, false>(s, a, dev);
+  if (a.R == 32) return launch<32, LAYOUT, AUG, false, PCA>(s, a, dev);
+  if (a.R == 64) return launch<64, LAYOUT, AUG, false, PCA>(s, a, dev);
+  return launch<0, LAYOUT, AUG, false, PCA>(s, a, dev);
 }
 
 struct RunOpts {
@@ -136,6 +136,7 @@ struct RunOpts {
   const int64_t *index = nullptr;  // indexed entry
   int64_t n_src = 0;
   const int64_t *h_index = nullptr;  // indexed entry, index in HOST memory, copied into the kernel arguments
+  const tsdf_pca *pca = nullptr;     // joint PCA projection fused into the labels (requires labels)
 };
 
 int run(const float *d_depth, int64_t depth_len, const int64_t *d_offsets, const int32_t *d_headers, int n, int R,
@@ -188,6 +189,12 @@ int run(const float *d_depth, int64_t depth_len, const int64_t *d_offsets, const
     a.n_joints = o.labels->n_joints;
     a.clamp = o.labels->clamp;
   }
+  if (o.pca) {
+    a.pca_mean = o.pca->d_mean;
+    a.pca_coeff = o.pca->d_coeff;
+    a.gt_pca = o.pca->d_out_gt_pca;
+    a.pca_k = o.pca->n_components;
+  }
   a.pixmap = o.pixmap;
   hipStream_t s = static_cast<hipStream_t>(hip_stream);
   hipError_t e;
@@ -200,6 +207,10 @@ int run(const float *d_depth, int64_t depth_len, const int64_t *d_offsets, const
 #else
     return TSDF_ERR_INVALID_ARG;
 #endif
+  } else if (a.pca_k && o.xforms) {   // (the joint-PCA variants: labels + projection)
+    e = layout == TSDF_LAYOUT_CZYX ? launch_r<0, true, true>(s, a, dev) : launch_r<1, true, true>(s, a, dev);
+  } else if (a.pca_k) {
+    e = layout == TSDF_LAYOUT_CZYX ? launch_r<0, false, true>(s, a, dev) : launch_r<1, false, true>(s, a, dev);
   } else if (o.xforms) {
     e = layout == TSDF_LAYOUT_CZYX ? launch_r<0, true>(s, a, dev) : launch_r<1, true>(s, a, dev);
   } else {
@@ -225,3 +236,50 @@ int run_normalize(const float *d_in, const float *d_max_l, const float *d_mid_p,
   return hipGetLastError() == hipSuccess ? TSDF_OK : TSDF_ERR_LAUNCH;
 }
 
+
+// tsdf_project_joints_hip: one wave per (frame, 64 components).
+int run_project(const float *d_gt, const float *d_max_l, const float *d_mid_p, int n, int n_joints, const tsdf_pca *pca,
+                void *hip_stream) {
+  if (n < 0 || tsdf_host::check_pca(pca, n, n_joints, true) != TSDF_OK) return TSDF_ERR_INVALID_ARG;
+  if (n == 0) return TSDF_OK;
+  if (!d_gt || !d_max_l || !d_mid_p) return TSDF_ERR_INVALID_ARG;
+  int dev = 0;
+  const int rc = check_device(&dev);
+  if (rc != TSDF_OK) return rc;
+  const int K = pca->n_components, kchunks = (K + 63) / 64;
+  const int64_t blocks = (int64_t)n * kchunks;
+  if (blocks > 0x7fffffff) return TSDF_ERR_INVALID_ARG;
+  hipLaunchKernelGGL(tsdf_project_kernel, dim3((unsigned)blocks), dim3(64), 0, static_cast<hipStream_t>(hip_stream), d_gt,
+                     d_max_l, d_mid_p, 3 * n_joints, pca->d_mean, pca->d_coeff, K, kchunks, pca->d_out_gt_pca);
+  return hipGetLastError() == hipSuccess ? TSDF_OK : TSDF_ERR_LAUNCH;
+}
+
+// tsdf_pose_error_hip: one wave per frame.
+int run_pose_error(const float *d_pred, const tsdf_pca *pca, const float *d_max_l, const float *d_mid_p, const float *d_gt,
+                   int n, int n_joints, void *hip_stream, float *d_err, float *d_fmean, float *d_fmax, float *d_joints) {
+  if (n < 0 || n_joints < 1 || n_joints > 170) return TSDF_ERR_INVALID_ARG;
+  if (pca && tsdf_host::check_pca(pca, n, n_joints, false) != TSDF_OK) return TSDF_ERR_INVALID_ARG;
+  if (n == 0) return TSDF_OK;
+  if (!d_pred || !d_max_l || !d_mid_p || !d_gt || !d_err || !d_fmean || !d_fmax) return TSDF_ERR_INVALID_ARG;
+  int dev = 0;
+  const int rc = check_device(&dev);
+  if (rc != TSDF_OK) return rc;
+  PoseArgs a;
+  a.pred = d_pred;
+  a.mean = pca ? pca->d_mean : nullptr;
+  a.W = pca ? pca->d_coeff : nullptr;
+  a.K = pca ? pca->n_components : 0;
+  a.max_l = d_max_l;
+  a.mid_p = d_mid_p;
+  a.gt = d_gt;
+  a.err = d_err;
+  a.fmean = d_fmean;
+  a.fmax = d_fmax;
+  a.joints = d_joints;
+  a.n = n;
+  a.nj = n_joints;
+  const int blocks = (n + kPoseWaves - 1) / kPoseWaves;
+  hipLaunchKernelGGL(tsdf_pose_error_kernel, dim3((unsigned)blocks), dim3(64 * kPoseWaves), 0,
+                     static_cast<hipStream_t>(hip_stream), a);
+  return hipGetLastError() == hipSuccess ? TSDF_OK : TSDF_ERR_LAUNCH;
+}

@@ -50,7 +50,7 @@
 //   phase2.inc   the voxel pass, plain and augmented; gather sources, projection tables, volume stores
 //   frame.inc    kernel arguments, LDS layout, group barrier, per-frame helpers, LDS-DMA staging, table fill
 //   queue.inc    per-(device, stream) work-queue words and exchange mailboxes, device and host side
-//   kernels.inc  tsdf_fused_kernel, tsdf_split_kernel, tsdf_normalize_kernel
+//   kernels.inc  tsdf_fused_kernel, tsdf_split_kernel, tsdf_normalize_kernel, tsdf_project_kernel, tsdf_pose_error_kernel
 //   launch.inc   host side of a call: device check, split plan, instantiation choice, argument marshalling
 //   abi.inc      extern "C" — include/tsdf.h (and, under -DTSDF_DEBUG_HOOKS, include/tsdf_debug.h)
 //   tsdf_host.inc  host-only helpers, also compiled alone under the CPU sanitizers
@@ -83,7 +83,7 @@ namespace {
 #include "phase2.inc"    // the voxel pass, plain and augmented
 #include "frame.inc"     // kernel arguments, LDS layout, per-frame helpers, staging, tables
 #include "queue.inc"     // work-queue words and exchange mailboxes (device + host side)
-#include "kernels.inc"   // tsdf_fused_kernel, tsdf_split_kernel, tsdf_normalize_kernel
+#include "kernels.inc"   // tsdf_fused_kernel, tsdf_split_kernel, tsdf_normalize_kernel, PCA / pose error
 #include "launch.inc"    // host side of a call
 
 }  // namespace

@@ -95,6 +95,15 @@ inline int check_run_args(const void *d_depth, int64_t depth_len, const void *d_
   return TSDF_OK;
 }
 
+// ---- the joint-PCA descriptor (include/tsdf.h, tsdf_pca) for n frames of n_joints joints ------------------------------
+// need_out: the entry writes d_out_gt_pca (every entry but tsdf_pose_error_hip).
+inline int check_pca(const tsdf_pca *pca, int n, int n_joints, bool need_out) {
+  if (!pca || n_joints < 1 || n_joints > 170) return TSDF_ERR_INVALID_ARG;
+  if (pca->n_components < 1 || pca->n_components > 3 * n_joints) return TSDF_ERR_INVALID_ARG;
+  if (n > 0 && (!pca->d_mean || !pca->d_coeff || (need_out && !pca->d_out_gt_pca))) return TSDF_ERR_INVALID_ARG;
+  return TSDF_OK;
+}
+
 // ---- per-stream slots -------------------------------------------------------------------------------------------------
 // Launches of one stream execute in order, so a device word owned by the stream is never shared by two running launches,
 // however many are in flight.  hipStreamPerThread is one handle for a different stream per thread: it is keyed by the

@@ -673,6 +673,9 @@ class _SlotGuard:
 
     def counts(self):
         rc, uc, b, c = sys.getrefcount, _storage_use_count, self.batch, self._cdata
+        if len(c) == 5:   # (full mode: the batch also carries gt_pca, which a consumer may hold on its own)
+            return (rc(b), rc(b[0]), rc(b[1]), rc(b[2]), rc(b[3]), rc(b[4]), uc(c[0]), uc(c[1]), uc(c[2]), uc(c[3]),
+                    uc(c[4]))
         return (rc(b), rc(b[0]), rc(b[1]), rc(b[2]), rc(b[3]), uc(c[0]), uc(c[1]), uc(c[2]), uc(c[3]))
 
     def arm(self):
@@ -751,7 +754,7 @@ class MSRA_Dataset(data.Dataset):
 
     def __init__(self, root_path, opt=None, train=True, aug=False, device="cuda", block: int = 1024,
                  packed_dir: Optional[str] = None, resident: Optional[bool] = None, prebatched: Optional[bool] = None,
-                 ring: Optional[int] = None, aug_seed: int = 0, _raw: Optional[MSRADepthDataset] = None):
+                 ring: Optional[int] = None, aug_seed: int = 0, _raw: Optional[MSRADepthDataset] = None, pca=None):
         self.AUG = bool(aug)
         self.aug_seed = aug_seed
         self.size = getattr(opt, "size", "small")
@@ -781,6 +784,25 @@ class MSRA_Dataset(data.Dataset):
         if self.AUG:
             from . import augment as _aug
             self._aug_params = _aug.draw_params(self._n, aug_seed)
+        # full mode (3D_CNN/dataset.py:165-180): the joint-PCA basis, and gt_pca as the item's fifth element
+        self.pca = None
+        self._cache_pca: Optional[torch.Tensor] = None
+        if pca is not None and pca is not False:
+            from .pca import JointPCA, fit_joint_pca
+            if pca is True:
+                if not train:
+                    raise ValueError("pca=True fits on a TRAINING dataset; pass the training set's basis (its .pca, a "
+                                     "JointPCA or a path) to a test dataset")
+                basis = fit_joint_pca(self)
+            elif isinstance(pca, JointPCA):
+                basis = pca
+            else:
+                basis = JointPCA.load(os.fspath(pca))
+            basis.check_k(self.PCA_SZ)
+            self.pca = basis.to(self.device)
+            # the shapes with which the reference's own decode, torch.addmm(PCA_mean.expand(b, C), est, PCA_coeff)
+            # (3D_CNN/train.py:221-225), is mu + p W^T
+            self.PCA_mean, self.PCA_coeff = basis.torch_decode_args(self.PCA_SZ, self.device)
 
     @classmethod
     def from_raw(cls, raw: MSRADepthDataset, device="cuda", **kw) -> "MSRA_Dataset":
@@ -820,17 +842,66 @@ class MSRA_Dataset(data.Dataset):
         out, _, gt_aug = voxelize_aug(depth, offsets, headers, torch.from_numpy(xf).to(self.device), res=32, gt=gt)
         return out, gt_aug
 
+    def _fit_labels(self) -> np.ndarray:
+        """The normalised labels (no clamp) of every item whose frame status is OK, float32[N, C] on the host, in item
+        order — what :func:`pca.fit_joint_pca` fits.  Plain items: the grid placement of the AABB launch (bit-identical
+        to the voxelizer's); augmented items: the augmented entry's own labels."""
+        from .voxelize import aabb, normalize_joints
+        n, dev, us = self._n, self.device, []
+        if self.resident:
+            rp = self._resident_packs()
+            ab = aabb(rp.depth, rp.offsets, rp.headers)
+            fr = torch.from_numpy(rp.frame).to(dev)
+            grid, st, gt = ab.grid[fr], ab.status[fr], rp.gt[fr]
+            u = normalize_joints(gt.contiguous(), grid[:, 3].contiguous(), grid[:, :3].contiguous(), clamp=False)
+            us.append(u[st == 0].cpu().numpy())
+        else:
+            for a in range(0, n, self.block):
+                pk = self.raw.take(np.arange(a, min(n, a + self.block)))
+                depth, offsets, headers = pk.to_torch(dev, pin=False, non_blocking=False)
+                ab = aabb(depth, offsets, headers)
+                gt = torch.from_numpy(np.ascontiguousarray(pk.gt)).to(dev)
+                u = normalize_joints(gt, ab.grid[:, 3].contiguous(), ab.grid[:, :3].contiguous(), clamp=False)
+                us.append(u[ab.status == 0].cpu().numpy())
+        if self.AUG:
+            for a in range(n, 2 * n, self.block):
+                idx = np.arange(a, min(2 * n, a + self.block))
+                if self.resident:
+                    rp = self._rp
+                    out, u = voxelize_indexed(rp.depth, rp.offsets, rp.headers,
+                                              torch.from_numpy(self._frame2[idx]).to(dev), rp.gt, clamp=False,
+                                              xforms=torch.from_numpy(self._xf_table[idx]).to(dev))
+                else:
+                    out, gt_aug = self._aug_batch_host_fed(idx)
+                    u = normalize_joints(gt_aug, out.max_l, out.mid_p, clamp=False)
+                us.append(u[out.status == 0].cpu().numpy())
+        return np.concatenate(us) if us else np.zeros((0, 63), np.float32)
+
+    def _with_pca(self, gt, max_l, mid_p):
+        """gt_pca of labels already on the device (``project_joints``: the paths that are not fused)."""
+        from .voxelize import project_joints
+        return project_joints(gt.contiguous(), max_l, mid_p, self.pca, self.PCA_SZ)
+
+    def _tuples(self, out, gt, gt_pca, m: int):
+        if gt_pca is None:
+            return [(out.tsdf[k], gt[k], out.max_l[k], out.mid_p[k]) for k in range(m)]
+        return [(out.tsdf[k], gt[k], out.max_l[k], out.mid_p[k], gt_pca[k]) for k in range(m)]
+
     def _load_block(self, blk: int):
         a, b = blk * self.block, min(len(self.raw), (blk + 1) * self.block)
         if self.resident:
             rp = self._resident_packs()
-            self._cache, _, self._cache_gt = voxelize_indexed(
-                rp.depth, rp.offsets, rp.headers, torch.from_numpy(rp.frame[a:b]).to(self.device), rp.gt, gt_copy=True)
+            r = voxelize_indexed(rp.depth, rp.offsets, rp.headers, torch.from_numpy(rp.frame[a:b]).to(self.device), rp.gt,
+                                 gt_copy=True, pca=self.pca, k=self.PCA_SZ if self.pca is not None else None)
+            self._cache, self._cache_gt = r[0], r[2]
+            self._cache_pca = r[3] if self.pca is not None else None
         else:
             pk = self.raw.take(np.arange(a, b))
             depth, offsets, headers = pk.to_torch(self.device, pin=False, non_blocking=False)
             self._cache = voxelize(depth, offsets, headers, res=32)
             self._cache_gt = torch.from_numpy(np.ascontiguousarray(pk.gt)).to(self.device)
+            self._cache_pca = None if self.pca is None else \
+                self._with_pca(self._cache_gt, self._cache.max_l, self._cache.mid_p)
         self._cache_block = blk
 
     # ---- the pre-batched path: one C call per batch, nothing allocated, nothing sliced ----
@@ -852,8 +923,9 @@ class MSRA_Dataset(data.Dataset):
         tensors: slower, never wrong."""
 
         kGroup = 16
+        pca, k = None, 0   # (class defaults: full mode is set per instance)
 
-        def __init__(self, rp: "ResidentPacks", bs: int, ring: int, device, frame=None, xf_table=None):
+        def __init__(self, rp: "ResidentPacks", bs: int, ring: int, device, frame=None, xf_table=None, pca=None, k=0):
             import ctypes
             from . import _lib
             self._ctypes, self._lib = ctypes, _lib
@@ -862,6 +934,7 @@ class MSRA_Dataset(data.Dataset):
             self.iring = -(-max(ring, self.kGroup) // self.kGroup) * self.kGroup   # index slots: whole event groups
             self.bs, self.ring, self.count, self.replaced = bs, ring, 0, 0
             self.L = _lib.load()
+            self.pca, self.k = pca, int(k)   # full mode: the fused projection writes each slot's gt_pca too
             self.rp_gt = rp.gt
             self.nc = rp.gt.shape[1]
             d = torch.device(device)
@@ -875,7 +948,8 @@ class MSRA_Dataset(data.Dataset):
                          int(rp.headers.shape[0]))
             self.slots = [None] * ring      # (tsdf, gt, max_l, mid_p, status, gt_nor) — the slot's own tensors
             self.labels = [None] * ring
-            self.args = [None] * ring       # (tsdf, max_l, mid_p, status, byref(labels)) pointers of the C call
+            self.args = [None] * ring       # (tsdf, max_l, mid_p, status, byref(labels)[, byref(pca)]) of the C call
+            self.pcas = [None] * ring       # full mode: the slot's tsdf_pca
             self.results = [None] * ring    # [PreBatched((tsdf, gt, max_l, mid_p))]
             self.guard = [None] * ring      # _SlotGuard of the slot's batch
             for k in range(ring):
@@ -887,17 +961,21 @@ class MSRA_Dataset(data.Dataset):
                 (lambda i: torch.cuda.current_stream(i).cuda_stream)
             self.cur_dev = getattr(torch._C, "_cuda_getDevice", torch.cuda.current_device)
             self.fn = self.L.tsdf_voxelize_indexed_hip
+            self.plain_xf = ()              # (the PCA entry of the page-locked path takes d_xforms = NULL first)
+            if pca is not None:
+                self.fn, self.plain_xf = self.L.tsdf_voxelize_indexed_pca_hip, (None,)
             self.take = (rp.frame if frame is None else frame).take   # dataset item -> frame of the resident packs
             # batches of at most INLINE_INDEX_MAX frames: the index goes to the GPU inside the kernel arguments
             # (tsdf_voxelize_indexed_host_hip reads it during the call) — no page-locked slot, no event, and the launch
             # does not start with a read over the link
             self.by_value = xf_table is None and bs <= _lib.INLINE_INDEX_MAX
-            self.fn_host = self.L.tsdf_voxelize_indexed_host_hip
+            self.fn_host = self.L.tsdf_voxelize_indexed_host_hip if pca is None else \
+                self.L.tsdf_voxelize_indexed_host_pca_hip
             self.idx_buf = np.empty(bs, np.int64)
             self.idx_ptr = self.idx_buf.ctypes.data
             self.xf_take = None
             if xf_table is not None:   # aug=True: one map per batch position, in page-locked memory the kernel reads
-                self.fn_aug = self.L.tsdf_voxelize_indexed_aug_hip
+                self.fn_aug = self.L.tsdf_voxelize_indexed_aug_hip if pca is None else self.L.tsdf_voxelize_indexed_pca_hip
                 self.h_xf = torch.empty((self.iring, bs, 24), dtype=torch.float64).pin_memory()
                 self.h_xf_np = self.h_xf.numpy()
                 self.xf_rows = [self.h_xf_np[k] for k in range(self.iring)]
@@ -921,7 +999,15 @@ class MSRA_Dataset(data.Dataset):
             self.labels[k] = self._lib.TsdfLabels(self.rp_gt.data_ptr(), nc // 3, 1, gt_nor.data_ptr(), gt.data_ptr())
             self.args[k] = (tsdf.data_ptr(), max_l.data_ptr(), mid_p.data_ptr(), status.data_ptr(),
                             self._ctypes.byref(self.labels[k]))
-            self.results[k] = [PreBatched((tsdf, gt, max_l, mid_p))]
+            batch = (tsdf, gt, max_l, mid_p)
+            if self.pca is not None:
+                gt_pca = torch.empty((bs, self.k), dtype=torch.float32, device=dev)
+                mean, coeff = self.pca.device_tensors(dev)
+                self.pcas[k] = self._lib.TsdfPca(mean.data_ptr(), coeff.data_ptr(), self.k, gt_pca.data_ptr())
+                self.slots[k] = self.slots[k] + (gt_pca,)
+                self.args[k] = self.args[k] + (self._ctypes.byref(self.pcas[k]),)
+                batch = batch + (gt_pca,)
+            self.results[k] = [PreBatched(batch)]
             self.guard[k] = _SlotGuard(self.results[k][0].batch)
 
         def held(self, k: int) -> bool:
@@ -957,21 +1043,21 @@ class MSRA_Dataset(data.Dataset):
             if f is not None:
                 f.sync()      # launches that read the old ring's page-locked words must be done before it goes away
             f = self._fast = MSRA_Dataset._Fast(self._rp, n, self._ring_size(n), self.device,
-                                                frame=self._frame2 if self.AUG else None, xf_table=self._xf_table)
+                                                frame=self._frame2 if self.AUG else None, xf_table=self._xf_table,
+                                                pca=self.pca, k=self.PCA_SZ)
         k = f.next_slot()
         a = f.args[k]
         if f.by_value:                        # (the epoch's short last batch, or another current device)
             f.idx_buf[:n] = f.take(indices)
             with torch.cuda.device(f.device):
-                rc = f.fn_host(*f.head, f.idx_ptr, n, 32, None, 0, f.raw_stream(f.dev_index), a[0], a[1], a[2], a[3], a[4])
+                rc = f.fn_host(*f.head, f.idx_ptr, n, 32, None, 0, f.raw_stream(f.dev_index), *a)
             if rc != 0:
                 from . import _lib
                 _lib.check(rc, "tsdf_voxelize_indexed_host_hip")
             f.count += 1
             if n == f.bs:
                 return f.results[k]
-            t = f.slots[k]
-            return [PreBatched((t[0][:n], t[1][:n], t[2][:n], t[3][:n]))]
+            return [PreBatched(tuple(t[:n] for t in f.results[k][0].batch))]
         ki = f.count % f.iring                # the index words' slot (page-locked ring of whole event groups)
         within = ki & (f.kGroup - 1)
         if within == 0 and f.read_used[ki >> 4]:
@@ -988,13 +1074,12 @@ class MSRA_Dataset(data.Dataset):
             else:
                 f.h_xf_np[ki, :n] = f.xf_take(indices, axis=0)
             with torch.cuda.device(f.device):
-                rc = f.fn_aug(*f.head, f.idx_ptrs[ki], n, 32, None, 0, f.raw_stream(f.dev_index), f.xf_ptr[ki], a[0], a[1],
-                              a[2], a[3], a[4])
+                rc = f.fn_aug(*f.head, f.idx_ptrs[ki], n, 32, None, 0, f.raw_stream(f.dev_index), f.xf_ptr[ki], *a)
         elif f.cur_dev() == f.dev_index:
-            rc = f.fn(*f.head, f.idx_ptrs[ki], n, 32, None, 0, f.raw_stream(f.dev_index), a[0], a[1], a[2], a[3], a[4])
+            rc = f.fn(*f.head, f.idx_ptrs[ki], n, 32, None, 0, f.raw_stream(f.dev_index), *f.plain_xf, *a)
         else:
             with torch.cuda.device(f.device):
-                rc = f.fn(*f.head, f.idx_ptrs[ki], n, 32, None, 0, f.raw_stream(f.dev_index), a[0], a[1], a[2], a[3], a[4])
+                rc = f.fn(*f.head, f.idx_ptrs[ki], n, 32, None, 0, f.raw_stream(f.dev_index), *f.plain_xf, *a)
         if within == f.kGroup - 1:
             f.read[ki >> 4].record(torch.cuda.current_stream(f.device))
             f.read_used[ki >> 4] = True
@@ -1004,8 +1089,7 @@ class MSRA_Dataset(data.Dataset):
         f.count += 1
         if n == f.bs:
             return f.results[k]
-        t = f.slots[k]
-        return [PreBatched((t[0][:n], t[1][:n], t[2][:n], t[3][:n]))]   # the epoch's short last batch
+        return [PreBatched(tuple(t[:n] for t in f.results[k][0].batch))]   # the epoch's short last batch
 
     def __getitems__(self, indices):
         """The frames of one batch, voxelized by one launch (torch's DataLoader calls this with the batch's indices
@@ -1022,7 +1106,7 @@ class MSRA_Dataset(data.Dataset):
             k = f.next_slot()      # (a slot whose batch the consumer still holds gets fresh tensors)
             f.take(indices, out=f.idx_buf)
             a = f.args[k]
-            rc = f.fn_host(*f.head, f.idx_ptr, f.bs, 32, None, 0, f.raw_stream(f.dev_index), a[0], a[1], a[2], a[3], a[4])
+            rc = f.fn_host(*f.head, f.idx_ptr, f.bs, 32, None, 0, f.raw_stream(f.dev_index), *a)
             if rc != 0:
                 from . import _lib
                 _lib.check(rc, "tsdf_voxelize_indexed_host_hip")
@@ -1040,26 +1124,34 @@ class MSRA_Dataset(data.Dataset):
         if idx.size and (idx.min() < 0 or idx.max() >= len(self)):
             raise IndexError(int(idx.max() if idx.max() >= len(self) else idx.min()))
         self._last = int(idx[-1]) if idx.size else self._last
+        kw = {} if self.pca is None else {"pca": self.pca, "k": self.PCA_SZ}
+        gt_pca = None
         if self.AUG:
             if self.resident:
                 rp = self._rp
                 xf = torch.from_numpy(self._xf_table[idx]).to(self.device)
-                out, _, gt = voxelize_indexed(rp.depth, rp.offsets, rp.headers,
-                                              torch.from_numpy(self._frame2[idx]).to(self.device), rp.gt, gt_copy=True,
-                                              xforms=xf)
+                r = voxelize_indexed(rp.depth, rp.offsets, rp.headers, torch.from_numpy(self._frame2[idx]).to(self.device),
+                                     rp.gt, gt_copy=True, xforms=xf, **kw)
+                out, gt = r[0], r[2]
+                gt_pca = r[3] if kw else None
             else:
                 out, gt = self._aug_batch_host_fed(idx)
-            return [(out.tsdf[k], gt[k], out.max_l[k], out.mid_p[k]) for k in range(idx.size)]
+                gt_pca = self._with_pca(gt, out.max_l, out.mid_p) if kw else None
+            return self._tuples(out, gt, gt_pca, idx.size)
         if self.resident:
             rp = self._rp
-            out, _, gt = voxelize_indexed(rp.depth, rp.offsets, rp.headers,
-                                          torch.from_numpy(rp.frame[idx]).to(self.device), rp.gt, gt_copy=True)
-            return [(out.tsdf[k], gt[k], out.max_l[k], out.mid_p[k]) for k in range(idx.size)]
+            r = voxelize_indexed(rp.depth, rp.offsets, rp.headers, torch.from_numpy(rp.frame[idx]).to(self.device), rp.gt,
+                                 gt_copy=True, **kw)
+            out, gt = r[0], r[2]
+            return self._tuples(out, gt, r[3] if kw else None, idx.size)
         pk = self.raw.take(idx)
         depth, offsets, headers = pk.to_torch(self.device, pin=False, non_blocking=False)
-        out = voxelize(depth, offsets, headers, res=32)
         gt = torch.from_numpy(np.ascontiguousarray(pk.gt)).to(self.device)
-        return [(out.tsdf[k], gt[k], out.max_l[k], out.mid_p[k]) for k in range(idx.size)]
+        if kw:   # (the labels path of the same launch, for gt_pca)
+            out, _, gt_pca = voxelize_labels(depth, offsets, headers, gt, res=32, clamp=False, **kw)
+        else:
+            out = voxelize(depth, offsets, headers, res=32)
+        return self._tuples(out, gt, gt_pca, idx.size)
 
     def _items_of(self, indices):
         """``indices`` as a list of item tuples whatever ``prebatched`` says (single-item access)."""
@@ -1084,4 +1176,6 @@ class MSRA_Dataset(data.Dataset):
         self._last = index
         k = index - blk * self.block
         c = self._cache
+        if self._cache_pca is not None:
+            return c.tsdf[k], self._cache_gt[k], c.max_l[k], c.mid_p[k], self._cache_pca[k]
         return c.tsdf[k], self._cache_gt[k], c.max_l[k], c.mid_p[k]

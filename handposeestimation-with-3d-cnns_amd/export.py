@@ -26,6 +26,10 @@ Differences from the reference writer, all deliberate and switchable:
     (3D_CNN/dataset.py:107-109 negates z of 3-D label arrays, pairing with the commented-out writer lines
     pre/read_MSRA.py:81-82 that pre-negate it; for the ``[n,63]`` array its own writer saves, ``g_t`` is undefined).
     After the reader's flip the labels are back in the camera frame (z = -depth) that ``mid_p`` lives in.
+
+``pca_dir`` adds what ``read_MSRA.main()`` ends with (``joint_pca(aug=False)``, pre/joint_pca.py): the nine
+leave-one-subject-out joint-PCA fits ``<pca_dir>/<fold>.npz``, fold t fitted on the normalised labels of every subject
+but the t-th — re-specified (``pca.py``), from the max_l / mid_p / labels already in memory.
 """
 from __future__ import annotations
 
@@ -99,18 +103,24 @@ def preprocess_tree(db_dir: str, save_dir: str, *, res: int = 32, layout: str = 
                     points_num: int = 6000, point_clouds: bool = True, gt_3d: bool = False,
                     subjects: Optional[Sequence[str]] = None, gestures: Optional[Sequence[str]] = None,
                     device="cuda", rng: Optional[np.random.Generator] = None,
-                    voxelize_fn: Optional[Callable] = None, verbose: bool = False) -> Dict[str, int]:
+                    voxelize_fn: Optional[Callable] = None, verbose: bool = False,
+                    pca_dir: Optional[str] = None) -> Dict[str, int]:
     """Replacement for ``read_MSRA.main()`` (pre/read_MSRA.py:37-140, AUG=False): voxelize a whole MSRA tree
     into ``save_dir`` in the reference's schema.  Returns ``{subject: frames}``.
 
     ``voxelize_fn(pack, res, layout, device) -> (tsdf, max_l, mid_p, status)`` may replace the HIP call
     (tests use it to check the file handling without a GPU); by default the HIP voxelizer runs and a
-    missing library or device is an error."""
+    missing library or device is an error.
+
+    ``pca_dir``: also write the joint-PCA fits of the first nine subjects' leave-one-out folds there (``pca.JointPCA``
+    files, ``<fold>.npz``): the labels are normalised with each frame's own max_l / mid_p (no clamp) and frames whose
+    status is not OK are left out."""
     vox = voxelize_fn if voxelize_fn is not None else _default_voxelize
     os.makedirs(save_dir, exist_ok=True)
     subs = list(subjects) if subjects is not None else sorted(
         d for d in os.listdir(db_dir) if os.path.isdir(os.path.join(db_dir, d)))
     totals: Dict[str, int] = {}
+    labels: Dict[str, list] = {}   # pca_dir: the normalised labels of the OK frames, per subject
     for sub in subs:
         sub_in, sub_out = os.path.join(db_dir, sub), os.path.join(save_dir, sub)
         ges_list = list(gestures) if gestures is not None else sorted(
@@ -121,6 +131,10 @@ def preprocess_tree(db_dir: str, save_dir: str, *, res: int = 32, layout: str = 
             bin_num, gt = packing.read_joint(g_dir)
             pk = packing.pack_bin_files(packing.gesture_bin_paths(g_dir, bin_num))
             tsdf, max_l, mid_p, status = vox(pk, res, layout, device)
+            if pca_dir is not None:
+                from .pca import normalize_labels_np
+                ok = np.asarray(max_l, np.float32) > 0 if status is None else np.asarray(status) == 0
+                labels.setdefault(sub, []).append(normalize_labels_np(gt, max_l, mid_p)[ok])
             pc = resample_point_clouds(pk, points_num, rng) if point_clouds else None
             write_gesture(sub_out, ges, np.asarray(tsdf, dtype), np.asarray(max_l, dtype),
                           np.asarray(mid_p, dtype), gt, status, pc, gt_3d)
@@ -129,4 +143,10 @@ def preprocess_tree(db_dir: str, save_dir: str, *, res: int = 32, layout: str = 
                 print("%s-%s files saved." % (sub, ges))
         np.save(os.path.join(save_dir, "data_num-%s.npy" % sub), total)
         totals[sub] = total
+    if pca_dir is not None:
+        from .pca import fit_labels
+        folds = subs[:9]   # (pre/joint_pca.py:17: sorted(os.listdir(result))[:9])
+        for t in range(len(folds)):
+            u = [x for s in folds if s != folds[t] for x in labels.get(s, [])]
+            fit_labels(np.concatenate(u) if u else np.zeros((0, 63), np.float32), fold=t).save(pca_dir)
     return totals

@@ -163,7 +163,7 @@ def voxelize(depth: torch.Tensor, offsets: torch.Tensor, headers: torch.Tensor, 
 def voxelize_labels(depth: torch.Tensor, offsets: torch.Tensor, headers: torch.Tensor, gt: torch.Tensor,
                     res: int = 32, layout: str = "czyx", cam: Optional[_lib.TsdfCam] = None, clamp: bool = True,
                     out: Optional[TsdfBatch] = None, out_gt_nor: Optional[torch.Tensor] = None,
-                    gt_copy: bool = False):
+                    gt_copy: bool = False, pca=None, k: Optional[int] = None):
     """:func:`voxelize` plus the label normalisation of the same launch: ``(gt - mid_p) / max_l + 0.5`` per
     joint coordinate (pre/joint_nor.py:8-18), clamped to [0,1] as 3D_CNN/train.py:241-242 does (``clamp``).
     gt float32[n,63] (or [n,J,3]) on the GPU.  Returns ``(TsdfBatch, gt_nor)``; frames whose status is not 0
@@ -171,28 +171,40 @@ def voxelize_labels(depth: torch.Tensor, offsets: torch.Tensor, headers: torch.T
 
     ``offsets``, ``headers`` and ``gt`` may be pinned CPU tensors (read by the kernel over the link; they must not
     change before the launch has finished); ``gt_copy=True`` then also returns the joints as a device tensor,
-    written by the same launch: ``(TsdfBatch, gt_nor, gt_on_device)``."""
+    written by the same launch: ``(TsdfBatch, gt_nor, gt_on_device)``.
+
+    ``pca`` (a :class:`pca.JointPCA`) and ``k`` (default: every component it holds) add the joint-PCA projection of the
+    unclamped labels to the same launch (``tsdf_voxelize_labels_pca_hip``): ``gt_pca`` float32[n, k] is appended to the
+    returned tuple."""
     L = _lib.load()
     dev, n, R = _check_inputs(L, depth, offsets, headers, res, layout)
     out = _make_out(out, n, R, dev)
     lab, gt_nor, gt_dev = _labels_struct(gt, n, dev, clamp, out_gt_nor, want_aug=gt_copy)
+    pst = gt_pca = None
+    if pca is not None:
+        pst, gt_pca = _pca_struct(pca, k, n, lab.n_joints, dev)
+    res_t = ((out, gt_nor, gt_dev) if gt_copy else (out, gt_nor)) + ((gt_pca,) if pca is not None else ())
     if n == 0:
-        return (out, gt_nor, gt_dev) if gt_copy else (out, gt_nor)
+        return res_t
     with _Current(dev):
         stream = _raw_stream(dev)
-        rc = L.tsdf_voxelize_labels_hip(depth.data_ptr(), depth.numel(), offsets.data_ptr(), headers.data_ptr(), n, R,
-                                        ctypes.byref(cam) if cam is not None else None, _lib.LAYOUTS[layout], stream,
-                                        out.tsdf.data_ptr(), out.max_l.data_ptr(), out.mid_p.data_ptr(),
-                                        out.status.data_ptr(), ctypes.byref(lab))
+        head = (depth.data_ptr(), depth.numel(), offsets.data_ptr(), headers.data_ptr(), n, R,
+                ctypes.byref(cam) if cam is not None else None, _lib.LAYOUTS[layout], stream)
+        tail = (out.tsdf.data_ptr(), out.max_l.data_ptr(), out.mid_p.data_ptr(), out.status.data_ptr(), ctypes.byref(lab))
+        if pst is None:
+            rc = L.tsdf_voxelize_labels_hip(*head, *tail)
+        else:
+            rc = L.tsdf_voxelize_labels_pca_hip(*head, None, *tail, ctypes.byref(pst))
     _lib.check(rc, "tsdf_voxelize_labels_hip")
-    return (out, gt_nor, gt_dev) if gt_copy else (out, gt_nor)
+    return res_t
 
 
 def voxelize_indexed(depth: torch.Tensor, offsets: torch.Tensor, headers: torch.Tensor, index: torch.Tensor,
                      gt: Optional[torch.Tensor] = None, res: int = 32, layout: str = "czyx",
                      cam: Optional[_lib.TsdfCam] = None, clamp: bool = True, out: Optional[TsdfBatch] = None,
                      gt_copy: bool = False, xforms: Optional[torch.Tensor] = None,
-                     out_gt_nor: Optional[torch.Tensor] = None, out_gt: Optional[torch.Tensor] = None):
+                     out_gt_nor: Optional[torch.Tensor] = None, out_gt: Optional[torch.Tensor] = None,
+                     pca=None, k: Optional[int] = None):
     """A batch drawn by index from a pack that lives on the GPU (``tsdf_voxelize_indexed_hip``): ``depth`` /
     ``offsets[N+1]`` / ``headers[N,6]`` (and ``gt[N,3J]``) describe the whole pack, uploaded once; frame i of the batch is
     pack frame ``index[i]`` (int64[n], any order — a shuffled minibatch; device or pinned host memory; or, for
@@ -202,7 +214,10 @@ def voxelize_indexed(depth: torch.Tensor, offsets: torch.Tensor, headers: torch.
     ``xforms`` float64[n,24] on the GPU (one map per batch position, as for :func:`voxelize_aug`) adds the fused 3-D
     augmentation: the labels are then mapped with it, ``gt_of_the_batch`` is ``T(joints)``.
     ``out`` / ``out_gt_nor`` / ``out_gt`` (the latter implies ``gt_copy``): preallocated outputs of exactly the batch's
-    shapes — a loader's ring buffers; nothing is allocated then."""
+    shapes — a loader's ring buffers; nothing is allocated then.
+    ``pca`` / ``k`` (needs ``gt``): the joint-PCA projection of the batch's unclamped labels by the same launch
+    (``tsdf_voxelize_indexed_pca_hip`` / ``tsdf_voxelize_indexed_host_pca_hip``); ``gt_pca`` float32[n, k] is appended to
+    the returned tuple."""
     L = _lib.load()
     by_value = isinstance(index, torch.Tensor) and not index.is_cuda and not index.is_pinned() and \
         index.dtype is torch.int64 and index.dim() == 1 and index.is_contiguous() and \
@@ -237,13 +252,24 @@ def voxelize_indexed(depth: torch.Tensor, offsets: torch.Tensor, headers: torch.
         gt_dev = out_gt if out_gt is not None else (torch.empty_like(gt_nor) if gt_copy else None)
         lab = _lib.TsdfLabels(gt.data_ptr(), nc // 3, 1 if clamp else 0, gt_nor.data_ptr(),
                               gt_dev.data_ptr() if gt_dev is not None else None)
+    pst = gt_pca = None
+    if pca is not None:
+        if gt is None:
+            raise ValueError("pca= needs gt (the projection is of the batch's labels)")
+        pst, gt_pca = _pca_struct(pca, k, n, lab.n_joints, dev)
     if n:
         with _Current(dev):
             head = (depth.data_ptr(), depth.numel(), offsets.data_ptr(), headers.data_ptr(), n_pack, index.data_ptr(), n, R,
                     ctypes.byref(cam) if cam is not None else None, _lib.LAYOUTS[layout], _raw_stream(dev))
             tail = (out.tsdf.data_ptr(), out.max_l.data_ptr(), out.mid_p.data_ptr(), out.status.data_ptr(),
                     ctypes.byref(lab) if lab is not None else None)
-            if by_value:
+            if pst is not None:
+                if by_value:
+                    rc = L.tsdf_voxelize_indexed_host_pca_hip(*head, *tail, ctypes.byref(pst))
+                else:
+                    rc = L.tsdf_voxelize_indexed_pca_hip(*head, xforms.data_ptr() if xforms is not None else None, *tail,
+                                                         ctypes.byref(pst))
+            elif by_value:
                 rc = L.tsdf_voxelize_indexed_host_hip(*head, *tail)
             elif xforms is None:
                 rc = L.tsdf_voxelize_indexed_hip(*head, *tail)
@@ -252,7 +278,113 @@ def voxelize_indexed(depth: torch.Tensor, offsets: torch.Tensor, headers: torch.
         _lib.check(rc, "tsdf_voxelize_indexed_hip")
     if gt is None:
         return out
-    return (out, gt_nor, gt_dev) if gt_copy else (out, gt_nor)
+    return ((out, gt_nor, gt_dev) if gt_copy else (out, gt_nor)) + ((gt_pca,) if pca is not None else ())
+
+
+def _pca_struct(pca, k, n, n_joints, dev, out=None):
+    """The ``tsdf_pca`` struct for ``pca`` (a :class:`pca.JointPCA`) with ``k`` components on ``dev``, and its output
+    tensor float32[n, k] (kept alive by the caller)."""
+    k = pca.check_k(k)
+    if pca.n_coords != 3 * n_joints:
+        raise ValueError(f"the PCA basis is for {pca.n_coords} coordinates, the labels have {3 * n_joints}")
+    mean, coeff = pca.device_tensors(dev)
+    if out is None:
+        out = torch.empty((n, k), dtype=torch.float32, device=dev)
+    else:
+        _dev_check("out", out, torch.float32, dev)
+        if tuple(out.shape) != (n, k):
+            raise ValueError(f"out must have shape {(n, k)}")
+    return _lib.TsdfPca(mean.data_ptr(), coeff.data_ptr(), k, out.data_ptr()), out
+
+
+def project_joints(gt: torch.Tensor, max_l: torch.Tensor, mid_p: torch.Tensor, pca, k: Optional[int] = None,
+                   out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Joint-PCA coefficients of world joints already on the GPU (``tsdf_project_joints_hip``): the labels are normalised
+    with ``max_l`` / ``mid_p`` (no clamp; ``max_l == 0`` gives 0.5) and projected on the first ``k`` components of
+    ``pca`` — bit-identical to the ``gt_pca`` the fused voxelizer entries write.  gt [n, 3J] or [n, J, 3] -> [n, k]."""
+    L = _lib.load()
+    _dev_check("gt", gt, torch.float32)
+    dev = gt.device
+    n = gt.shape[0]
+    _dev_check("max_l", max_l, torch.float32, dev)
+    _dev_check("mid_p", mid_p, torch.float32, dev)
+    if max_l.numel() != n or tuple(mid_p.shape) != (n, 3):
+        raise ValueError("max_l must be [n] and mid_p [n,3]")
+    nc = gt.numel() // n if n else pca.n_coords
+    if n and (gt.numel() != n * nc or nc % 3 or not 1 <= nc // 3 <= 170):
+        raise ValueError("gt must have shape [n, 3*J] or [n, J, 3]")
+    pst, out = _pca_struct(pca, k, n, nc // 3, dev, out)
+    if n:
+        with _Current(dev):
+            rc = L.tsdf_project_joints_hip(gt.data_ptr(), max_l.data_ptr(), mid_p.data_ptr(), n, nc // 3,
+                                           ctypes.byref(pst), _raw_stream(dev))
+        _lib.check(rc, "tsdf_project_joints_hip")
+    return out
+
+
+class PoseError(NamedTuple):
+    err: torch.Tensor                 # float32[n, J]  per-joint Euclidean error, mm
+    frame_mean: torch.Tensor          # float32[n]     mean over the frame's joints
+    frame_max: torch.Tensor           # float32[n]     worst joint of the frame
+    joints: Optional[torch.Tensor]    # float32[n, 3J] the decoded prediction in mm (``joints=True``), else None
+
+
+def pose_error(pred: torch.Tensor, gt: torch.Tensor, max_l: torch.Tensor, mid_p: torch.Tensor, pca=None,
+               joints: bool = False) -> PoseError:
+    """The per-batch evaluation of 3D_CNN/train.py (decode, denormalise, per-joint error: :219-227,325-333 and
+    ``cal_out`` :410-427) in ONE launch (``tsdf_pose_error_hip``), without a host sync.
+
+    pred   float32[n, K] PCA coefficients (``pca`` given: decoded as mu + p W[:, :K]^T) or float32[n, 3J] normalised
+           coordinates (``pca=None``: the small mode's network output)
+    gt     float32[n, 3J] (or [n, J, 3]) world joints in mm; max_l [n], mid_p [n, 3] of the frames' grids
+    Returns :class:`PoseError`; :func:`joints_within` / :func:`frames_within` turn ``err`` into the usual scores."""
+    L = _lib.load()
+    _dev_check("pred", pred, torch.float32)
+    dev = pred.device
+    n = pred.shape[0]
+    _dev_check("gt", gt, torch.float32, dev)
+    _dev_check("max_l", max_l, torch.float32, dev)
+    _dev_check("mid_p", mid_p, torch.float32, dev)
+    if gt.shape[0] != n or max_l.numel() != n or tuple(mid_p.shape) != (n, 3):
+        raise ValueError("pred, gt, max_l [n] and mid_p [n,3] must describe the same n frames")
+    nc = gt.numel() // n if n else (pca.n_coords if pca is not None else 63)
+    if n and (gt.numel() != n * nc or nc % 3 or not 1 <= nc // 3 <= 170):
+        raise ValueError("gt must have shape [n, 3*J] or [n, J, 3]")
+    nj = nc // 3
+    pst = None
+    if pca is not None:
+        if pred.dim() != 2:
+            raise ValueError("pred must be [n, K] PCA coefficients")
+        k = pca.check_k(pred.shape[1])
+        if pca.n_coords != nc:
+            raise ValueError(f"the PCA basis is for {pca.n_coords} coordinates, gt has {nc}")
+        mean, coeff = pca.device_tensors(dev)
+        pst = _lib.TsdfPca(mean.data_ptr(), coeff.data_ptr(), k, None)
+    elif pred.numel() != n * nc:
+        raise ValueError("pred must hold 3*J normalised coordinates per frame (or pass pca=)")
+    err = torch.empty((n, nj), dtype=torch.float32, device=dev)
+    fmean = torch.empty(n, dtype=torch.float32, device=dev)
+    fmax = torch.empty(n, dtype=torch.float32, device=dev)
+    jt = torch.empty((n, nc), dtype=torch.float32, device=dev) if joints else None
+    if n:
+        with _Current(dev):
+            rc = L.tsdf_pose_error_hip(pred.data_ptr(), ctypes.byref(pst) if pst is not None else None, max_l.data_ptr(),
+                                       mid_p.data_ptr(), gt.data_ptr(), n, nj, _raw_stream(dev), err.data_ptr(),
+                                       fmean.data_ptr(), fmax.data_ptr(), jt.data_ptr() if jt is not None else None)
+        _lib.check(rc, "tsdf_pose_error_hip")
+    return PoseError(err, fmean, fmax, jt)
+
+
+def joints_within(err: torch.Tensor, mm: float = 20.0) -> torch.Tensor:
+    """The reference's "proportion" (``cal_out``, 3D_CNN/train.py:417-420): percent of joints whose error is below
+    ``mm`` (strictly, as ``sqrt_sum < t``).  A 0-d float32 tensor on err's device (no host sync)."""
+    return (err < mm).sum().to(torch.float32) / err.numel() * 100
+
+
+def frames_within(err: torch.Tensor, mm: float) -> torch.Tensor:
+    """Fraction of frames whose WORST joint is within ``mm`` (error <= mm) — the usual MSRA success curve.  ``err``
+    float32[n, J] (``PoseError.err``); a 0-d float32 tensor."""
+    return (err.amax(dim=1) <= mm).to(torch.float32).mean()
 
 
 def normalize_joints(gt: torch.Tensor, max_l: torch.Tensor, mid_p: torch.Tensor, clamp: bool = True,

@@ -341,6 +341,70 @@ int tsdf_describe_launch(int n, int R, int layout, int aug, char *buf, int bufle
  * tsdf_describe_launch names a split launch by family only ("tsdf_split_kernel<32, 0, false, x8"): whether the exchange
  * or the redundant form runs depends on the stream the launch is issued on. */
 
+/* ---- Joint PCA and pose error (adds only; TSDF_ABI_VERSION stays 7, tsdf_labels is unchanged) ----
+ * The reference's --size full training regresses PCA coefficients of the normalised joints (3D_CNN/train.py:196-226,
+ * 3D_CNN/dataset.py:165-180, pre/joint_pca.py) and scores every batch (train.py:219-227,325-333, cal_out :410-427).  Its
+ * own pieces cannot run (pre/joint_pca.py passes the function instead of the data, iterates over an int, writes
+ * ./PCA.npz; dataset.py:176 centres raw-mm joints on a mean of normalised ones; the decode multiplies by W, not W^T), so
+ * this is a RE-SPECIFICATION.  n frames, J joints, C = 3J coordinates, K components (1 <= K <= C).
+ *   1. Normalised label  u = (gt - mid_p) / max_l + 0.5: the float32 arithmetic of tsdf_normalize_joints_hip with the
+ *      clamp OFF (pre/joint_nor.py does not clamp) whatever tsdf_labels.clamp says; augmented launches: the label of
+ *      T(joint) in the augmented grid, as d_out_gt_nor.  A frame that is not TSDF_FRAME_OK has u = 0.5 everywhere.
+ *   2. Fit (host, float64, not in this library): mean mu and covariance (N-1 divisor) of u over a training fold's OK
+ *      frames, W = eigenvectors by descending eigenvalue, each column's largest-|.| entry positive (ties: lowest index).
+ *   3. Projection  t_j = fl32(u_j - mu_j);  p_k = fl32(sum_j (double)t_j * (double)W[j][k]), the float64 sum taken in
+ *      ascending j from 0.0, one rounding per add (the products are exact in float64).
+ *   4. Decode and error  u^_j = fl32(acc), acc = (double)mu_j, then acc += (double)p_k * (double)W[j][k] for ascending
+ *      k; x = (u^ - 0.5) * max_l + mid_p as tsdf_denormalize_joints_hip (max_l == 0 -> mid_p); per joint
+ *      e = sqrt((dx*dx + dy*dy) + dz*dz), d = x - gt, float32, every operation rounded to nearest (cal_out in
+ *      float32); frame mean = fl32((sum_j (double)e_j, ascending j) / J); frame max = the largest e_j, exact.
+ *      A prediction given as normalised coordinates (the small mode) is u^ itself.
+ */
+typedef struct tsdf_pca {
+  const float *d_mean;  /* float32[C]: mu                                                                          */
+  const float *d_coeff; /* float32[C][C], row-major: W[j][k] = d_coeff[j*C + k]; columns k >= n_components unread  */
+  int n_components;     /* K, 1..C                                                                                 */
+  float *d_out_gt_pca;  /* float32[n][K] (written by the voxelizer entries and tsdf_project_joints_hip)            */
+} tsdf_pca;
+
+/* The labels entries with the projection fused into the same launch: besides everything tsdf_voxelize_labels_hip
+ * (d_xforms == NULL) or tsdf_voxelize_aug_labels_hip (d_xforms != NULL) writes, pca->d_out_gt_pca receives p (item 3)
+ * of every frame.  The lanes that write a frame's labels compute it: no extra launch.  labels and pca are required;
+ * every other output is bit-identical to the entry without pca. */
+int tsdf_voxelize_labels_pca_hip(const float *d_depth, int64_t depth_len, const int64_t *d_offsets,
+                                 const int32_t *d_headers, int n, int R, const tsdf_cam *cam, int layout,
+                                 void *hip_stream, const double *d_xforms, float *d_out_tsdf, float *d_out_max_l,
+                                 float *d_out_mid_p, int32_t *d_out_status, const tsdf_labels *labels,
+                                 const tsdf_pca *pca);
+/* tsdf_voxelize_indexed_hip (d_xforms == NULL) / tsdf_voxelize_indexed_aug_hip (d_xforms != NULL) + projection;
+ * gt_pca is indexed by batch position. */
+int tsdf_voxelize_indexed_pca_hip(const float *d_depth, int64_t depth_len, const int64_t *d_offsets,
+                                  const int32_t *d_headers, int64_t n_pack, const int64_t *d_index, int n, int R,
+                                  const tsdf_cam *cam, int layout, void *hip_stream, const double *d_xforms,
+                                  float *d_out_tsdf, float *d_out_max_l, float *d_out_mid_p, int32_t *d_out_status,
+                                  const tsdf_labels *labels, const tsdf_pca *pca);
+/* tsdf_voxelize_indexed_host_hip (index by value, n <= TSDF_INLINE_INDEX_MAX) + projection. */
+int tsdf_voxelize_indexed_host_pca_hip(const float *d_depth, int64_t depth_len, const int64_t *d_offsets,
+                                       const int32_t *d_headers, int64_t n_pack, const int64_t *h_index, int n, int R,
+                                       const tsdf_cam *cam, int layout, void *hip_stream, float *d_out_tsdf,
+                                       float *d_out_max_l, float *d_out_mid_p, int32_t *d_out_status,
+                                       const tsdf_labels *labels, const tsdf_pca *pca);
+
+/* Normalise (item 1; max_l == 0 counts as not OK) and project (item 3) joints already on the device:
+ * d_gt float32[n][3*n_joints] in mm, d_max_l float32[n], d_mid_p float32[n][3] -> pca->d_out_gt_pca float32[n][K].
+ * Bit-identical to the fused entries for the same max_l / mid_p. */
+int tsdf_project_joints_hip(const float *d_gt, const float *d_max_l, const float *d_mid_p, int n, int n_joints,
+                            const tsdf_pca *pca, void *hip_stream);
+
+/* Pose error (item 4) of n predictions against world joints d_gt float32[n][3*n_joints] (mm):
+ *   pca != NULL: d_pred float32[n][K] holds PCA coefficients, decoded with pca->d_mean / d_coeff (d_out_gt_pca unused);
+ *   pca == NULL: d_pred float32[n][3*n_joints] holds normalised coordinates.
+ * Writes d_out_err float32[n][n_joints], d_out_frame_mean float32[n], d_out_frame_max float32[n] and, when not NULL,
+ * d_out_joints float32[n][3*n_joints] (the decoded prediction in mm).  One launch, no atomics, deterministic. */
+int tsdf_pose_error_hip(const float *d_pred, const tsdf_pca *pca, const float *d_max_l, const float *d_mid_p,
+                        const float *d_gt, int n, int n_joints, void *hip_stream, float *d_out_err,
+                        float *d_out_frame_mean, float *d_out_frame_max, float *d_out_joints);
+
 #ifdef __cplusplus
 }
 #endif

@@ -33,6 +33,9 @@ What each fixture pins:
           gt / max_l / mid_p of every item, the volumes of a few.  Pins row f1 to the class instead of to a reading of it.
   unseen_ref_<k>  run_reference on 33 more seeded frames that no volume fixture holds (unseen_frames): what the
           reference computed for them, for tests/test_reference_live.py.
+  cal_out_ref  3D_CNN/train.py::cal_out (:410-427) RUN (train.py imported with a stub tqdm, from a scratch directory
+          holding an empty result/) on seeded small-mode predictions decoded as train.py:263-266 does: inputs, per-joint
+          errors (the torch.sqrt it takes), the proportion and err_mean.  Pins pose_error / joints_within.
   aabb_*  the numba-typing AABB (pre/tsdf_numba.py:84-96,140-141) from
           oracle/tsdf_oracle_np.py — a restatement, not a run (min_max_kernel cannot
           be executed here: no usable numba, no params.py).
@@ -441,11 +444,66 @@ def run_unseen(outdir):
         print(f"{os.path.basename(fn)}: {len(out['names'])} frames, {os.path.getsize(fn)} bytes")
 
 
+def run_reference_cal_out(outdir):
+    """cal_out_ref.npz: the reference's own evaluation (3D_CNN/train.py::cal_out) on seeded normalised predictions of
+    16 frames, decoded to mm with the reference's small-mode expression (train.py:263-266) in float32 torch."""
+    import tempfile
+    import types
+
+    import torch
+    ref_cnn = os.path.join(os.path.dirname(REF_PRE), "3D_CNN")
+    if ref_cnn not in sys.path:
+        sys.path.insert(0, ref_cnn)
+    sys.modules.setdefault("tqdm", types.SimpleNamespace(tqdm=lambda x, *a, **k: x))
+    cwd = os.getcwd()
+    with tempfile.TemporaryDirectory() as tmp:
+        os.makedirs(os.path.join(tmp, "result"))
+        os.chdir(tmp)
+        try:
+            import train as ref_train   # (train.py:28 lists ./result/ at import)
+        finally:
+            os.chdir(cwd)
+    threshold = 20
+    ref_train.opt = types.SimpleNamespace(threshold=threshold)
+    rng = np.random.default_rng(4242)
+    b = 16
+    max_l = rng.uniform(120, 260, b).astype(np.float32)
+    mid_p = (rng.normal(0, 60, (b, 3)) + [0, 0, -400]).astype(np.float32)
+    gt = (mid_p[:, None, :] + rng.normal(0, 0.3, (b, 21, 3)) * max_l[:, None, None]).astype(np.float32).reshape(b, 63)
+    gt_nor = ((gt.reshape(b, 21, 3) - mid_p[:, None, :]) / max_l[:, None, None] + np.float32(0.5)).reshape(b, 63)
+    pred = (gt_nor + rng.normal(0, 0.09, (b, 63))).astype(np.float32)   # errors of a few mm to ~60 mm
+    est = torch.from_numpy(pred)
+    ml, mp = torch.from_numpy(max_l).unsqueeze(1), torch.from_numpy(mid_p).unsqueeze(1)
+    output = ((est - 0.5) * ml).view(b, -1, 3) + mp   # train.py:263-266
+    seen = []
+
+    class _SpyTorch:   # the per-joint errors: what cal_out's torch.sqrt returns
+        def __getattr__(self, k):
+            return getattr(torch, k)
+
+        def sqrt(self, x):
+            r = torch.sqrt(x)
+            seen.append(r.clone())
+            return r
+
+    ref_train.torch = _SpyTorch()
+    try:
+        good, err_mean = ref_train.cal_out(output, torch.from_numpy(gt), b)
+    finally:
+        ref_train.torch = torch
+    err = seen[0].numpy()
+    assert err.shape == (b, 21) and 0 < (err < threshold).mean() < 1
+    np.savez_compressed(os.path.join(outdir, "cal_out_ref.npz"), pred=pred, max_l=max_l, mid_p=mid_p, gt=gt,
+                        output=output.numpy().reshape(b, 63), err=err, threshold=np.float32(threshold),
+                        proportion=np.float32(good.item()), err_mean=np.float32(err_mean.item()))
+    print(f"cal_out_ref: {b} frames, proportion {good.item():.3f} %, err_mean {err_mean.item():.3f}")
+
+
 def main(only=None):
     outdir = os.path.join(ROOT, "tests", "golden")
     os.makedirs(outdir, exist_ok=True)
     steps = {"aug": run_reference_aug, "io": run_reference_io, "dataset": run_reference_dataset, "volumes": run_volumes,
-             "unseen": run_unseen}
+             "unseen": run_unseen, "cal_out": run_reference_cal_out}
     for name in (only or list(steps)):   # --only: some of the fixtures, the others untouched (npz files carry time stamps)
         steps[name](outdir)
 
@@ -455,5 +513,5 @@ if __name__ == "__main__":
 
     ap = argparse.ArgumentParser(description="Regenerate tests/golden/*.npz by running the reference's own code "
                                              "(needs /root/reference).")
-    ap.add_argument("--only", default="", help="comma list of aug,io,dataset,volumes,unseen: just these fixtures")
+    ap.add_argument("--only", default="", help="comma list of aug,io,dataset,volumes,unseen,cal_out: just these fixtures")
     main([x for x in ap.parse_args().only.split(",") if x])
