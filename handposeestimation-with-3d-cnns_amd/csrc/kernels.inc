@@ -591,7 +591,7 @@ __global__ void __launch_bounds__(64 * kPoseWaves) tsdf_pose_error_kernel(PoseAr
     for (int j = 0; j < a.nj; ++j) {
       const float e = s_err[wave][j];
       s = __dadd_rn(s, (double)e);
-      mx = e > mx ? e : mx;
+      mx = e > mx || e != e ? e : mx;   // (a NaN error is the frame's max, whichever joint has it)
     }
     a.fmean[frame] = (float)(s / (double)a.nj);
     a.fmax[frame] = mx;

@@ -357,7 +357,8 @@ int tsdf_describe_launch(int n, int R, int layout, int aug, char *buf, int bufle
  *   4. Decode and error  u^_j = fl32(acc), acc = (double)mu_j, then acc += (double)p_k * (double)W[j][k] for ascending
  *      k; x = (u^ - 0.5) * max_l + mid_p as tsdf_denormalize_joints_hip (max_l == 0 -> mid_p); per joint
  *      e = sqrt((dx*dx + dy*dy) + dz*dz), d = x - gt, float32, every operation rounded to nearest (cal_out in
- *      float32); frame mean = fl32((sum_j (double)e_j, ascending j) / J); frame max = the largest e_j, exact.
+ *      float32); frame mean = fl32((sum_j (double)e_j, ascending j) / J); frame max = the largest e_j, exact, and NaN
+ *      when any e_j is NaN.
  *      A prediction given as normalised coordinates (the small mode) is u^ itself.
  */
 typedef struct tsdf_pca {

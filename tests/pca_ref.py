@@ -62,5 +62,46 @@ def pose_error(pred, gt, max_l, mid_p, mean=None, W=None):
     mx = err[:, 0].copy()
     for j in range(err.shape[1]):
         s = s + err[:, j].astype(np.float64)
-        mx = np.where(err[:, j] > mx, err[:, j], mx)
+        mx = np.where((err[:, j] > mx) | np.isnan(err[:, j]), err[:, j], mx)
     return err, (s / err.shape[1]).astype(f32), mx.astype(f32), x
+
+
+# ---- order-free float64 references: the exact sums, up to float64 rounding, whatever order a kernel adds in ----------
+# A bug that the kernels and the restatement above share (W transposed, a wrong row or column) is far outside these
+# bounds; a different summation order is well inside them.
+
+def project64(u, mean, W, k):
+    """(t @ W[:, :k] in float64, sum_j |t_j W[j,k]|) with t = fl32(u - mu) as item 3 defines it."""
+    t = (np.asarray(u, f32) - np.asarray(mean, f32)).astype(f32).astype(np.float64)
+    W64 = np.asarray(W, f32).astype(np.float64)[:, :k]
+    return t @ W64, np.abs(t) @ np.abs(W64)
+
+
+def decode64(p, mean, W):
+    """(mu + p @ W[:, :K]^T in float64, |mu_j| + sum_k |p_k W[j,k]|), K = p.shape[1]."""
+    p64 = np.asarray(p, f32).astype(np.float64)
+    W64 = np.asarray(W, f32).astype(np.float64)[:, :p64.shape[1]]
+    mu = np.asarray(mean, f32).astype(np.float64)
+    return mu + p64 @ W64.T, np.abs(mu) + np.abs(p64) @ np.abs(W64.T)
+
+
+def bound64(ref, scale, terms):
+    """What a float32 result of a float64 sum of `terms` products may differ from ref by: the final float32 rounding
+    (half an ulp, 2^-24 relative; 2^-149 for subnormals) plus `terms` float64 roundings on each side (2^-53 of the
+    running |sum| <= scale each), doubled for slack."""
+    return 2 * (np.abs(ref) * 2.0 ** -24 + 2.0 ** -149 + 2 * terms * scale * 2.0 ** -53)
+
+
+def bits(a):
+    """The bit patterns of a 4-byte array or tensor (a tensor is copied to the host).  Equality of these is
+    bit-exactness, which np.array_equal / torch.equal are not: they take -0 for +0 and never match a NaN."""
+    if hasattr(a, "detach"):
+        a = a.detach().cpu().numpy()
+    a = np.ascontiguousarray(a)
+    assert a.dtype.itemsize == 4, a.dtype
+    return a.view(np.uint32)
+
+
+def same_bits(a, b):
+    x, y = bits(a), bits(b)
+    return x.shape == y.shape and np.array_equal(x, y)

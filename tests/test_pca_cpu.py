@@ -190,3 +190,24 @@ def test_preprocess_tree_writes_nine_leave_one_out_fits(pkg, synth, tmp_path, P)
         assert f.n_frames == len(u) == 8 * 2 * 5
         np.testing.assert_array_equal(f.mean, u.astype(np.float64).mean(0).astype(np.float32))
         assert not np.array_equal(f.mean, P.JointPCA.load(os.path.join(pca_dir, "%d.npz" % ((t + 1) % 9))).mean)
+
+
+def test_restatement_within_order_free_bound_at_170_joints(P):
+    """The sequential restatement at C = 510 against the float64 matmul (pca_ref.project64 / decode64): within the
+    rounding bound, and a transposed basis — a bug the restatement and a kernel could share — far outside it."""
+    C = 510
+    pca = P.fit_labels(_separated(n=600, C=C, seed=7))
+    rng = np.random.default_rng(8)
+    u = _separated(n=16, C=C, seed=9)
+    u[3] = 0.5   # a frame that is not OK
+    assert (pca.coeff < 0).any() and (pca.coeff > 0).any()
+    for k in (1, 65, C - 1, C):
+        p = pca_ref.project(u, pca.mean, pca.coeff, k)
+        ref, scale = pca_ref.project64(u, pca.mean, pca.coeff, k)
+        assert (np.abs(p - ref) <= pca_ref.bound64(ref, scale, C)).all()
+        q = (p + rng.normal(0, 0.05, p.shape)).astype(np.float32)
+        uh = pca_ref.decode(q, pca.mean, pca.coeff[:, :k])
+        ref, scale = pca_ref.decode64(q, pca.mean, pca.coeff)
+        assert (np.abs(uh - ref) <= pca_ref.bound64(ref, scale, k + 1)).all()
+    ref, scale = pca_ref.project64(u, pca.mean, pca.coeff.T, C)
+    assert (np.abs(pca_ref.project(u, pca.mean, pca.coeff, C) - ref) > pca_ref.bound64(ref, scale, C)).mean() > 0.9

@@ -1,6 +1,6 @@
 """GPU tier: the joint-PCA projection fused into the labels path, tsdf_project_joints_hip, tsdf_pose_error_hip and
 MSRA_Dataset(pca=...) — against the numpy restatement (tests/pca_ref.py) and the run of the reference's cal_out
-(tests/golden/cal_out_ref.npz)."""
+(tests/golden/cal_out_ref.npz).  "Bit-exact" compares bit patterns (pca_ref.same_bits): -0 is not +0."""
 import importlib
 import os
 
@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 
 import pca_ref
+from pca_ref import same_bits
 
 torch = pytest.importorskip("torch")
 PKG = "handposeestimation-with-3d-cnns_amd"
@@ -52,7 +53,7 @@ def _expect(gt_mm, out, pca, k):
 
 def _same_batch(a, b):
     for x, y in zip(a, b):
-        assert torch.equal(x, y)
+        assert same_bits(x, y)
 
 
 @pytest.mark.parametrize("k", [63, 20])
@@ -64,12 +65,12 @@ def test_fused_projection_plain_bit_exact(pkg, synth, P, k):
     out, nor, gt_pca = pkg.voxelize_labels(d, o, h, g, clamp=True, pca=pca, k=k)
     torch.cuda.synchronize()
     _same_batch(out, out0)
-    assert torch.equal(nor, nor0)
+    assert same_bits(nor, nor0)
     st = out.status.cpu().numpy()
     assert (st != 0).sum() == 2 and (st == 0).sum() == 22
-    assert np.array_equal(gt_pca.cpu().numpy(), _expect(gt, out, pca, k))
+    assert same_bits(gt_pca, _expect(gt, out, pca, k))
     # the standalone entry: same arithmetic, same bits
-    assert torch.equal(pkg.project_joints(g, out.max_l, out.mid_p, pca, k), gt_pca)
+    assert same_bits(pkg.project_joints(g, out.max_l, out.mid_p, pca, k), gt_pca)
 
 
 @pytest.mark.parametrize("by_value", [True, False])
@@ -85,11 +86,11 @@ def test_fused_projection_indexed_bit_exact(pkg, synth, P, by_value):
     out, nor, gd, gt_pca = pkg.voxelize_indexed(d, o, h, index, g, clamp=False, gt_copy=True, pca=pca, k=63)
     torch.cuda.synchronize()
     _same_batch(out, out0)
-    assert torch.equal(nor, nor0) and torch.equal(gd, gd0)
-    assert np.array_equal(gt_pca.cpu().numpy(), _expect(gt[idx], out, pca, 63))
+    assert same_bits(nor, nor0) and same_bits(gd, gd0)
+    assert same_bits(gt_pca, _expect(gt[idx], out, pca, 63))
     # unclamped labels: the fused projection uses gt_nor's values exactly
-    assert np.array_equal(gt_pca.cpu().numpy(), pca_ref.project(nor.cpu().numpy(), pca.mean, pca.coeff, 63))
-    assert torch.equal(pkg.project_joints(gd, out.max_l, out.mid_p, pca, 63), gt_pca)
+    assert same_bits(gt_pca, pca_ref.project(nor.cpu().numpy(), pca.mean, pca.coeff, 63))
+    assert same_bits(pkg.project_joints(gd, out.max_l, out.mid_p, pca, 63), gt_pca)
 
 
 def test_fused_projection_augmented_bit_exact(pkg, synth, P):
@@ -105,9 +106,9 @@ def test_fused_projection_augmented_bit_exact(pkg, synth, P):
                                                   pca=pca, k=40)
     torch.cuda.synchronize()
     _same_batch(out, out0)
-    assert torch.equal(nor, nor0) and torch.equal(gaug, gaug0)
-    assert np.array_equal(gt_pca.cpu().numpy(), _expect(gaug.cpu().numpy(), out, pca, 40))
-    assert torch.equal(pkg.project_joints(gaug, out.max_l, out.mid_p, pca, 40), gt_pca)
+    assert same_bits(nor, nor0) and same_bits(gaug, gaug0)
+    assert same_bits(gt_pca, _expect(gaug.cpu().numpy(), out, pca, 40))
+    assert same_bits(pkg.project_joints(gaug, out.max_l, out.mid_p, pca, 40), gt_pca)
 
 
 def test_pose_error_matches_restatement_and_recovers_gt(pkg, synth, P):
@@ -119,16 +120,16 @@ def test_pose_error_matches_restatement_and_recovers_gt(pkg, synth, P):
     torch.cuda.synchronize()
     ml, mp = out.max_l.cpu().numpy(), out.mid_p.cpu().numpy()
     err, fmean, fmax, x = pca_ref.pose_error(gt_pca.cpu().numpy(), gt, ml, mp, pca.mean, pca.coeff)
-    assert np.array_equal(pe.err.cpu().numpy(), err)
-    assert np.array_equal(pe.frame_mean.cpu().numpy(), fmean)
-    assert np.array_equal(pe.frame_max.cpu().numpy(), fmax)
-    assert np.array_equal(pe.joints.cpu().numpy(), x)
+    assert same_bits(pe.err, err)
+    assert same_bits(pe.frame_mean, fmean)
+    assert same_bits(pe.frame_max, fmax)
+    assert same_bits(pe.joints, x)
     assert float(np.abs(x - gt).max()) <= 1e-3 and float(pe.frame_max.max()) <= 1e-3   # K = C: decode(project) = gt
     # a truncated basis and noisy coefficients: still the restatement, bit for bit
     noisy = (gt_pca[:, :12] + 0.05 * torch.randn(24, 12, device=DEV, generator=torch.Generator(DEV).manual_seed(1)))
     pe = pkg.pose_error(noisy.contiguous(), g, out.max_l, out.mid_p, pca=pca)
     err, fmean, fmax, _ = pca_ref.pose_error(noisy.cpu().numpy(), gt, ml, mp, pca.mean, pca.coeff[:, :12])
-    assert np.array_equal(pe.err.cpu().numpy(), err) and np.array_equal(pe.frame_mean.cpu().numpy(), fmean)
+    assert same_bits(pe.err, err) and same_bits(pe.frame_mean, fmean)
     assert pe.joints is None and float(pe.frame_max.min()) > 1.0
 
 
@@ -136,7 +137,7 @@ def test_pose_error_pinned_to_reference_cal_out(pkg, golden_dir):
     g = np.load(os.path.join(golden_dir, "cal_out_ref.npz"))
     pe = pkg.pose_error(_t(g["pred"]), _t(g["gt"]), _t(g["max_l"]), _t(g["mid_p"]), joints=True)
     prop = pkg.joints_within(pe.err, float(g["threshold"]))
-    assert np.array_equal(pe.joints.cpu().numpy(), g["output"])
+    assert same_bits(pe.joints, g["output"])
     np.testing.assert_allclose(pe.err.cpu().numpy(), g["err"], rtol=2e-7, atol=0)
     assert float(prop) == pytest.approx(float(g["proportion"]), abs=1e-4)
     assert float(pe.frame_mean.double().sum()) == pytest.approx(float(g["err_mean"]), rel=1e-6)
@@ -169,7 +170,7 @@ def test_dataset_pca_dataloader_yields_5_tuples(pkg, tree, tmp_path, P):
         tsdf, gt, ml, mp, gt_pca = batch
         b = gt.shape[0]
         assert gt_pca.shape == (b, 30) and gt_pca.is_cuda
-        assert torch.equal(gt_pca, pkg.project_joints(gt, ml, mp, ds.pca, 30))
+        assert same_bits(gt_pca, pkg.project_joints(gt, ml, mp, ds.pca, 30))
         n_batches += 1
     assert n_batches == -(-len(ds) // 16)
     # the reference's unmodified decode (3D_CNN/train.py:221-225) at K = C recovers gt
@@ -185,16 +186,16 @@ def test_dataset_pca_dataloader_yields_5_tuples(pkg, tree, tmp_path, P):
     ref = full._items_of([0, 1, 2, 17])
     for a, r in zip(items, ref):
         for x, y in zip(a, r):
-            assert torch.equal(x, y)
+            assert same_bits(x, y)
     nb = _ds(pkg, tree, tmp, pca=ds.pca, k=30, prebatched=False)
     its = nb.__getitems__([3, 9, 4])
     assert all(len(it) == 5 for it in its)
     got = torch.stack([it[4] for it in its])
-    assert torch.equal(got, pkg.project_joints(torch.stack([it[1] for it in its]), torch.stack([it[2] for it in its]),
+    assert same_bits(got, pkg.project_joints(torch.stack([it[1] for it in its]), torch.stack([it[2] for it in its]),
                                                torch.stack([it[3] for it in its]), ds.pca, 30))
     path = ds.pca.save(tmp, fold=1)
     te = _ds(pkg, tree, tmp, train=False, pca=path, k=30)
-    assert len(te[0]) == 5 and np.array_equal(te.pca.coeff, ds.pca.coeff)
+    assert len(te[0]) == 5 and same_bits(te.pca.coeff, ds.pca.coeff)
     with pytest.raises(ValueError):
         _ds(pkg, tree, tmp, train=False, pca=True)
 
@@ -210,15 +211,15 @@ def test_dataset_pca_fit_matches_restatement_and_aug(pkg, tree, tmp_path, P):
     mp = torch.stack([it[3] for it in items]).cpu().numpy()
     ok = ml > 0
     ref = P.fit_labels(pca_ref.normalize(gt, ml, mp)[ok])
-    np.testing.assert_array_equal(ds.pca.mean, ref.mean)
-    np.testing.assert_array_equal(ds.pca.coeff, ref.coeff)
+    assert same_bits(ds.pca.mean, ref.mean)
+    assert same_bits(ds.pca.coeff, ref.coeff)
     assert len(raw) == len(ds)
     # aug=True: the fit covers the augmented items too, and every item has gt_pca of its own (mapped) labels
     da = _ds(pkg, tree, tmp, pca=True, aug=True, k=63)
     assert da.pca.n_frames == len(da) and da.pca.aug
     from torch.utils.data import DataLoader
     tsdf, gt, ml, mp, gt_pca = next(iter(DataLoader(da, batch_size=16, shuffle=True)))
-    assert torch.equal(gt_pca, pkg.project_joints(gt, ml, mp, da.pca, 63))
+    assert same_bits(gt_pca, pkg.project_joints(gt, ml, mp, da.pca, 63))
 
 
 def test_dataset_without_pca_is_unchanged(pkg, tree, tmp_path):
@@ -239,5 +240,5 @@ def test_ring_counts_a_consumer_that_keeps_only_gt_pca(pkg, tree, tmp_path, P):
         del batch
     torch.cuda.synchronize()
     for held, snap in kept:   # no slot was recycled under a held gt_pca
-        assert torch.equal(held, snap)
+        assert same_bits(held, snap)
     assert ds._fast.replaced >= 1
