@@ -11,11 +11,13 @@ Host side:                               packing (MSRA .bin reader / batch packe
                                          dataset (on-the-fly MSRADepthDataset / VoxelLoader / ResidentLoader, label normalisation)
 Full mode and evaluation:                pca (JointPCA, fit_joint_pca), project_joints, pose_error, joints_within,
                                          frames_within
+Point clouds:                            point_clouds (back-projected, resampled on the device), export.preprocess_tree
 """
 from . import _lib  # noqa: F401
 from ._lib import TsdfCam, TsdfError, default_cam  # noqa: F401
-from .voxelize import (AabbBatch, PoseError, TsdfBatch, aabb, denormalize_joints, frames_within,  # noqa: F401
-                       joints_within, normalize_joints, pose_error, project_joints, release_stream, voxel_pixels,
+from .voxelize import (AabbBatch, PointCloudBatch, PoseError, TsdfBatch, aabb, denormalize_joints,  # noqa: F401
+                       frames_within, joints_within, normalize_joints, point_clouds, pose_error, project_joints,
+                       release_stream, voxel_pixels,
                        voxelize, voxelize_aug, voxelize_grid, voxelize_indexed, voxelize_labels)
 from .pca import JointPCA, fit_joint_pca  # noqa: F401
 from . import augment, dataset, export, packing, pca, shard, synth  # noqa: F401
@@ -27,4 +29,5 @@ from .process import DataProcess  # noqa: F401
 __all__ = ["voxelize", "voxelize_labels", "voxelize_indexed", "ResidentLoader", "voxel_pixels", "release_stream", "voxelize_grid", "voxelize_aug", "augment", "aabb", "TsdfBatch", "AabbBatch", "TsdfCam", "TsdfError",
            "default_cam", "cal_tsdf_cuda", "tsdf_f", "tsdf_cal", "DataProcess", "packing", "shard",
            "synth", "dataset", "MSRADepthDataset", "MSRA_Dataset", "VoxelLoader", "VoxelBatch", "normalize_joints", "denormalize_joints",
-           "pca", "JointPCA", "fit_joint_pca", "project_joints", "pose_error", "PoseError", "joints_within", "frames_within"]
+           "pca", "JointPCA", "fit_joint_pca", "project_joints", "pose_error", "PoseError", "joints_within", "frames_within",
+           "point_clouds", "PointCloudBatch"]

@@ -211,6 +211,14 @@ int tsdf_pose_error_hip(const float *d_pred, const tsdf_pca *pca, const float *d
                         d_out_frame_max, d_out_joints);
 }
 
+int tsdf_point_clouds_hip(const float *d_depth, int64_t depth_len, const int64_t *d_offsets, const int32_t *d_headers,
+                          int n, int points, const tsdf_cam *cam, uint64_t seed, int64_t frame_base,
+                          const double *d_xforms, void *hip_stream, double *d_out_points, int32_t *d_out_count,
+                          int32_t *d_out_status) {
+  return run_point_clouds(d_depth, depth_len, d_offsets, d_headers, n, points, cam, seed, frame_base, d_xforms,
+                          hip_stream, d_out_points, d_out_count, d_out_status);
+}
+
 #ifdef TSDF_DEBUG_HOOKS   // the debug build only (make debug -> build/libtsdf_hip_debug.so): include/tsdf_debug.h
 int tsdf_debug_pixmap_hip(const float *d_depth, int64_t depth_len, const int64_t *d_offsets, const int32_t *d_headers,
                           int n, int R, const tsdf_cam *cam, int layout, void *hip_stream, const float *d_grid,

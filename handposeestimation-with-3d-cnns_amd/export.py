@@ -9,6 +9,10 @@ frame on the CPU (~0.2 s each) and writes, per subject directory under ``./resul
     Point_Cloud/<gesture>.npy   [n,6000,3] random resample of the point cloud (:117-118)
     ../data_num-<subject>.npy   frames of the subject (scalar)                (:139)
 
+and, with its AUG switch on, four twins of the augmented frames (:68-75,86-91,112-117,128-136):
+
+    Point_Cloud_aug/<g>.npy     TSDF_aug/<g>.npz (tsdf, max_l, mid_p)     ground_truth_aug/<g>.npy     num_aug/<g>.npy
+
 which is what ``3D_CNN/dataset.py:93-131`` reads back.  ``preprocess_tree`` writes the same files with the
 voxelization done by the HIP kernel: a gesture (~500 frames) is packed (``packing.pack_bin_files``), uploaded
 once and voxelized in one launch.
@@ -27,9 +31,25 @@ Differences from the reference writer, all deliberate and switchable:
     pre/read_MSRA.py:81-82 that pre-negate it; for the ``[n,63]`` array its own writer saves, ``g_t`` is undefined).
     After the reader's flip the labels are back in the camera frame (z = -depth) that ``mid_p`` lives in.
 
+``aug=True`` writes the twins too (``DataProcess(aug=True)`` re-specified, process.py): each frame's map comes from
+``augment.random_affines`` centred on the frame's plain grid centre ``mid_p``; ``TSDF_aug`` is the fused augmented
+voxelization under that map (``voxelize_aug``, same res / layout / dtype, plus ``status`` and the map itself as ``xform``
+float64[n,24]), ``ground_truth_aug`` the joints under the same map, ``Point_Cloud_aug`` the mapped cloud.
+``data_num-<subject>.npy`` keeps counting plain frames, as the reference does.
+
+Random draws.  ``rng`` feeds the plain files only and ``aug_rng`` the augmented ones, so ``aug=True`` leaves every
+plain file byte-identical to an ``aug=False`` run with the same ``rng``.  Per gesture, in this order:
+  * ``point_clouds="host"`` (or True): the plain cloud draws from ``rng`` (``resample_point_clouds``); the maps come
+    from ``aug_rng``, then the augmented cloud draws from ``aug_rng``;
+  * ``point_clouds="device"``: the plain cloud is ``voxelize.point_clouds(seed=rng.integers(0, 2**63))``; the maps
+    come from ``aug_rng``, then the augmented cloud is ``point_clouds(seed=aug_rng.integers(0, 2**63), xforms=maps)``;
+    both with ``frame_base=0``.  Replaying the two generators reproduces every file.
+
 ``pca_dir`` adds what ``read_MSRA.main()`` ends with (``joint_pca(aug=False)``, pre/joint_pca.py): the nine
 leave-one-subject-out joint-PCA fits ``<pca_dir>/<fold>.npz``, fold t fitted on the normalised labels of every subject
-but the t-th — re-specified (``pca.py``), from the max_l / mid_p / labels already in memory.
+but the t-th — re-specified (``pca.py``), from the max_l / mid_p / labels already in memory.  With ``aug=True`` also
+``<fold>-aug.npz`` (``joint_pca(aug=True)``, pre/joint_pca.py:29-36): the same fold fitted on its plain labels stacked
+over its augmented ones, the latter normalised with the ``TSDF_aug`` grid.
 """
 from __future__ import annotations
 
@@ -41,6 +61,7 @@ import numpy as np
 from . import packing
 
 _SUBDIRS = ("Point_Cloud", "TSDF", "ground_truth", "num")
+_AUG_SUBDIRS = tuple(d + "_aug" for d in _SUBDIRS)
 
 
 def _default_voxelize(pk: packing.PackedFrames, res: int, layout: str, device):
@@ -56,10 +77,47 @@ def _default_voxelize(pk: packing.PackedFrames, res: int, layout: str, device):
             out.status.cpu().numpy())
 
 
+def _default_voxelize_aug(pk: packing.PackedFrames, xforms: np.ndarray, gt: np.ndarray, res: int, layout: str, device):
+    """Upload + one augmented launch with the labels: host arrays (tsdf, max_l, mid_p, status, gt_aug)."""
+    import torch
+
+    from .voxelize import voxelize_aug
+
+    depth, offsets, headers = pk.to_torch(device, pin=True, non_blocking=True)
+    xf = torch.from_numpy(np.ascontiguousarray(xforms, np.float64)).to(depth.device)
+    g = torch.from_numpy(np.ascontiguousarray(np.asarray(gt, np.float32).reshape(len(pk), -1))).to(depth.device)
+    out, _, gt_aug = voxelize_aug(depth, offsets, headers, xf, res=res, layout=layout, gt=g)
+    torch.cuda.synchronize(depth.device)
+    return (out.tsdf.cpu().numpy(), out.max_l.cpu().numpy(), out.mid_p.cpu().numpy(), out.status.cpu().numpy(),
+            gt_aug.cpu().numpy())
+
+
+def device_point_clouds(pk: packing.PackedFrames, points_num: int, seed: int, xforms: Optional[np.ndarray] = None,
+                        device="cuda") -> np.ndarray:
+    """``voxelize.point_clouds`` on a pack (upload, one launch, ``frame_base=0``): host ``float64[n, points_num, 3]``."""
+    import torch
+
+    from .voxelize import point_clouds
+
+    depth, offsets, headers = pk.to_torch(device, pin=True, non_blocking=True)
+    xf = None if xforms is None else torch.from_numpy(np.ascontiguousarray(xforms, np.float64)).to(depth.device)
+    out = point_clouds(depth, offsets, headers, points=points_num, seed=seed, xforms=xf)
+    return out.points.cpu().numpy()
+
+
+def _map_points(pts: np.ndarray, xform: np.ndarray) -> np.ndarray:
+    """The forward map of ``tsdf_point_clouds_hip`` (include/tsdf.h): (A_i0 x + A_i1 y) + (A_i2 z + b_i), float64,
+    products and sums rounded separately."""
+    f = np.asarray(xform, np.float64).reshape(24)[:12].reshape(3, 4)
+    x, y, z = pts[:, 0], pts[:, 1], pts[:, 2]
+    return np.stack([(f[k, 0] * x + f[k, 1] * y) + (f[k, 2] * z + f[k, 3]) for k in range(3)], axis=1)
+
+
 def resample_point_clouds(pk: packing.PackedFrames, points_num: int = 6000,
-                          rng: Optional[np.random.Generator] = None) -> np.ndarray:
+                          rng: Optional[np.random.Generator] = None, xforms: Optional[np.ndarray] = None) -> np.ndarray:
     """``DataProcess.point_cloud`` + ``set_length`` (pre/process.py:30-84) for every frame of a pack:
-    ``float64[n, points_num, 3]``.  Frames without any non-zero point give zeros."""
+    ``float64[n, points_num, 3]``.  Frames without any non-zero point give zeros.  ``xforms`` float64[n, 24]: each
+    frame's cloud is mapped with its forward rows (as ``tsdf_point_clouds_hip`` maps them) before it is resampled."""
     from .process import DataProcess
 
     rng = rng if rng is not None else np.random.default_rng()
@@ -68,6 +126,8 @@ def resample_point_clouds(pk: packing.PackedFrames, points_num: int = 6000,
     for i in range(n):
         header, depth = pk.frame(i)
         pts = DataProcess({"header": header, "depth": depth}, None, points_num).point_cloud()
+        if xforms is not None:
+            pts = _map_points(pts, xforms[i])
         m = pts.shape[0]
         if m == 0:
             continue
@@ -99,28 +159,62 @@ def write_gesture(sub_dir: str, gesture: str, tsdf: np.ndarray, max_l: np.ndarra
         np.save(os.path.join(sub_dir, "Point_Cloud", "%s.npy" % gesture), point_cloud)
 
 
+def write_gesture_aug(sub_dir: str, gesture: str, tsdf: np.ndarray, max_l: np.ndarray, mid_p: np.ndarray,
+                      ground_truth: np.ndarray, status: np.ndarray, xforms: np.ndarray,
+                      point_cloud: Optional[np.ndarray] = None, gt_3d: bool = False) -> None:
+    """The four augmented twins of pre/read_MSRA.py:112-117,128-136 (``TSDF_aug`` gains ``status`` and ``xform``)."""
+    for d in _AUG_SUBDIRS:
+        os.makedirs(os.path.join(sub_dir, d), exist_ok=True)
+    n = int(tsdf.shape[0])
+    np.savez(os.path.join(sub_dir, "TSDF_aug", "%s.npz" % gesture), tsdf=tsdf, max_l=max_l, mid_p=mid_p,
+             status=np.asarray(status, np.int32), xform=np.asarray(xforms, np.float64).reshape(n, 24))
+    gt = np.asarray(ground_truth, np.float32).reshape(n, -1)
+    if gt_3d:
+        gt = gt.reshape(n, 21, 3).copy()
+        gt[:, :, 2] = -gt[:, :, 2]
+    np.save(os.path.join(sub_dir, "ground_truth_aug", "%s.npy" % gesture), gt)
+    np.save(os.path.join(sub_dir, "num_aug", "%s.npy" % gesture), n)
+    if point_cloud is not None:
+        np.save(os.path.join(sub_dir, "Point_Cloud_aug", "%s.npy" % gesture), point_cloud)
+
+
 def preprocess_tree(db_dir: str, save_dir: str, *, res: int = 32, layout: str = "cxyz", dtype=np.float32,
-                    points_num: int = 6000, point_clouds: bool = True, gt_3d: bool = False,
+                    points_num: int = 6000, point_clouds=True, gt_3d: bool = False,
                     subjects: Optional[Sequence[str]] = None, gestures: Optional[Sequence[str]] = None,
                     device="cuda", rng: Optional[np.random.Generator] = None,
                     voxelize_fn: Optional[Callable] = None, verbose: bool = False,
-                    pca_dir: Optional[str] = None) -> Dict[str, int]:
-    """Replacement for ``read_MSRA.main()`` (pre/read_MSRA.py:37-140, AUG=False): voxelize a whole MSRA tree
-    into ``save_dir`` in the reference's schema.  Returns ``{subject: frames}``.
+                    pca_dir: Optional[str] = None, aug: bool = False,
+                    aug_rng: Optional[np.random.Generator] = None,
+                    voxelize_aug_fn: Optional[Callable] = None) -> Dict[str, int]:
+    """Replacement for ``read_MSRA.main()`` (pre/read_MSRA.py:37-140): voxelize a whole MSRA tree into ``save_dir`` in
+    the reference's schema (with ``aug=True`` its AUG=True schema).  Returns ``{subject: frames}``.
 
-    ``voxelize_fn(pack, res, layout, device) -> (tsdf, max_l, mid_p, status)`` may replace the HIP call
-    (tests use it to check the file handling without a GPU); by default the HIP voxelizer runs and a
+    ``voxelize_fn(pack, res, layout, device) -> (tsdf, max_l, mid_p, status)`` and
+    ``voxelize_aug_fn(pack, xforms, gt, res, layout, device) -> (tsdf, max_l, mid_p, status, gt_aug)`` may replace the
+    HIP calls (tests use them to check the file handling without a GPU); by default the HIP voxelizer runs and a
     missing library or device is an error.
 
+    ``point_clouds``: True / "host" (``resample_point_clouds`` on the host), "device" (``voxelize.point_clouds``) or
+    False (no cloud files).  The draws of each are in the module docstring.
+
     ``pca_dir``: also write the joint-PCA fits of the first nine subjects' leave-one-out folds there (``pca.JointPCA``
-    files, ``<fold>.npz``): the labels are normalised with each frame's own max_l / mid_p (no clamp) and frames whose
-    status is not OK are left out."""
+    files, ``<fold>.npz``, and with ``aug=True`` ``<fold>-aug.npz``): the labels are normalised with each frame's own
+    max_l / mid_p (no clamp) and frames whose status is not OK are left out."""
+    if point_clouds is True:
+        point_clouds = "host"
+    if point_clouds not in (False, None, "host", "device"):
+        raise ValueError('point_clouds must be True / "host", "device" or False')
     vox = voxelize_fn if voxelize_fn is not None else _default_voxelize
+    vox_aug = voxelize_aug_fn if voxelize_aug_fn is not None else _default_voxelize_aug
+    rng = rng if rng is not None else np.random.default_rng()
+    if aug:
+        aug_rng = aug_rng if aug_rng is not None else np.random.default_rng()
     os.makedirs(save_dir, exist_ok=True)
     subs = list(subjects) if subjects is not None else sorted(
         d for d in os.listdir(db_dir) if os.path.isdir(os.path.join(db_dir, d)))
     totals: Dict[str, int] = {}
     labels: Dict[str, list] = {}   # pca_dir: the normalised labels of the OK frames, per subject
+    labels_aug: Dict[str, list] = {}   # ... and of the OK augmented frames (aug=True)
     for sub in subs:
         sub_in, sub_out = os.path.join(db_dir, sub), os.path.join(save_dir, sub)
         ges_list = list(gestures) if gestures is not None else sorted(
@@ -135,9 +229,28 @@ def preprocess_tree(db_dir: str, save_dir: str, *, res: int = 32, layout: str = 
                 from .pca import normalize_labels_np
                 ok = np.asarray(max_l, np.float32) > 0 if status is None else np.asarray(status) == 0
                 labels.setdefault(sub, []).append(normalize_labels_np(gt, max_l, mid_p)[ok])
-            pc = resample_point_clouds(pk, points_num, rng) if point_clouds else None
+            pc = None
+            if point_clouds == "host":
+                pc = resample_point_clouds(pk, points_num, rng)
+            elif point_clouds == "device":
+                pc = device_point_clouds(pk, points_num, int(rng.integers(0, 2 ** 63)), device=device)
             write_gesture(sub_out, ges, np.asarray(tsdf, dtype), np.asarray(max_l, dtype),
                           np.asarray(mid_p, dtype), gt, status, pc, gt_3d)
+            if aug:
+                from .augment import random_affines
+                xf = random_affines(np.asarray(mid_p, np.float64), rng=aug_rng)[0]
+                tsdf_a, max_l_a, mid_p_a, status_a, gt_a = vox_aug(pk, xf, gt, res, layout, device)
+                if pca_dir is not None:
+                    from .pca import normalize_labels_np
+                    ok = np.asarray(status_a) == 0
+                    labels_aug.setdefault(sub, []).append(normalize_labels_np(gt_a, max_l_a, mid_p_a)[ok])
+                pc_a = None
+                if point_clouds == "host":
+                    pc_a = resample_point_clouds(pk, points_num, aug_rng, xforms=xf)
+                elif point_clouds == "device":
+                    pc_a = device_point_clouds(pk, points_num, int(aug_rng.integers(0, 2 ** 63)), xf, device=device)
+                write_gesture_aug(sub_out, ges, np.asarray(tsdf_a, dtype), np.asarray(max_l_a, dtype),
+                                  np.asarray(mid_p_a, dtype), gt_a, status_a, xf, pc_a, gt_3d)
             total += bin_num
             if verbose:
                 print("%s-%s files saved." % (sub, ges))
@@ -149,4 +262,7 @@ def preprocess_tree(db_dir: str, save_dir: str, *, res: int = 32, layout: str = 
         for t in range(len(folds)):
             u = [x for s in folds if s != folds[t] for x in labels.get(s, [])]
             fit_labels(np.concatenate(u) if u else np.zeros((0, 63), np.float32), fold=t).save(pca_dir)
+            if aug:   # pre/joint_pca.py:29-36: the plain labels, then the augmented ones
+                u += [x for s in folds if s != folds[t] for x in labels_aug.get(s, [])]
+                fit_labels(np.concatenate(u) if u else np.zeros((0, 63), np.float32), fold=t, aug=True).save(pca_dir)
     return totals

@@ -564,3 +564,62 @@ def voxelize_aug(depth: torch.Tensor, offsets: torch.Tensor, headers: torch.Tens
                 rc = L.tsdf_voxelize_aug_labels_hip(*args, ctypes.byref(lab))
         _lib.check(rc, "tsdf_voxelize_aug_hip")
     return out if gt is None else (out, gt_nor, gt_aug)
+
+
+class PointCloudBatch(NamedTuple):
+    points: torch.Tensor  # float64[n, P, 3]
+    count: torch.Tensor   # int32[n]  valid pixels of the frame (m)
+    status: torch.Tensor  # int32[n]  (_lib.TSDF_FRAME_*)
+
+
+def point_clouds(depth: torch.Tensor, offsets: torch.Tensor, headers: torch.Tensor, points: int = 6000, seed: int = 0,
+                 frame_base: int = 0, xforms: Optional[torch.Tensor] = None, cam: Optional[_lib.TsdfCam] = None,
+                 out: Optional[PointCloudBatch] = None) -> PointCloudBatch:
+    """``DataProcess.point_cloud`` + ``set_length`` (pre/process.py:30-84) for n packed frames in one launch
+    (``tsdf_point_clouds_hip``; the contract is in include/tsdf.h): every pixel with d != 0 back-projected in float64,
+    resampled to ``points`` points by a counter-based draw from ``seed`` and the frame's number ``frame_base + i``
+    (so a batch split over several calls gives the same clouds as one call).
+
+    xforms  optional float64[n, 24] on the GPU (``augment.random_affines``): the points are mapped with the forward rows.
+    Returns :class:`PointCloudBatch`; frames that are not OK get all-zero rows.  Enqueues on the current stream and
+    returns without synchronising."""
+    L = _lib.load()
+    _dev_check("depth", depth, torch.float32)
+    dev = depth.device
+    _dev_check("offsets", offsets, torch.int64, dev, host_ok=True)
+    _dev_check("headers", headers, torch.int32, dev, host_ok=True)
+    if headers.dim() != 2 or headers.shape[1] != 6:
+        raise ValueError("headers must have shape [n, 6]")
+    n = headers.shape[0]
+    if offsets.numel() != n + 1:
+        raise ValueError("offsets must have n+1 entries")
+    P = int(points)
+    if not 1 <= P <= 0x7fffffff:
+        raise ValueError("points must be in 1..2^31-1")
+    seed, frame_base = int(seed), int(frame_base)
+    if not 0 <= seed < 2 ** 64:
+        raise ValueError("seed must be in [0, 2^64)")
+    if not -2 ** 63 <= frame_base < 2 ** 63:
+        raise ValueError("frame_base must fit int64")
+    if xforms is not None:
+        _dev_check("xforms", xforms, torch.float64, dev)
+        if tuple(xforms.shape) != (n, 24):
+            raise ValueError("xforms must have shape [n, 24]")
+    if out is None:
+        out = PointCloudBatch(torch.empty((n, P, 3), dtype=torch.float64, device=dev),
+                              torch.empty(n, dtype=torch.int32, device=dev),
+                              torch.empty(n, dtype=torch.int32, device=dev))
+    else:
+        _dev_check("out.points", out.points, torch.float64, dev)
+        _dev_check("out.count", out.count, torch.int32, dev)
+        _dev_check("out.status", out.status, torch.int32, dev)
+        if tuple(out.points.shape) != (n, P, 3) or out.count.numel() != n or out.status.numel() != n:
+            raise ValueError("out tensors have the wrong shape")
+    if n:
+        with _Current(dev):
+            rc = L.tsdf_point_clouds_hip(depth.data_ptr(), depth.numel(), offsets.data_ptr(), headers.data_ptr(), n, P,
+                                         ctypes.byref(cam) if cam is not None else None, seed, frame_base,
+                                         xforms.data_ptr() if xforms is not None else None, _raw_stream(dev),
+                                         out.points.data_ptr(), out.count.data_ptr(), out.status.data_ptr())
+        _lib.check(rc, "tsdf_point_clouds_hip")
+    return out

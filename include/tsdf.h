@@ -406,6 +406,36 @@ int tsdf_pose_error_hip(const float *d_pred, const tsdf_pca *pca, const float *d
                         const float *d_gt, int n, int n_joints, void *hip_stream, float *d_out_err,
                         float *d_out_frame_mean, float *d_out_frame_max, float *d_out_joints);
 
+/* ---- Point clouds (adds only; TSDF_ABI_VERSION stays 7) ----
+ * DataProcess.point_cloud + set_length (pre/process.py:30-84) for n packed frames in one launch: every valid pixel of a
+ * crop is back-projected and the cloud is resampled to `points` (P) points.  The reference resamples with numpy's global
+ * generator; here the draw is counter-based, so the result does not depend on the launch shape.
+ *   1. Valid pixels: d != 0 — pre/process.py:62-64, NOT the voxelizer's |d| >= invalid_eps rule, so a NaN pixel is
+ *      valid as in the reference.  Valid pixels are taken in row-major order over the crop; m, the number of valid
+ *      pixels of the frame, is written to d_out_count (saturated to INT32_MAX).
+ *   2. Point of crop pixel (row r, column c), float64, one rounding per operation, no fma: with W, H, left, top from the
+ *      header and F = cam->focal (NULL cam: 241.42),
+ *          x = (((c + left) - W/2) * d) / F,   y = -((((r + top) - H/2) * d)) / F,   z = -d
+ *      (the header's W/2, H/2 as process.py uses them, not cam->cx / cy; invalid_eps and trunc_voxels are unused).
+ *   3. Resample (the rule of set_length): g = frame_base + i (mod 2^64), mix = splitmix64
+ *      (z += 0x9E3779B97F4A7C15; z = (z ^ z>>30) * 0xBF58476D1CE4E5B9; z = (z ^ z>>27) * 0x94D049BB133111EB;
+ *      z ^= z>>31, all mod 2^64), u(j) = mix(mix(seed + g) + j), k(j) = ((u >> 32) * m) >> 32 (exact product).
+ *      m < P: slot j < m takes valid pixel j and every later slot valid pixel k(j); m >= P: every slot takes k(j).
+ *   4. d_xforms != NULL (float64[n][24], the layout of tsdf_voxelize_aug_hip; only the forward rows are read): each
+ *      point becomes p'_i = (A_i0 x + A_i1 y) + (A_i2 z + b_i), products and sums rounded separately — the grouping the
+ *      inverse map of tsdf_voxelize_aug_hip uses.
+ *   5. A frame with m == 0 gets TSDF_FRAME_DEGENERATE, a frame that breaks the voxelizer's header rule
+ *      TSDF_FRAME_BAD_HEADER (its depth is not read, count 0); both get all-zero rows.  NULL d_out_points, n < 0,
+ *      points < 1 or a misaligned d_xforms return TSDF_ERR_INVALID_ARG before any device work; n == 0 is a no-op.
+ *   d_out_points  float64[n][P][3];  d_out_count, d_out_status  int32[n] or NULL.
+ * The library allocates nothing.  A crop of up to 98304 pixels (a 320x240 frame) is bitmapped in LDS in one pass; a
+ * larger one is counted first and then taken in windows of 98304 pixels, with the same result (the crop is read twice).
+ */
+int tsdf_point_clouds_hip(const float *d_depth, int64_t depth_len, const int64_t *d_offsets, const int32_t *d_headers,
+                          int n, int points, const tsdf_cam *cam, uint64_t seed, int64_t frame_base,
+                          const double *d_xforms, void *hip_stream, double *d_out_points, int32_t *d_out_count,
+                          int32_t *d_out_status);
+
 #ifdef __cplusplus
 }
 #endif
