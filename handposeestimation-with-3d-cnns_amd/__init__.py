@@ -12,12 +12,15 @@ Host side:                               packing (MSRA .bin reader / batch packe
 Full mode and evaluation:                pca (JointPCA, fit_joint_pca), project_joints, pose_error, joints_within,
                                          frames_within
 Point clouds:                            point_clouds (back-projected, resampled on the device), export.preprocess_tree
+The reference's process(), batched:      cloud_grids (grid placed on a cloud's extremes), process_batch (point_clouds ->
+                                         cloud_grids -> voxelize_grid)
 """
 from . import _lib  # noqa: F401
 from ._lib import TsdfCam, TsdfError, default_cam  # noqa: F401
-from .voxelize import (AabbBatch, PointCloudBatch, PoseError, TsdfBatch, aabb, denormalize_joints,  # noqa: F401
-                       frames_within, joints_within, normalize_joints, point_clouds, pose_error, project_joints,
-                       release_stream, voxel_pixels,
+from .voxelize import (AabbBatch, CloudGridBatch, PointCloudBatch, PoseError, ProcessBatch, TsdfBatch, aabb,  # noqa: F401
+                       cloud_grids, denormalize_joints,
+                       frames_within, joints_within, normalize_joints, point_clouds, pose_error, process_batch,
+                       project_joints, release_stream, voxel_pixels,
                        voxelize, voxelize_aug, voxelize_grid, voxelize_indexed, voxelize_labels)
 from .pca import JointPCA, fit_joint_pca  # noqa: F401
 from . import augment, dataset, export, packing, pca, shard, synth  # noqa: F401
@@ -30,4 +33,4 @@ __all__ = ["voxelize", "voxelize_labels", "voxelize_indexed", "ResidentLoader", 
            "default_cam", "cal_tsdf_cuda", "tsdf_f", "tsdf_cal", "DataProcess", "packing", "shard",
            "synth", "dataset", "MSRADepthDataset", "MSRA_Dataset", "VoxelLoader", "VoxelBatch", "normalize_joints", "denormalize_joints",
            "pca", "JointPCA", "fit_joint_pca", "project_joints", "pose_error", "PoseError", "joints_within", "frames_within",
-           "point_clouds", "PointCloudBatch"]
+           "point_clouds", "PointCloudBatch", "cloud_grids", "CloudGridBatch", "process_batch", "ProcessBatch"]

@@ -152,6 +152,8 @@ def _bind(L, path: str):
     L.tsdf_point_clouds_hip.restype = ctypes.c_int
     L.tsdf_point_clouds_hip.argtypes = [vp, ctypes.c_int64, vp, vp, ctypes.c_int, ctypes.c_int, cam_p, ctypes.c_uint64,
                                         ctypes.c_int64, vp, vp, vp, vp, vp]
+    L.tsdf_cloud_grid_hip.restype = ctypes.c_int
+    L.tsdf_cloud_grid_hip.argtypes = [vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, cam_p, vp, vp, vp, vp, vp, vp]
     L.tsdf_describe_launch.restype = ctypes.c_int
     L.tsdf_describe_launch.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_char_p, ctypes.c_int]
     return L

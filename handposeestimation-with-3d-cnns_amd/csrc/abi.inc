@@ -219,6 +219,13 @@ int tsdf_point_clouds_hip(const float *d_depth, int64_t depth_len, const int64_t
                           hip_stream, d_out_points, d_out_count, d_out_status);
 }
 
+int tsdf_cloud_grid_hip(const double *d_points, int n, int points, int R, const tsdf_cam *cam, void *hip_stream,
+                        float *d_out_grid, float *d_out_max_l, float *d_out_mid_p, float *d_out_aabb,
+                        int32_t *d_out_status) {
+  return run_cloud_grid(d_points, n, points, R, cam, hip_stream, d_out_grid, d_out_max_l, d_out_mid_p, d_out_aabb,
+                        d_out_status);
+}
+
 #ifdef TSDF_DEBUG_HOOKS   // the debug build only (make debug -> build/libtsdf_hip_debug.so): include/tsdf_debug.h
 int tsdf_debug_pixmap_hip(const float *d_depth, int64_t depth_len, const int64_t *d_offsets, const int32_t *d_headers,
                           int n, int R, const tsdf_cam *cam, int layout, void *hip_stream, const float *d_grid,

@@ -53,6 +53,7 @@
 //   kernels.inc  tsdf_fused_kernel, tsdf_split_kernel, tsdf_normalize_kernel, tsdf_project_kernel, tsdf_pose_error_kernel
 //   launch.inc   host side of a call: device check, split plan, instantiation choice, argument marshalling
 //   cloud.inc    tsdf_point_cloud_kernel and its host side (back-projected, resampled point clouds)
+//   cloudgrid.inc  tsdf_cloud_grid_kernel and its host side (grid placement from a point cloud: tsdf_f's first half)
 //   abi.inc      extern "C" — include/tsdf.h (and, under -DTSDF_DEBUG_HOOKS, include/tsdf_debug.h)
 //   tsdf_host.inc  host-only helpers, also compiled alone under the CPU sanitizers
 // Build-time switches: TSDF_DEBUG_HOOKS (debug build: test hooks), TSDF_STAMPS (diagnostic build: in-kernel timeline),
@@ -87,6 +88,7 @@ namespace {
 #include "kernels.inc"   // tsdf_fused_kernel, tsdf_split_kernel, tsdf_normalize_kernel, PCA / pose error
 #include "launch.inc"    // host side of a call
 #include "cloud.inc"     // tsdf_point_clouds_hip: point clouds resampled on the device
+#include "cloudgrid.inc" // tsdf_cloud_grid_hip: the grid placed on a cloud's extremes
 
 }  // namespace
 

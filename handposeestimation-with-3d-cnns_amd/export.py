@@ -17,9 +17,14 @@ which is what ``3D_CNN/dataset.py:93-131`` reads back.  ``preprocess_tree`` writ
 voxelization done by the HIP kernel: a gesture (~500 frames) is packed (``packing.pack_bin_files``), uploaded
 once and voxelized in one launch.
 
-Differences from the reference writer, all deliberate and switchable:
+Differences from the reference writer, all deliberate, each with the switch that undoes it:
   * grid placement uses ALL valid pixels (the numba path), not the random 6000-point
-    resample ``DataProcess.process()`` uses — the files are reproducible;
+    resample ``DataProcess.process()`` uses — the files do not depend on the draw.  ``placement="cloud"`` gives the
+    reference's rule back: ``TSDF/<g>.npz`` is then voxelized on the grid of the very cloud that is written to
+    ``Point_Cloud/<g>.npy`` (``voxelize.cloud_grids`` + ``voxelize_grid``), so the saved ``max_l`` / ``mid_p`` are a
+    function of the saved cloud, as in the reference's files.  It needs ``point_clouds`` on.  The ``_aug`` twins keep
+    the all-pixels placement of the augmented voxelizer (it has no entry with a caller-supplied grid); their maps are
+    centred on the ``mid_p`` that was written, and ``pca_dir`` uses the ``max_l`` / ``mid_p`` that were written;
   * arrays are float32 (the reader casts to float32 anyway, 3D_CNN/dataset.py:101-103); ``dtype=np.float64``
     gives the reference's ``np.empty`` default back;
   * layout is ``[c,x,y,z]`` — what the reference writer produced, since it went through the CPU loop
@@ -90,6 +95,22 @@ def _default_voxelize_aug(pk: packing.PackedFrames, xforms: np.ndarray, gt: np.n
     torch.cuda.synchronize(depth.device)
     return (out.tsdf.cpu().numpy(), out.max_l.cpu().numpy(), out.mid_p.cpu().numpy(), out.status.cpu().numpy(),
             gt_aug.cpu().numpy())
+
+
+def _default_voxelize_cloud(pk: packing.PackedFrames, cloud: np.ndarray, res: int, layout: str, device):
+    """Upload the pack and its clouds; grid placement from each cloud, then the volumes on that placement: host arrays
+    (tsdf, max_l, mid_p, status), status being the first non-zero of the two stages."""
+    import torch
+
+    from .voxelize import cloud_grids, voxelize_grid
+
+    depth, offsets, headers = pk.to_torch(device, pin=True, non_blocking=True)
+    pts = torch.from_numpy(np.ascontiguousarray(cloud, np.float64)).to(depth.device)
+    cg = cloud_grids(pts, res=res)
+    tsdf, st = voxelize_grid(depth, offsets, headers, cg.grid, res=res, layout=layout)
+    status = torch.where(cg.status != 0, cg.status, st)
+    torch.cuda.synchronize(depth.device)
+    return tsdf.cpu().numpy(), cg.max_l.cpu().numpy(), cg.mid_p.cpu().numpy(), status.cpu().numpy()
 
 
 def device_point_clouds(pk: packing.PackedFrames, points_num: int, seed: int, xforms: Optional[np.ndarray] = None,
@@ -185,7 +206,8 @@ def preprocess_tree(db_dir: str, save_dir: str, *, res: int = 32, layout: str = 
                     voxelize_fn: Optional[Callable] = None, verbose: bool = False,
                     pca_dir: Optional[str] = None, aug: bool = False,
                     aug_rng: Optional[np.random.Generator] = None,
-                    voxelize_aug_fn: Optional[Callable] = None) -> Dict[str, int]:
+                    voxelize_aug_fn: Optional[Callable] = None, placement: str = "pixels",
+                    voxelize_cloud_fn: Optional[Callable] = None) -> Dict[str, int]:
     """Replacement for ``read_MSRA.main()`` (pre/read_MSRA.py:37-140): voxelize a whole MSRA tree into ``save_dir`` in
     the reference's schema (with ``aug=True`` its AUG=True schema).  Returns ``{subject: frames}``.
 
@@ -193,6 +215,12 @@ def preprocess_tree(db_dir: str, save_dir: str, *, res: int = 32, layout: str = 
     ``voxelize_aug_fn(pack, xforms, gt, res, layout, device) -> (tsdf, max_l, mid_p, status, gt_aug)`` may replace the
     HIP calls (tests use them to check the file handling without a GPU); by default the HIP voxelizer runs and a
     missing library or device is an error.
+
+    ``placement``: "pixels" (default: the grid on all valid pixels) or "cloud" (the reference's rule: the grid on the
+    resampled cloud that is written to ``Point_Cloud``; needs ``point_clouds``).  With "cloud" the plain volumes come from
+    ``voxelize_cloud_fn(pack, cloud, res, layout, device) -> (tsdf, max_l, mid_p, status)``, ``cloud`` being the host
+    ``float64[n, points_num, 3]`` array that is saved (default: ``voxelize.cloud_grids`` + ``voxelize_grid``), and
+    ``voxelize_fn`` is not called.  The random draws and their order are those of the module docstring either way.
 
     ``point_clouds``: True / "host" (``resample_point_clouds`` on the host), "device" (``voxelize.point_clouds``) or
     False (no cloud files).  The draws of each are in the module docstring.
@@ -204,7 +232,12 @@ def preprocess_tree(db_dir: str, save_dir: str, *, res: int = 32, layout: str = 
         point_clouds = "host"
     if point_clouds not in (False, None, "host", "device"):
         raise ValueError('point_clouds must be True / "host", "device" or False')
+    if placement not in ("pixels", "cloud"):
+        raise ValueError('placement must be "pixels" or "cloud"')
+    if placement == "cloud" and not point_clouds:
+        raise ValueError('placement="cloud" places the grid on the saved cloud: it needs point_clouds="host" or "device"')
     vox = voxelize_fn if voxelize_fn is not None else _default_voxelize
+    vox_cloud = voxelize_cloud_fn if voxelize_cloud_fn is not None else _default_voxelize_cloud
     vox_aug = voxelize_aug_fn if voxelize_aug_fn is not None else _default_voxelize_aug
     rng = rng if rng is not None else np.random.default_rng()
     if aug:
@@ -224,16 +257,19 @@ def preprocess_tree(db_dir: str, save_dir: str, *, res: int = 32, layout: str = 
             g_dir = os.path.join(sub_in, ges)
             bin_num, gt = packing.read_joint(g_dir)
             pk = packing.pack_bin_files(packing.gesture_bin_paths(g_dir, bin_num))
-            tsdf, max_l, mid_p, status = vox(pk, res, layout, device)
-            if pca_dir is not None:
-                from .pca import normalize_labels_np
-                ok = np.asarray(max_l, np.float32) > 0 if status is None else np.asarray(status) == 0
-                labels.setdefault(sub, []).append(normalize_labels_np(gt, max_l, mid_p)[ok])
+            if placement == "pixels":
+                tsdf, max_l, mid_p, status = vox(pk, res, layout, device)
             pc = None
             if point_clouds == "host":
                 pc = resample_point_clouds(pk, points_num, rng)
             elif point_clouds == "device":
                 pc = device_point_clouds(pk, points_num, int(rng.integers(0, 2 ** 63)), device=device)
+            if placement == "cloud":
+                tsdf, max_l, mid_p, status = vox_cloud(pk, pc, res, layout, device)
+            if pca_dir is not None:
+                from .pca import normalize_labels_np
+                ok = np.asarray(max_l, np.float32) > 0 if status is None else np.asarray(status) == 0
+                labels.setdefault(sub, []).append(normalize_labels_np(gt, max_l, mid_p)[ok])
             write_gesture(sub_out, ges, np.asarray(tsdf, dtype), np.asarray(max_l, dtype),
                           np.asarray(mid_p, dtype), gt, status, pc, gt_3d)
             if aug:

@@ -623,3 +623,71 @@ def point_clouds(depth: torch.Tensor, offsets: torch.Tensor, headers: torch.Tens
                                          out.points.data_ptr(), out.count.data_ptr(), out.status.data_ptr())
         _lib.check(rc, "tsdf_point_clouds_hip")
     return out
+
+
+class CloudGridBatch(NamedTuple):
+    grid: torch.Tensor    # float32[n, 8]  vox_ori[3], voxel_len, trunc_dis, 0, 0, 0 (the ``grid`` of voxelize_grid)
+    max_l: torch.Tensor   # float32[n]
+    mid_p: torch.Tensor   # float32[n, 3]
+    aabb: torch.Tensor    # float32[n, 6]  min xyz, max xyz of the cloud (z over the points with z != 0)
+    status: torch.Tensor  # int32[n]  (_lib.TSDF_FRAME_*)
+
+
+def cloud_grids(points: torch.Tensor, res: int = 32, cam: Optional[_lib.TsdfCam] = None) -> CloudGridBatch:
+    """The grid placement ``tsdf_f(data, point_cloud)`` derives from the cloud it is handed (pre/tsdf_for.py:9-16 with
+    ``max_min_point``, :23-41) for n clouds in one launch (``tsdf_cloud_grid_hip``; the contract is in include/tsdf.h):
+    per-axis extremes as float32 (z over the points with z != 0), then the float32 glue.
+
+    points  float64[n, P, 3] on the GPU — what :func:`point_clouds` returns, or any other cloud.
+    Returns :class:`CloudGridBatch`; ``grid`` goes straight to :func:`voxelize_grid`.  A cloud without a z != 0, with a
+    NaN, of non-finite or zero extent is TSDF_FRAME_DEGENERATE: zero grid row, ``max_l`` 0.  Enqueues on the current
+    stream and returns without synchronising."""
+    L = _lib.load()
+    _dev_check("points", points, torch.float64)
+    dev = points.device
+    if points.dim() != 3 or points.shape[2] != 3:
+        raise ValueError("points must have shape [n, P, 3]")
+    n, P = int(points.shape[0]), int(points.shape[1])
+    if not 1 <= P <= 0x7fffffff:
+        raise ValueError("points must hold 1..2^31-1 points per frame")
+    if not L.tsdf_resolution_supported(int(res)):
+        raise ValueError(f"unsupported grid resolution {res} (multiple of 4 in 4..128)")
+    out = CloudGridBatch(torch.empty((n, 8), dtype=torch.float32, device=dev),
+                         torch.empty(n, dtype=torch.float32, device=dev),
+                         torch.empty((n, 3), dtype=torch.float32, device=dev),
+                         torch.empty((n, 6), dtype=torch.float32, device=dev),
+                         torch.empty(n, dtype=torch.int32, device=dev))
+    if n:
+        with _Current(dev):
+            rc = L.tsdf_cloud_grid_hip(points.data_ptr(), n, P, int(res), ctypes.byref(cam) if cam is not None else None,
+                                       _raw_stream(dev), out.grid.data_ptr(), out.max_l.data_ptr(), out.mid_p.data_ptr(),
+                                       out.aabb.data_ptr(), out.status.data_ptr())
+        _lib.check(rc, "tsdf_cloud_grid_hip")
+    return out
+
+
+class ProcessBatch(NamedTuple):
+    points: torch.Tensor  # float64[n, P, 3]  the resampled clouds
+    tsdf: torch.Tensor    # float32[n, 3, R, R, R]
+    max_l: torch.Tensor   # float32[n]
+    mid_p: torch.Tensor   # float32[n, 3]
+    status: torch.Tensor  # int32[n]  the first non-zero status of the three stages
+    count: torch.Tensor   # int32[n]  valid pixels of the frame
+
+
+def process_batch(depth: torch.Tensor, offsets: torch.Tensor, headers: torch.Tensor, points: int = 6000, seed: int = 0,
+                  frame_base: int = 0, res: int = 32, layout: str = "czyx",
+                  cam: Optional[_lib.TsdfCam] = None) -> ProcessBatch:
+    """``DataProcess.process()`` (pre/process.py:13-28) for n packed frames: back-project and resample the cloud
+    (:func:`point_clouds`), place the grid on the AABB of THAT cloud (:func:`cloud_grids` — the reference's rule; every
+    other batched path places it on all valid pixels) and voxelize with that placement (:func:`voxelize_grid`).  Three
+    launches on the current stream, no synchronisation, nothing on the host in between.
+
+    ``seed`` / ``frame_base`` as for :func:`point_clouds`: a batch split over several calls gives the same result.
+    A frame that is not OK in any stage has a zero volume and ``max_l`` 0; ``status`` is the first non-zero status among
+    the stages (cloud, grid, volume)."""
+    pc = point_clouds(depth, offsets, headers, points=points, seed=seed, frame_base=frame_base, cam=cam)
+    cg = cloud_grids(pc.points, res=res, cam=cam)
+    tsdf, st = voxelize_grid(depth, offsets, headers, cg.grid, res=res, layout=layout, cam=cam)
+    status = torch.where(pc.status != 0, pc.status, torch.where(cg.status != 0, cg.status, st))
+    return ProcessBatch(pc.points, tsdf, cg.max_l, cg.mid_p, status, pc.count)

@@ -436,6 +436,40 @@ int tsdf_point_clouds_hip(const float *d_depth, int64_t depth_len, const int64_t
                           const double *d_xforms, void *hip_stream, double *d_out_points, int32_t *d_out_count,
                           int32_t *d_out_status);
 
+/* ---- Grid placement from a point cloud (adds only; TSDF_ABI_VERSION stays 7) ----
+ * The first half of tsdf_f(data, point_cloud) (pre/tsdf_for.py:9-16 with max_min_point, :23-41) for n clouds in one
+ * launch: what DataProcess.process() (pre/process.py:13-28) places its grid on is the AABB of the RESAMPLED cloud, not
+ * of all valid pixels.  tsdf_point_clouds_hip -> tsdf_cloud_grid_hip -> tsdf_voxelize_grid_hip is that pipeline with
+ * nothing on the host in between.
+ *   1. d_points is float64[n][P][3] (P = points), the layout tsdf_point_clouds_hip writes, 8-byte aligned.  Any cloud is
+ *      accepted, not only one of this library.
+ *   2. Extremes: x and y over all P points; z over the points with z != 0 only (the test is on the float64 value: -0.0
+ *      is dropped, a denormal is kept).  Each extreme is the float64 extreme rounded to float32 (the kernel converts
+ *      first and reduces in float32; rounding to nearest is monotone, so the values are the same).  Where an extreme is
+ *      +-0 its sign is unspecified.
+ *   3. Glue, float32, one rounding per operation, in this order (pre/tsdf_for.py:11-16): mid = (max + min) / 2;
+ *      max_l = max_i(max_i - min_i); voxel_len = max_l / R; trunc_dis = voxel_len * cam->trunc_voxels (NULL cam: 3);
+ *      vox_ori = (mid - max_l / 2) + voxel_len / 2.
+ *   4. A frame with no point of z != 0, with a NaN among the values that enter an extreme (a NaN z is never dropped), with
+ *      a non-finite extent or centre, or with max_l == 0 gets TSDF_FRAME_DEGENERATE: its grid row is all zero,
+ *      max_l = 0, and mid_p is as computed when all three are finite (the zero-extent case), else 0 — the rule of
+ *      tsdf_frame_status above.  tsdf_voxelize_grid_hip then writes a zero volume for it (trunc_dis <= 0).  The
+ *      reference raises (np.max of an empty array) or goes on with a NaN grid for such clouds.  The all-zero cloud that
+ *      tsdf_point_clouds_hip writes for a frame that is not OK is such a frame.
+ *   5. n == 0 is a no-op.  n < 0, points < 1, an unsupported R, a NULL d_points / d_out_grid / d_out_max_l /
+ *      d_out_mid_p or a d_points that is not 8-byte aligned return TSDF_ERR_INVALID_ARG before any device work.  The
+ *      call never synchronises, allocates nothing, uses no atomics and no global state, is deterministic and may be
+ *      captured into a hipGraph.
+ *   d_out_grid   float32[n][8]  vox_ori[3], voxel_len, trunc_dis, 0, 0, 0 — the d_grid of tsdf_voxelize_grid_hip
+ *   d_out_max_l  float32[n]     d_out_mid_p  float32[n][3]
+ *   d_out_aabb   float32[n][6] or NULL: min x,y,z then max x,y,z; a zero row for a frame with a NaN or without any
+ *                z != 0 (the other not-OK frames keep their extremes)
+ *   d_out_status int32[n] or NULL
+ */
+int tsdf_cloud_grid_hip(const double *d_points, int n, int points, int R, const tsdf_cam *cam, void *hip_stream,
+                        float *d_out_grid, float *d_out_max_l, float *d_out_mid_p, float *d_out_aabb,
+                        int32_t *d_out_status);
+
 #ifdef __cplusplus
 }
 #endif

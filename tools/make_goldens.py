@@ -36,6 +36,11 @@ What each fixture pins:
   cal_out_ref  3D_CNN/train.py::cal_out (:410-427) RUN (train.py imported with a stub tqdm, from a scratch directory
           holding an empty result/) on seeded small-mode predictions decoded as train.py:263-266 does: inputs, per-joint
           errors (the torch.sqrt it takes), the proportion and err_mean.  Pins pose_error / joints_within.
+  process_ref_<k>  DataProcess.process()'s placement rule (pre/process.py:13-28): for every volume fixture's frame the
+          cloud of tests/point_cloud_ref.py (P = 6000, seed 7; its sha256 is kept, not the cloud) handed to
+          pre/tsdf_for.py::tsdf_f(data, cloud) — the grid on the AABB of the RESAMPLED cloud — with the tsdf_cal spy, and
+          the loop again on float64-typed parameters; max_min_point's own return values beside them.  A few frames
+          with P = 500 and P = 20000 carry the grid values only.  Pins tsdf_cloud_grid_hip / process_batch.
   aabb_*  the numba-typing AABB (pre/tsdf_numba.py:84-96,140-141) from
           oracle/tsdf_oracle_np.py — a restatement, not a run (min_max_kernel cannot
           be executed here: no usable numba, no params.py).
@@ -444,6 +449,100 @@ def run_unseen(outdir):
         print(f"{os.path.basename(fn)}: {len(out['names'])} frames, {os.path.getsize(fn)} bytes")
 
 
+PROCESS_PER_FILE = 8    # process_ref_<k>.npz: frames [8k, 8k+8) of volume_frames(), each file under 1 MiB
+PROCESS_P, PROCESS_SEED = 6000, 7
+PROCESS_GRID_ONLY = [("full_0", 500), ("crop_10", 500), ("sparse_1pct", 500), ("full_1", 20000), ("small_odd", 20000),
+                     ("mixed_halves", 20000)]     # (frame, P): grid values only, no volumes
+
+
+def process_cloud(header, depth, P, seed=PROCESS_SEED):
+    """The frame's resampled cloud float64[P,3] as tsdf_point_clouds_hip is specified (tests/point_cloud_ref.py)."""
+    tests = os.path.join(ROOT, "tests")
+    if tests not in sys.path:
+        sys.path.insert(0, tests)
+    import point_cloud_ref
+    off = np.array([0, depth.size], np.int64)
+    pts, _, st = point_cloud_ref.point_clouds(depth, off, np.asarray(header, np.int32).reshape(1, 6), P, seed=seed)
+    assert st[0] == 0
+    return pts[0]
+
+
+def cloud_digest(cloud):
+    import hashlib
+    return hashlib.sha256(np.ascontiguousarray(cloud, np.float64).tobytes()).hexdigest()
+
+
+def run_reference_process(header, depth, cloud, volumes=True):
+    """tsdf_f(data, cloud) of the reference, RUN: what it returned and what it passed to tsdf_cal; with ``volumes`` the
+    loop as it runs today (loop32) and on float64-typed parameters (loop64), both as float32 in [c,z,y,x]."""
+    tsdf_for, _, _ = _reference()
+    captured = {}
+    orig = tsdf_for.tsdf_cal
+
+    def spy(data, vox_ori, voxel_len, truncation):
+        captured["p"] = (np.array(vox_ori), voxel_len, truncation)
+        return orig(data, vox_ori, voxel_len, truncation) if volumes else None
+
+    tsdf_for.tsdf_cal = spy
+    try:
+        loop32, max_l, mid_p = tsdf_for.tsdf_f({"header": header, "depth": depth}, cloud)
+    finally:
+        tsdf_for.tsdf_cal = orig
+    vox_ori, voxel_len, truncation = captured["p"]
+    assert vox_ori.dtype == np.float32 and np.asarray(voxel_len).dtype == np.float32
+    assert np.asarray(max_l).dtype == np.float32 and np.asarray(mid_p).dtype == np.float32
+    pmax, pmin = tsdf_for.max_min_point(cloud)
+    g = dict(header=np.asarray(header, np.int32), point_max=pmax, point_min=pmin, max_l=np.float32(max_l),
+             mid_p=np.asarray(mid_p, np.float32), vox_ori=vox_ori, voxel_len=np.float32(voxel_len),
+             trunc=np.float32(truncation))
+    if volumes:
+        data64 = {"header": header, "depth": depth.astype(np.float64)}
+        loop64 = orig(data64, vox_ori.astype(np.float64), np.float64(voxel_len), np.float64(truncation))
+        l32 = np.ascontiguousarray(loop32.transpose(0, 3, 2, 1)).astype(np.float32)
+        l64 = np.ascontiguousarray(loop64.transpose(0, 3, 2, 1)).astype(np.float32)
+        assert np.array_equal(l32.astype(np.float64), loop32.transpose(0, 3, 2, 1)), "loop32 holds f32 values"
+        diff = np.flatnonzero(l32.view(np.uint32) != l64.view(np.uint32))
+        g.update(loop64=l64, loop32_diff_index=diff.astype(np.int64), loop32_diff_value=l32.reshape(-1)[diff],
+                 n_flip=np.int64((np.abs(l32 - l64) > 1e-5).any(axis=0).sum()))
+    return g
+
+
+def run_process(outdir):
+    """process_ref_<k>.npz.  Touches no other fixture and not MANIFEST.txt."""
+    frames = volume_frames()
+    by_name = {name: (h, d) for name, h, d in frames}
+    recs = []
+    for name, h, d in frames:
+        cloud = process_cloud(h, d, PROCESS_P)
+        with np.errstate(all="ignore"):
+            g = run_reference_process(h, d, cloud)
+        g.update(P=np.int64(PROCESS_P), seed=np.int64(PROCESS_SEED), depth_sha256=np.array(depth_digest(d)),
+                 cloud_sha256=np.array(cloud_digest(cloud)))
+        recs.append((name, g))
+        print(f"{name}: valid {int((d != 0).sum())} max_l {float(g['max_l']):.4f} loop32 != loop64 on "
+              f"{g['loop32_diff_index'].size} voxels ({int(g['n_flip'])} by more than 1e-5)")
+    k = 0
+    for k in range(0, len(recs), PROCESS_PER_FILE):
+        part = recs[k:k + PROCESS_PER_FILE]
+        out = {"names": np.array([name for name, _ in part])}
+        for i, (_, g) in enumerate(part):
+            out.update({f"f{i}_{key}": v for key, v in g.items()})
+        fn = os.path.join(outdir, f"process_ref_{k // PROCESS_PER_FILE}.npz")
+        np.savez_compressed(fn, **out)
+        print(f"{os.path.basename(fn)}: {len(part)} frames, {os.path.getsize(fn)} bytes")
+    out = {"names": np.array([f"{name}@P{P}" for name, P in PROCESS_GRID_ONLY])}
+    for i, (name, P) in enumerate(PROCESS_GRID_ONLY):
+        h, d = by_name[name]
+        cloud = process_cloud(h, d, P)
+        g = run_reference_process(h, d, cloud, volumes=False)
+        g.update(P=np.int64(P), seed=np.int64(PROCESS_SEED), depth_sha256=np.array(depth_digest(d)),
+                 cloud_sha256=np.array(cloud_digest(cloud)))
+        out.update({f"f{i}_{key}": v for key, v in g.items()})
+    fn = os.path.join(outdir, f"process_ref_{k // PROCESS_PER_FILE + 1}.npz")
+    np.savez_compressed(fn, **out)
+    print(f"{os.path.basename(fn)}: {len(PROCESS_GRID_ONLY)} frames (grid values only), {os.path.getsize(fn)} bytes")
+
+
 def run_reference_cal_out(outdir):
     """cal_out_ref.npz: the reference's own evaluation (3D_CNN/train.py::cal_out) on seeded normalised predictions of
     16 frames, decoded to mm with the reference's small-mode expression (train.py:263-266) in float32 torch."""
@@ -503,7 +602,7 @@ def main(only=None):
     outdir = os.path.join(ROOT, "tests", "golden")
     os.makedirs(outdir, exist_ok=True)
     steps = {"aug": run_reference_aug, "io": run_reference_io, "dataset": run_reference_dataset, "volumes": run_volumes,
-             "unseen": run_unseen, "cal_out": run_reference_cal_out}
+             "unseen": run_unseen, "cal_out": run_reference_cal_out, "process": run_process}
     for name in (only or list(steps)):   # --only: some of the fixtures, the others untouched (npz files carry time stamps)
         steps[name](outdir)
 
@@ -513,5 +612,5 @@ if __name__ == "__main__":
 
     ap = argparse.ArgumentParser(description="Regenerate tests/golden/*.npz by running the reference's own code "
                                              "(needs /root/reference).")
-    ap.add_argument("--only", default="", help="comma list of aug,io,dataset,volumes,unseen,cal_out: just these fixtures")
+    ap.add_argument("--only", default="", help="comma list of aug,io,dataset,volumes,unseen,cal_out,process: just these fixtures")
     main([x for x in ap.parse_args().only.split(",") if x])
