@@ -18,7 +18,7 @@ The reference's process(), batched:      cloud_grids (grid placed on a cloud's e
 from . import _lib  # noqa: F401
 from ._lib import TsdfCam, TsdfError, default_cam  # noqa: F401
 from .voxelize import (AabbBatch, CloudGridBatch, PointCloudBatch, PoseError, ProcessBatch, TsdfBatch, aabb,  # noqa: F401
-                       cloud_grids, denormalize_joints,
+                       cloud_grids, denormalize_joints, empty_batch,
                        frames_within, joints_within, normalize_joints, point_clouds, pose_error, process_batch,
                        project_joints, release_stream, voxel_pixels,
                        voxelize, voxelize_aug, voxelize_grid, voxelize_indexed, voxelize_labels)

@@ -89,8 +89,9 @@ _lib = None
 _debug_lib = None
 
 
-def _bind(L, path: str):
-    """Declare the argument / result types of every entry point of include/tsdf.h on a loaded library."""
+def _bind(L, path: str, debug: bool = False):
+    """Declare the argument / result types of every entry point of include/tsdf.h on a loaded library (``debug``: and of
+    the hooks of include/tsdf_debug.h)."""
     vp = ctypes.c_void_p
     cam_p = ctypes.POINTER(TsdfCam)
     L.tsdf_version.restype = ctypes.c_int
@@ -103,59 +104,41 @@ def _bind(L, path: str):
     L.tsdf_resolution_supported.argtypes = [ctypes.c_int]
     L.tsdf_default_cam.restype = None
     L.tsdf_default_cam.argtypes = [cam_p]
-    L.tsdf_voxelize_hip.restype = ctypes.c_int
-    L.tsdf_voxelize_hip.argtypes = [vp, ctypes.c_int64, vp, vp, ctypes.c_int, ctypes.c_int, cam_p, ctypes.c_int, vp,
-                                    vp, vp, vp, vp]
-    L.tsdf_voxelize_grid_hip.restype = ctypes.c_int
-    L.tsdf_voxelize_grid_hip.argtypes = [vp, ctypes.c_int64, vp, vp, ctypes.c_int, ctypes.c_int, cam_p, ctypes.c_int, vp,
-                                         vp, vp, vp]
-    L.tsdf_voxelize_aug_hip.restype = ctypes.c_int
-    L.tsdf_voxelize_aug_hip.argtypes = [vp, ctypes.c_int64, vp, vp, ctypes.c_int, ctypes.c_int, cam_p, ctypes.c_int, vp,
-                                        vp, vp, vp, vp, vp]
-    L.tsdf_aabb_hip.restype = ctypes.c_int
-    L.tsdf_aabb_hip.argtypes = [vp, ctypes.c_int64, vp, vp, ctypes.c_int, ctypes.c_int, cam_p, vp, vp, vp, vp, vp]
-    lab_p = ctypes.POINTER(TsdfLabels)
-    L.tsdf_voxelize_labels_hip.restype = ctypes.c_int
-    L.tsdf_voxelize_labels_hip.argtypes = L.tsdf_voxelize_hip.argtypes + [lab_p]
-    L.tsdf_voxelize_aug_labels_hip.restype = ctypes.c_int
-    L.tsdf_voxelize_aug_labels_hip.argtypes = L.tsdf_voxelize_aug_hip.argtypes + [lab_p]
-    L.tsdf_voxelize_indexed_hip.restype = ctypes.c_int
-    L.tsdf_voxelize_indexed_hip.argtypes = [vp, ctypes.c_int64, vp, vp, ctypes.c_int64, vp, ctypes.c_int, ctypes.c_int,
-                                            cam_p, ctypes.c_int, vp, vp, vp, vp, vp, lab_p]
-    L.tsdf_voxelize_indexed_host_hip.restype = ctypes.c_int
-    L.tsdf_voxelize_indexed_host_hip.argtypes = L.tsdf_voxelize_indexed_hip.argtypes
-    L.tsdf_voxelize_indexed_aug_hip.restype = ctypes.c_int
-    L.tsdf_voxelize_indexed_aug_hip.argtypes = [vp, ctypes.c_int64, vp, vp, ctypes.c_int64, vp, ctypes.c_int, ctypes.c_int,
-                                                cam_p, ctypes.c_int, vp, vp, vp, vp, vp, vp, lab_p]
-    L.tsdf_host_gather_frames.restype = ctypes.c_int
-    L.tsdf_host_gather_frames.argtypes = [vp, vp, ctypes.c_int64, vp, ctypes.c_int64, vp, ctypes.c_int64, vp, ctypes.c_int]
-    L.tsdf_host_gather_frames_n.restype = ctypes.c_int
-    L.tsdf_host_gather_frames_n.argtypes = [vp, ctypes.c_int64, vp, ctypes.c_int64, vp, ctypes.c_int64, vp, ctypes.c_int64, vp,
-                                            ctypes.c_int]
-    L.tsdf_normalize_joints_hip.restype = ctypes.c_int
-    L.tsdf_normalize_joints_hip.argtypes = [vp, vp, vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, vp, vp]
-    L.tsdf_denormalize_joints_hip.restype = ctypes.c_int
-    L.tsdf_denormalize_joints_hip.argtypes = [vp, vp, vp, ctypes.c_int, ctypes.c_int, vp, vp]
-    L.tsdf_stream_release.restype = ctypes.c_int
-    L.tsdf_stream_release.argtypes = [vp]
-    pca_p = ctypes.POINTER(TsdfPca)
-    L.tsdf_voxelize_labels_pca_hip.restype = ctypes.c_int
-    L.tsdf_voxelize_labels_pca_hip.argtypes = L.tsdf_voxelize_aug_hip.argtypes + [lab_p, pca_p]
-    L.tsdf_voxelize_indexed_pca_hip.restype = ctypes.c_int
-    L.tsdf_voxelize_indexed_pca_hip.argtypes = L.tsdf_voxelize_indexed_aug_hip.argtypes + [pca_p]
-    L.tsdf_voxelize_indexed_host_pca_hip.restype = ctypes.c_int
-    L.tsdf_voxelize_indexed_host_pca_hip.argtypes = L.tsdf_voxelize_indexed_hip.argtypes + [pca_p]
-    L.tsdf_project_joints_hip.restype = ctypes.c_int
-    L.tsdf_project_joints_hip.argtypes = [vp, vp, vp, ctypes.c_int, ctypes.c_int, pca_p, vp]
-    L.tsdf_pose_error_hip.restype = ctypes.c_int
-    L.tsdf_pose_error_hip.argtypes = [vp, pca_p, vp, vp, vp, ctypes.c_int, ctypes.c_int, vp, vp, vp, vp, vp]
-    L.tsdf_point_clouds_hip.restype = ctypes.c_int
-    L.tsdf_point_clouds_hip.argtypes = [vp, ctypes.c_int64, vp, vp, ctypes.c_int, ctypes.c_int, cam_p, ctypes.c_uint64,
-                                        ctypes.c_int64, vp, vp, vp, vp, vp]
-    L.tsdf_cloud_grid_hip.restype = ctypes.c_int
-    L.tsdf_cloud_grid_hip.argtypes = [vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, cam_p, vp, vp, vp, vp, vp, vp]
-    L.tsdf_describe_launch.restype = ctypes.c_int
-    L.tsdf_describe_launch.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_char_p, ctypes.c_int]
+    lab_p, pca_p = ctypes.POINTER(TsdfLabels), ctypes.POINTER(TsdfPca)
+    i, i64 = ctypes.c_int, ctypes.c_int64
+    pack = [vp, i64, vp, vp, i, i, cam_p, i, vp]              # depth, depth_len, offsets, headers, n, R, cam, layout, stream
+    indexed = [vp, i64, vp, vp, i64, vp, i, i, cam_p, i, vp]  # ... headers, n_pack, index, n, R, cam, layout, stream
+    outs = [vp, vp, vp, vp]                                   # tsdf, max_l, mid_p, status
+    for name, argtypes in {
+            "tsdf_voxelize_hip": pack + outs,
+            "tsdf_voxelize_labels_hip": pack + outs + [lab_p],
+            "tsdf_voxelize_grid_hip": pack + [vp, vp, vp],                       # grid, tsdf, status
+            "tsdf_voxelize_aug_hip": pack + [vp] + outs,                         # xforms
+            "tsdf_voxelize_aug_labels_hip": pack + [vp] + outs + [lab_p],
+            "tsdf_voxelize_labels_pca_hip": pack + [vp] + outs + [lab_p, pca_p],
+            "tsdf_aabb_hip": pack[:7] + [vp] + [vp, vp, vp, vp],                 # no layout; aabb, grid, ori, status
+            "tsdf_voxelize_indexed_hip": indexed + outs + [lab_p],
+            "tsdf_voxelize_indexed_host_hip": indexed + outs + [lab_p],
+            "tsdf_voxelize_indexed_aug_hip": indexed + [vp] + outs + [lab_p],
+            "tsdf_voxelize_indexed_pca_hip": indexed + [vp] + outs + [lab_p, pca_p],
+            "tsdf_voxelize_indexed_host_pca_hip": indexed + outs + [lab_p, pca_p],
+            "tsdf_host_gather_frames": [vp, vp, i64, vp, i64, vp, i64, vp, i],
+            "tsdf_host_gather_frames_n": [vp, i64, vp, i64, vp, i64, vp, i64, vp, i],
+            "tsdf_normalize_joints_hip": [vp, vp, vp, i, i, i, vp, vp],
+            "tsdf_denormalize_joints_hip": [vp, vp, vp, i, i, vp, vp],
+            "tsdf_stream_release": [vp],
+            "tsdf_project_joints_hip": [vp, vp, vp, i, i, pca_p, vp],
+            "tsdf_pose_error_hip": [vp, pca_p, vp, vp, vp, i, i, vp, vp, vp, vp, vp],
+            "tsdf_point_clouds_hip": pack[:4] + [i, i, cam_p, ctypes.c_uint64, i64, vp, vp, vp, vp, vp],
+            "tsdf_cloud_grid_hip": [vp, i, i, i, cam_p, vp, vp, vp, vp, vp, vp],
+            "tsdf_describe_launch": [i, i, i, i, ctypes.c_char_p, i],
+            "tsdf_debug_pixmap_hip": pack + [vp, vp, vp, vp],                    # grid, tsdf, pixmap, status
+            "tsdf_debug_set_queue_word": [vp, ctypes.c_uint64],
+    }.items():
+        if not name.startswith("tsdf_debug_") or debug:
+            fn = getattr(L, name)
+            fn.restype = i
+            fn.argtypes = argtypes
     return L
 
 
@@ -182,13 +165,7 @@ def load_debug():
     if not os.path.exists(DEBUG_LIB_PATH):
         raise ImportError(f"{DEBUG_LIB_PATH} not found: build it with `make -C handposeestimation-with-3d-cnns_amd/csrc debug` "
                           "(__graft_entry__.build() does)")
-    L = _bind(ctypes.CDLL(DEBUG_LIB_PATH), DEBUG_LIB_PATH)
-    vp = ctypes.c_void_p
-    L.tsdf_debug_pixmap_hip.restype = ctypes.c_int
-    L.tsdf_debug_pixmap_hip.argtypes = [vp, ctypes.c_int64, vp, vp, ctypes.c_int, ctypes.c_int, ctypes.POINTER(TsdfCam),
-                                        ctypes.c_int, vp, vp, vp, vp, vp]
-    L.tsdf_debug_set_queue_word.restype = ctypes.c_int
-    L.tsdf_debug_set_queue_word.argtypes = [vp, ctypes.c_uint64]
+    L = _bind(ctypes.CDLL(DEBUG_LIB_PATH), DEBUG_LIB_PATH, debug=True)
     _debug_lib = L
     return L
 

@@ -1,5 +1,8 @@
 // abi.inc — the C ABI of include/tsdf.h (included by tsdf_hip.hip after its anonymous namespace).
 
+// Every voxelizer entry describes its call (Frames, Outs, RunOpts with the bits of what it needs) and returns run():
+// all argument checks are tsdf_host::check_run_args, called there.
+
 extern "C" {
 
 void tsdf_default_cam(tsdf_cam *cam) {
@@ -23,48 +26,46 @@ int tsdf_resolution_supported(int R) { return R >= 4 && R <= kMaxR && (R % 4) ==
 int tsdf_voxelize_hip(const float *d_depth, int64_t depth_len, const int64_t *d_offsets, const int32_t *d_headers, int n,
                       int R, const tsdf_cam *cam, int layout, void *hip_stream, float *d_out_tsdf,
                       float *d_out_max_l, float *d_out_mid_p, int32_t *d_out_status) {
-  if (n > 0 && (!d_out_tsdf || !d_out_max_l || !d_out_mid_p)) return TSDF_ERR_INVALID_ARG;
-  return run(d_depth, depth_len, d_offsets, d_headers, n, R, cam, layout, hip_stream, d_out_tsdf, d_out_max_l,
-             d_out_mid_p, d_out_status, RunOpts{});
+  RunOpts o;
+  o.needs = kNeedPlacement;
+  return run(Frames{d_depth, depth_len, d_offsets, d_headers, n, R, cam, layout, hip_stream},
+             Outs{d_out_tsdf, d_out_max_l, d_out_mid_p, d_out_status}, o);
 }
 
 int tsdf_voxelize_labels_hip(const float *d_depth, int64_t depth_len, const int64_t *d_offsets, const int32_t *d_headers,
                              int n, int R, const tsdf_cam *cam, int layout, void *hip_stream, float *d_out_tsdf,
                              float *d_out_max_l, float *d_out_mid_p, int32_t *d_out_status, const tsdf_labels *labels) {
-  if (n > 0 && (!d_out_tsdf || !d_out_max_l || !d_out_mid_p)) return TSDF_ERR_INVALID_ARG;
-  if (!labels) return TSDF_ERR_INVALID_ARG;
   RunOpts o;
+  o.needs = kNeedPlacement | kNeedLabels;
   o.labels = labels;
-  return run(d_depth, depth_len, d_offsets, d_headers, n, R, cam, layout, hip_stream, d_out_tsdf, d_out_max_l,
-             d_out_mid_p, d_out_status, o);
+  return run(Frames{d_depth, depth_len, d_offsets, d_headers, n, R, cam, layout, hip_stream},
+             Outs{d_out_tsdf, d_out_max_l, d_out_mid_p, d_out_status}, o);
 }
 
 int tsdf_voxelize_indexed_hip(const float *d_depth, int64_t depth_len, const int64_t *d_offsets, const int32_t *d_headers,
                               int64_t n_pack, const int64_t *d_index, int n, int R, const tsdf_cam *cam, int layout,
                               void *hip_stream, float *d_out_tsdf, float *d_out_max_l, float *d_out_mid_p,
                               int32_t *d_out_status, const tsdf_labels *labels) {
-  if (n > 0 && (!d_out_tsdf || !d_out_max_l || !d_out_mid_p || !d_index)) return TSDF_ERR_INVALID_ARG;
-  if (n_pack < 0 || (n > 0 && n_pack == 0)) return TSDF_ERR_INVALID_ARG;
   RunOpts o;
+  o.needs = kNeedPlacement | kNeedIndex;
   o.labels = labels;
   o.index = d_index;
   o.n_src = n_pack;
-  return run(d_depth, depth_len, d_offsets, d_headers, n, R, cam, layout, hip_stream, d_out_tsdf, d_out_max_l,
-             d_out_mid_p, d_out_status, o);
+  return run(Frames{d_depth, depth_len, d_offsets, d_headers, n, R, cam, layout, hip_stream},
+             Outs{d_out_tsdf, d_out_max_l, d_out_mid_p, d_out_status}, o);
 }
 
 int tsdf_voxelize_indexed_host_hip(const float *d_depth, int64_t depth_len, const int64_t *d_offsets,
                                    const int32_t *d_headers, int64_t n_pack, const int64_t *h_index, int n, int R,
                                    const tsdf_cam *cam, int layout, void *hip_stream, float *d_out_tsdf, float *d_out_max_l,
                                    float *d_out_mid_p, int32_t *d_out_status, const tsdf_labels *labels) {
-  if (n > 0 && (!d_out_tsdf || !d_out_max_l || !d_out_mid_p || !h_index)) return TSDF_ERR_INVALID_ARG;
-  if (n_pack < 0 || (n > 0 && n_pack == 0) || n > TSDF_INLINE_INDEX_MAX) return TSDF_ERR_INVALID_ARG;
   RunOpts o;
+  o.needs = kNeedPlacement | kNeedHostIndex;
   o.labels = labels;
   o.h_index = h_index;
   o.n_src = n_pack;
-  return run(d_depth, depth_len, d_offsets, d_headers, n, R, cam, layout, hip_stream, d_out_tsdf, d_out_max_l,
-             d_out_mid_p, d_out_status, o);
+  return run(Frames{d_depth, depth_len, d_offsets, d_headers, n, R, cam, layout, hip_stream},
+             Outs{d_out_tsdf, d_out_max_l, d_out_mid_p, d_out_status}, o);
 }
 
 int tsdf_voxelize_indexed_aug_hip(const float *d_depth, int64_t depth_len, const int64_t *d_offsets,
@@ -72,49 +73,46 @@ int tsdf_voxelize_indexed_aug_hip(const float *d_depth, int64_t depth_len, const
                                   const tsdf_cam *cam, int layout, void *hip_stream, const double *d_xforms,
                                   float *d_out_tsdf, float *d_out_max_l, float *d_out_mid_p, int32_t *d_out_status,
                                   const tsdf_labels *labels) {
-  if (n > 0 && (!d_out_tsdf || !d_out_max_l || !d_out_mid_p || !d_index || !d_xforms)) return TSDF_ERR_INVALID_ARG;
-  if (n_pack < 0 || (n > 0 && n_pack == 0) || (reinterpret_cast<uintptr_t>(d_xforms) & 7)) return TSDF_ERR_INVALID_ARG;
   RunOpts o;
+  o.needs = kNeedPlacement | kNeedIndex | kNeedXforms;
   o.labels = labels;
   o.index = d_index;
   o.n_src = n_pack;
   o.xforms = d_xforms;
-  return run(d_depth, depth_len, d_offsets, d_headers, n, R, cam, layout, hip_stream, d_out_tsdf, d_out_max_l,
-             d_out_mid_p, d_out_status, o);
+  return run(Frames{d_depth, depth_len, d_offsets, d_headers, n, R, cam, layout, hip_stream},
+             Outs{d_out_tsdf, d_out_max_l, d_out_mid_p, d_out_status}, o);
 }
 
 int tsdf_voxelize_grid_hip(const float *d_depth, int64_t depth_len, const int64_t *d_offsets, const int32_t *d_headers, int n,
                            int R, const tsdf_cam *cam, int layout, void *hip_stream, const float *d_grid,
                            float *d_out_tsdf, int32_t *d_out_status) {
-  if (n > 0 && (!d_out_tsdf || !d_grid)) return TSDF_ERR_INVALID_ARG;
   RunOpts o;
+  o.needs = kNeedGridIn;
   o.grid_in = d_grid;
-  return run(d_depth, depth_len, d_offsets, d_headers, n, R, cam, layout, hip_stream, d_out_tsdf, nullptr, nullptr,
-             d_out_status, o);
+  return run(Frames{d_depth, depth_len, d_offsets, d_headers, n, R, cam, layout, hip_stream},
+             Outs{d_out_tsdf, nullptr, nullptr, d_out_status}, o);
 }
 
 int tsdf_voxelize_aug_hip(const float *d_depth, int64_t depth_len, const int64_t *d_offsets, const int32_t *d_headers, int n,
                           int R, const tsdf_cam *cam, int layout, void *hip_stream, const double *d_xforms,
                           float *d_out_tsdf, float *d_out_max_l, float *d_out_mid_p, int32_t *d_out_status) {
-  if (n > 0 && (!d_out_tsdf || !d_out_max_l || !d_out_mid_p || !d_xforms)) return TSDF_ERR_INVALID_ARG;
-  if (reinterpret_cast<uintptr_t>(d_xforms) & 7) return TSDF_ERR_INVALID_ARG;
   RunOpts o;
+  o.needs = kNeedPlacement | kNeedXforms;
   o.xforms = d_xforms;
-  return run(d_depth, depth_len, d_offsets, d_headers, n, R, cam, layout, hip_stream, d_out_tsdf, d_out_max_l,
-             d_out_mid_p, d_out_status, o);
+  return run(Frames{d_depth, depth_len, d_offsets, d_headers, n, R, cam, layout, hip_stream},
+             Outs{d_out_tsdf, d_out_max_l, d_out_mid_p, d_out_status}, o);
 }
 
 int tsdf_voxelize_aug_labels_hip(const float *d_depth, int64_t depth_len, const int64_t *d_offsets,
                                  const int32_t *d_headers, int n, int R, const tsdf_cam *cam, int layout,
                                  void *hip_stream, const double *d_xforms, float *d_out_tsdf, float *d_out_max_l,
                                  float *d_out_mid_p, int32_t *d_out_status, const tsdf_labels *labels) {
-  if (n > 0 && (!d_out_tsdf || !d_out_max_l || !d_out_mid_p || !d_xforms)) return TSDF_ERR_INVALID_ARG;
-  if ((reinterpret_cast<uintptr_t>(d_xforms) & 7) || !labels) return TSDF_ERR_INVALID_ARG;
   RunOpts o;
+  o.needs = kNeedPlacement | kNeedXforms | kNeedLabels;
   o.xforms = d_xforms;
   o.labels = labels;
-  return run(d_depth, depth_len, d_offsets, d_headers, n, R, cam, layout, hip_stream, d_out_tsdf, d_out_max_l,
-             d_out_mid_p, d_out_status, o);
+  return run(Frames{d_depth, depth_len, d_offsets, d_headers, n, R, cam, layout, hip_stream},
+             Outs{d_out_tsdf, d_out_max_l, d_out_mid_p, d_out_status}, o);
 }
 
 int tsdf_aabb_hip(const float *d_depth, int64_t depth_len, const int64_t *d_offsets, const int32_t *d_headers, int n, int R,
@@ -125,8 +123,8 @@ int tsdf_aabb_hip(const float *d_depth, int64_t depth_len, const int64_t *d_offs
   o.grid = d_out_grid;
   o.ori = d_out_ori;
   o.aabb_only = 1;
-  return run(d_depth, depth_len, d_offsets, d_headers, n, R, cam, TSDF_LAYOUT_CZYX, hip_stream, nullptr, nullptr,
-             nullptr, d_out_status, o);
+  return run(Frames{d_depth, depth_len, d_offsets, d_headers, n, R, cam, TSDF_LAYOUT_CZYX, hip_stream},
+             Outs{nullptr, nullptr, nullptr, d_out_status}, o);
 }
 
 int tsdf_normalize_joints_hip(const float *d_gt, const float *d_max_l, const float *d_mid_p, int n, int n_joints,
@@ -139,27 +137,19 @@ int tsdf_denormalize_joints_hip(const float *d_pred, const float *d_max_l, const
   return run_normalize(d_pred, d_max_l, d_mid_p, n, n_joints, 0, 1, hip_stream, d_out_joints);
 }
 
-// ---- joint PCA and pose error: every argument is checked here, before run() looks at the device ----
-static int pca_entry_args(int n, const tsdf_labels *labels, const tsdf_pca *pca) {
-  if (!labels || !pca) return TSDF_ERR_INVALID_ARG;
-  return tsdf_host::check_pca(pca, n, labels->n_joints, true);
-}
-
+// ---- joint PCA and pose error ----
 int tsdf_voxelize_labels_pca_hip(const float *d_depth, int64_t depth_len, const int64_t *d_offsets,
                                  const int32_t *d_headers, int n, int R, const tsdf_cam *cam, int layout,
                                  void *hip_stream, const double *d_xforms, float *d_out_tsdf, float *d_out_max_l,
                                  float *d_out_mid_p, int32_t *d_out_status, const tsdf_labels *labels,
                                  const tsdf_pca *pca) {
-  if (n > 0 && (!d_out_tsdf || !d_out_max_l || !d_out_mid_p)) return TSDF_ERR_INVALID_ARG;
-  if (reinterpret_cast<uintptr_t>(d_xforms) & 7) return TSDF_ERR_INVALID_ARG;
-  const int chk = pca_entry_args(n, labels, pca);
-  if (chk != TSDF_OK) return chk;
   RunOpts o;
+  o.needs = kNeedPlacement | kNeedLabels | kNeedPca;   // (xforms is optional here)
   o.xforms = d_xforms;
   o.labels = labels;
   o.pca = pca;
-  return run(d_depth, depth_len, d_offsets, d_headers, n, R, cam, layout, hip_stream, d_out_tsdf, d_out_max_l,
-             d_out_mid_p, d_out_status, o);
+  return run(Frames{d_depth, depth_len, d_offsets, d_headers, n, R, cam, layout, hip_stream},
+             Outs{d_out_tsdf, d_out_max_l, d_out_mid_p, d_out_status}, o);
 }
 
 int tsdf_voxelize_indexed_pca_hip(const float *d_depth, int64_t depth_len, const int64_t *d_offsets,
@@ -167,18 +157,15 @@ int tsdf_voxelize_indexed_pca_hip(const float *d_depth, int64_t depth_len, const
                                   const tsdf_cam *cam, int layout, void *hip_stream, const double *d_xforms,
                                   float *d_out_tsdf, float *d_out_max_l, float *d_out_mid_p, int32_t *d_out_status,
                                   const tsdf_labels *labels, const tsdf_pca *pca) {
-  if (n > 0 && (!d_out_tsdf || !d_out_max_l || !d_out_mid_p || !d_index)) return TSDF_ERR_INVALID_ARG;
-  if (n_pack < 0 || (n > 0 && n_pack == 0) || (reinterpret_cast<uintptr_t>(d_xforms) & 7)) return TSDF_ERR_INVALID_ARG;
-  const int chk = pca_entry_args(n, labels, pca);
-  if (chk != TSDF_OK) return chk;
   RunOpts o;
+  o.needs = kNeedPlacement | kNeedIndex | kNeedLabels | kNeedPca;   // (xforms is optional here)
   o.labels = labels;
   o.index = d_index;
   o.n_src = n_pack;
   o.xforms = d_xforms;
   o.pca = pca;
-  return run(d_depth, depth_len, d_offsets, d_headers, n, R, cam, layout, hip_stream, d_out_tsdf, d_out_max_l,
-             d_out_mid_p, d_out_status, o);
+  return run(Frames{d_depth, depth_len, d_offsets, d_headers, n, R, cam, layout, hip_stream},
+             Outs{d_out_tsdf, d_out_max_l, d_out_mid_p, d_out_status}, o);
 }
 
 int tsdf_voxelize_indexed_host_pca_hip(const float *d_depth, int64_t depth_len, const int64_t *d_offsets,
@@ -186,17 +173,14 @@ int tsdf_voxelize_indexed_host_pca_hip(const float *d_depth, int64_t depth_len, 
                                        const tsdf_cam *cam, int layout, void *hip_stream, float *d_out_tsdf,
                                        float *d_out_max_l, float *d_out_mid_p, int32_t *d_out_status,
                                        const tsdf_labels *labels, const tsdf_pca *pca) {
-  if (n > 0 && (!d_out_tsdf || !d_out_max_l || !d_out_mid_p || !h_index)) return TSDF_ERR_INVALID_ARG;
-  if (n_pack < 0 || (n > 0 && n_pack == 0) || n > TSDF_INLINE_INDEX_MAX) return TSDF_ERR_INVALID_ARG;
-  const int chk = pca_entry_args(n, labels, pca);
-  if (chk != TSDF_OK) return chk;
   RunOpts o;
+  o.needs = kNeedPlacement | kNeedHostIndex | kNeedLabels | kNeedPca;
   o.labels = labels;
   o.h_index = h_index;
   o.n_src = n_pack;
   o.pca = pca;
-  return run(d_depth, depth_len, d_offsets, d_headers, n, R, cam, layout, hip_stream, d_out_tsdf, d_out_max_l,
-             d_out_mid_p, d_out_status, o);
+  return run(Frames{d_depth, depth_len, d_offsets, d_headers, n, R, cam, layout, hip_stream},
+             Outs{d_out_tsdf, d_out_max_l, d_out_mid_p, d_out_status}, o);
 }
 
 int tsdf_project_joints_hip(const float *d_gt, const float *d_max_l, const float *d_mid_p, int n, int n_joints,
@@ -230,12 +214,12 @@ int tsdf_cloud_grid_hip(const double *d_points, int n, int points, int R, const 
 int tsdf_debug_pixmap_hip(const float *d_depth, int64_t depth_len, const int64_t *d_offsets, const int32_t *d_headers,
                           int n, int R, const tsdf_cam *cam, int layout, void *hip_stream, const float *d_grid,
                           float *d_out_tsdf, int32_t *d_out_pixmap, int32_t *d_out_status) {
-  if (n > 0 && (!d_out_tsdf || !d_out_pixmap)) return TSDF_ERR_INVALID_ARG;
   RunOpts o;
+  o.needs = kNeedPixmap;   // (a NULL grid: the frame's own placement)
   o.grid_in = d_grid;
   o.pixmap = d_out_pixmap;
-  return run(d_depth, depth_len, d_offsets, d_headers, n, R, cam, layout, hip_stream, d_out_tsdf, nullptr, nullptr,
-             d_out_status, o);
+  return run(Frames{d_depth, depth_len, d_offsets, d_headers, n, R, cam, layout, hip_stream},
+             Outs{d_out_tsdf, nullptr, nullptr, d_out_status}, o);
 }
 #endif
 

@@ -1,5 +1,6 @@
 // launch.inc — part of the one translation unit tsdf_hip.hip (included there, inside its anonymous namespace).
-// Host side of a call: device check, split plan, choice of instantiation, argument marshalling.
+// Host side of a call: the one argument check (tsdf_host.inc), device check, split plan, choice of instantiation,
+// argument marshalling.
 
 const tsdf_cam kDefaultCam = {241.42, 160.0, 120.0, 1.0f, 3.0f};
 
@@ -126,36 +127,23 @@ hipError_t launch_r(hipStream_t s, KArgs &a, int dev) {
   return launch<0, LAYOUT, AUG, false, PCA>(s, a, dev);
 }
 
-struct RunOpts {
-  float *aabb = nullptr, *grid = nullptr, *ori = nullptr;
-  int aabb_only = 0;
-  const float *grid_in = nullptr;
-  const double *xforms = nullptr;
-  const tsdf_labels *labels = nullptr;
-  int32_t *pixmap = nullptr;
-  const int64_t *index = nullptr;  // indexed entry
-  int64_t n_src = 0;
-  const int64_t *h_index = nullptr;  // indexed entry, index in HOST memory, copied into the kernel arguments
-  const tsdf_pca *pca = nullptr;     // joint PCA projection fused into the labels (requires labels)
-};
+using namespace tsdf_host;   // Frames, Outs, RunOpts and the kNeed* bits
 
-int run(const float *d_depth, int64_t depth_len, const int64_t *d_offsets, const int32_t *d_headers, int n, int R,
-        const tsdf_cam *cam, int layout, void *hip_stream, float *t, float *ml, float *mp, int32_t *st,
-        const RunOpts &o) {
-  // (argument checks: tsdf_host.inc, shared with the sanitizer build of the host code)
-  const int chk = tsdf_host::check_run_args(d_depth, depth_len, d_offsets, d_headers, n, R, cam, layout, t, o.aabb_only,
-                                            o.labels, tsdf_resolution_supported(R));
-  if (chk == tsdf_host::kNothingToDo) return TSDF_OK;
+int run(const Frames &f, const Outs &out, const RunOpts &o) {
+  // (every argument check: tsdf_host.inc, shared with the sanitizer build of the host code)
+  const int chk = check_run_args(f, out, o, tsdf_resolution_supported(f.R));
+  if (chk == kNothingToDo) return TSDF_OK;
   if (chk != TSDF_OK) return chk;
-  if (!cam) cam = &kDefaultCam;
+  const int n = f.n, R = f.R, layout = f.layout;
+  const tsdf_cam *cam = f.cam ? f.cam : &kDefaultCam;
   int dev = 0;
   int rc = check_device(&dev);
   if (rc != TSDF_OK) return rc;
   KArgs a;
   memset(&a, 0, sizeof a);
-  a.depth = d_depth;
-  a.offsets = d_offsets;
-  a.headers = d_headers;
+  a.depth = f.depth;
+  a.offsets = f.offsets;
+  a.headers = f.headers;
   a.n = n;
   a.R = R;
   a.cam.focal = cam->focal;
@@ -164,21 +152,20 @@ int run(const float *d_depth, int64_t depth_len, const int64_t *d_offsets, const
   a.cam.inv_focal = 1.0 / cam->focal;
   a.cam.eps = cam->invalid_eps;
   a.cam.trunc_vox = cam->trunc_voxels;
-  a.tsdf = t;
-  a.max_l = ml;
-  a.mid_p = mp;
-  a.status = st;
+  a.tsdf = out.tsdf;
+  a.max_l = out.max_l;
+  a.mid_p = out.mid_p;
+  a.status = out.status;
   a.aabb = o.aabb;
   a.grid = o.grid;
   a.ori = o.ori;
   a.aabb_only = o.aabb_only;
   a.grid_in = o.grid_in;
   a.xforms = o.xforms;
-  a.depth_len = depth_len;
+  a.depth_len = f.depth_len;
   a.index = o.index;
   a.n_src = o.n_src;
-  if (o.h_index) {
-    if (n > TSDF_INLINE_INDEX_MAX) return TSDF_ERR_INVALID_ARG;
+  if (o.needs & kNeedHostIndex) {   // (checked: h_index is there and n <= TSDF_INLINE_INDEX_MAX)
     a.n_inline = n;
     memcpy(a.inline_index, o.h_index, sizeof(int64_t) * (size_t)n);
   }
@@ -196,7 +183,7 @@ int run(const float *d_depth, int64_t depth_len, const int64_t *d_offsets, const
     a.pca_k = o.pca->n_components;
   }
   a.pixmap = o.pixmap;
-  hipStream_t s = static_cast<hipStream_t>(hip_stream);
+  hipStream_t s = static_cast<hipStream_t>(f.stream);
   hipError_t e;
   if (o.pixmap) {
 #ifdef TSDF_DEBUG_HOOKS   // the diagnostic instantiations (DBG) exist in the debug build only

@@ -9,7 +9,10 @@
 // Contents:
 //   tsdf_host::gather()          frames of a packed host buffer copied back to back by a few threads
 //                                (tsdf_host_gather_frames / _n of include/tsdf.h)
-//   tsdf_host::check_run_args()  the argument validation every voxelizer entry starts with
+//   tsdf_host::Frames / Outs / RunOpts   one call of a voxelizer entry, as abi.inc hands it to run()
+//   tsdf_host::check_run_args()  ALL argument validation of the voxelizer entries, driven by RunOpts::needs; run() calls
+//                                it once, the entries themselves check nothing
+//   tsdf_host::check_pca()       the joint-PCA descriptor
 //   tsdf_host::SlotTable         (stream, thread) -> slot of the per-stream device words, under its own mutex, with the
 //                                launch counter that tags a stream's work-queue word
 #pragma once
@@ -75,25 +78,50 @@ inline int gather(const float *src, int64_t src_len, const int64_t *src_offsets,
   return TSDF_OK;
 }
 
-// ---- what every voxelizer entry checks before it looks at the device ----------------------------------------------
-// TSDF_OK: go on (n > 0);  1: nothing to do (n == 0, after the checks that do not need data);  < 0: the error.
-constexpr int kNothingToDo = 1;
-inline int check_run_args(const void *d_depth, int64_t depth_len, const void *d_offsets, const void *d_headers, int n, int /*R*/,
-                          const tsdf_cam *cam, int layout, const void *out_tsdf, int aabb_only, const tsdf_labels *labels,
-                          int resolution_supported) {
-  if (n < 0 || !resolution_supported) return TSDF_ERR_INVALID_ARG;
-  if (layout != TSDF_LAYOUT_CZYX && layout != TSDF_LAYOUT_CXYZ) return TSDF_ERR_INVALID_ARG;
-  if (labels) {
-    if (labels->n_joints < 1 || labels->n_joints > 170) return TSDF_ERR_INVALID_ARG;
-    if (n > 0 && (!labels->d_gt || !labels->d_out_gt_nor)) return TSDF_ERR_INVALID_ARG;
-  }
-  if (n == 0) return kNothingToDo;
-  if (!d_depth || !d_offsets || !d_headers || depth_len < 0) return TSDF_ERR_INVALID_ARG;
-  if (!aabb_only && (!out_tsdf || (reinterpret_cast<uintptr_t>(out_tsdf) & 15))) return TSDF_ERR_INVALID_ARG;
-  if (cam && (!(cam->focal > 0.0) || !(cam->invalid_eps > 0.0f) || !(cam->trunc_voxels > 0.0f)))
-    return TSDF_ERR_INVALID_ARG;  // (written so that NaN fails)
-  return TSDF_OK;
-}
+// ---- one call of a voxelizer entry: the packed frames, the outputs, and what the entry adds ----------------------------
+// Every extern "C" voxelizer entry (abi.inc) fills these three and hands them to run() (launch.inc), which calls
+// check_run_args() once.  They live here so that the sanitizer build compiles the check with the structs it reads.
+struct Frames {
+  const float *depth;
+  int64_t depth_len;
+  const int64_t *offsets;
+  const int32_t *headers;
+  int n, R;
+  const tsdf_cam *cam;
+  int layout;
+  void *stream;
+};
+
+struct Outs {
+  float *tsdf, *max_l, *mid_p;
+  int32_t *status;
+};
+
+// what an entry requires when n > 0 (RunOpts::needs)
+enum : unsigned {
+  kNeedPlacement = 1u << 0,  // max_l and mid_p
+  kNeedIndex = 1u << 1,      // index, in device memory; n_src frames in the pack
+  kNeedHostIndex = 1u << 2,  // h_index, in host memory, at most TSDF_INLINE_INDEX_MAX entries; n_src frames in the pack
+  kNeedXforms = 1u << 3,
+  kNeedLabels = 1u << 4,     // (also when n == 0)
+  kNeedPca = 1u << 5,        // (also when n == 0; implies labels)
+  kNeedGridIn = 1u << 6,
+  kNeedPixmap = 1u << 7,
+};
+
+struct RunOpts {
+  unsigned needs = 0;
+  float *aabb = nullptr, *grid = nullptr, *ori = nullptr;
+  int aabb_only = 0;
+  const float *grid_in = nullptr;
+  const double *xforms = nullptr;
+  const tsdf_labels *labels = nullptr;
+  int32_t *pixmap = nullptr;
+  const int64_t *index = nullptr;  // indexed entry
+  int64_t n_src = 0;
+  const int64_t *h_index = nullptr;  // indexed entry, index in HOST memory, copied into the kernel arguments
+  const tsdf_pca *pca = nullptr;     // joint PCA projection fused into the labels (requires labels)
+};
 
 // ---- the joint-PCA descriptor (include/tsdf.h, tsdf_pca) for n frames of n_joints joints ------------------------------
 // need_out: the entry writes d_out_gt_pca (every entry but tsdf_pose_error_hip).
@@ -101,6 +129,38 @@ inline int check_pca(const tsdf_pca *pca, int n, int n_joints, bool need_out) {
   if (!pca || n_joints < 1 || n_joints > 170) return TSDF_ERR_INVALID_ARG;
   if (pca->n_components < 1 || pca->n_components > 3 * n_joints) return TSDF_ERR_INVALID_ARG;
   if (n > 0 && (!pca->d_mean || !pca->d_coeff || (need_out && !pca->d_out_gt_pca))) return TSDF_ERR_INVALID_ARG;
+  return TSDF_OK;
+}
+
+// ---- what every voxelizer entry checks before it looks at the device ----------------------------------------------
+// TSDF_OK: go on (n > 0);  1: nothing to do (n == 0, after the checks that do not need data);  < 0: the error.
+constexpr int kNothingToDo = 1;
+inline int check_run_args(const Frames &f, const Outs &out, const RunOpts &o, int resolution_supported) {
+  const int n = f.n;
+  // -- what holds for an empty batch too: sizes, descriptors, alignment
+  if (n < 0 || !resolution_supported) return TSDF_ERR_INVALID_ARG;
+  if (f.layout != TSDF_LAYOUT_CZYX && f.layout != TSDF_LAYOUT_CXYZ) return TSDF_ERR_INVALID_ARG;
+  if ((o.needs & (kNeedLabels | kNeedPca)) && !o.labels) return TSDF_ERR_INVALID_ARG;
+  if (o.labels) {
+    if (o.labels->n_joints < 1 || o.labels->n_joints > 170) return TSDF_ERR_INVALID_ARG;
+    if (n > 0 && (!o.labels->d_gt || !o.labels->d_out_gt_nor)) return TSDF_ERR_INVALID_ARG;
+  }
+  if ((o.needs & kNeedPca) && check_pca(o.pca, n, o.labels->n_joints, true) != TSDF_OK) return TSDF_ERR_INVALID_ARG;
+  if (reinterpret_cast<uintptr_t>(o.xforms) & 7) return TSDF_ERR_INVALID_ARG;
+  if ((o.needs & (kNeedIndex | kNeedHostIndex)) && (o.n_src < 0 || (n > 0 && o.n_src == 0))) return TSDF_ERR_INVALID_ARG;
+  if ((o.needs & kNeedHostIndex) && n > TSDF_INLINE_INDEX_MAX) return TSDF_ERR_INVALID_ARG;
+  if (n == 0) return kNothingToDo;
+  // -- n > 0: everything the launch reads or writes
+  if ((o.needs & kNeedPlacement) && (!out.max_l || !out.mid_p)) return TSDF_ERR_INVALID_ARG;
+  if ((o.needs & kNeedIndex) && !o.index) return TSDF_ERR_INVALID_ARG;
+  if ((o.needs & kNeedHostIndex) && !o.h_index) return TSDF_ERR_INVALID_ARG;
+  if ((o.needs & kNeedXforms) && !o.xforms) return TSDF_ERR_INVALID_ARG;
+  if ((o.needs & kNeedGridIn) && !o.grid_in) return TSDF_ERR_INVALID_ARG;
+  if ((o.needs & kNeedPixmap) && !o.pixmap) return TSDF_ERR_INVALID_ARG;
+  if (!f.depth || !f.offsets || !f.headers || f.depth_len < 0) return TSDF_ERR_INVALID_ARG;
+  if (!o.aabb_only && (!out.tsdf || (reinterpret_cast<uintptr_t>(out.tsdf) & 15))) return TSDF_ERR_INVALID_ARG;
+  if (f.cam && (!(f.cam->focal > 0.0) || !(f.cam->invalid_eps > 0.0f) || !(f.cam->trunc_voxels > 0.0f)))
+    return TSDF_ERR_INVALID_ARG;  // (written so that NaN fails)
   return TSDF_OK;
 }
 

@@ -14,12 +14,35 @@ tsdf_host::SlotTable<64> g_table;   // (a small table: "full" is reachable in a 
 
 extern "C" {
 
-// tsdf_host::check_run_args with the product's defaults for what the hook does not take
-int tsdf_test_check_run_args(const void *d_depth, int64_t depth_len, const void *d_offsets, const void *d_headers, int n, int R,
-                             const tsdf_cam *cam, int layout, const void *out_tsdf, int aabb_only, const tsdf_labels *labels) {
+// tsdf_host::check_run_args — the one check behind every voxelizer entry — on the structs an entry would build: `needs`
+// are the kNeed* bits, the arguments after it what the entry puts into Outs / RunOpts
+int tsdf_test_check_entry_args(const void *d_depth, int64_t depth_len, const void *d_offsets, const void *d_headers, int n, int R,
+                               const tsdf_cam *cam, int layout, void *out_tsdf, int aabb_only, const tsdf_labels *labels,
+                               unsigned needs, void *max_l, void *mid_p, const void *index, const void *h_index, int64_t n_pack,
+                               const void *xforms, const tsdf_pca *pca, const void *grid_in, void *pixmap) {
   const int supported = R >= 4 && R <= 128 && (R % 4) == 0;
-  return tsdf_host::check_run_args(d_depth, depth_len, d_offsets, d_headers, n, R, cam, layout, out_tsdf, aabb_only, labels,
-                                   supported);
+  const tsdf_host::Frames f{static_cast<const float *>(d_depth), depth_len, static_cast<const int64_t *>(d_offsets),
+                            static_cast<const int32_t *>(d_headers), n, R, cam, layout, nullptr};
+  const tsdf_host::Outs out{static_cast<float *>(out_tsdf), static_cast<float *>(max_l), static_cast<float *>(mid_p), nullptr};
+  tsdf_host::RunOpts o;
+  o.needs = needs;
+  o.aabb_only = aabb_only;
+  o.labels = labels;
+  o.index = static_cast<const int64_t *>(index);
+  o.h_index = static_cast<const int64_t *>(h_index);
+  o.n_src = n_pack;
+  o.xforms = static_cast<const double *>(xforms);
+  o.pca = pca;
+  o.grid_in = static_cast<const float *>(grid_in);
+  o.pixmap = static_cast<int32_t *>(pixmap);
+  return tsdf_host::check_run_args(f, out, o, supported);
+}
+
+// the same check for an entry that requires nothing beyond the pack (the argument list this hook has always had)
+int tsdf_test_check_run_args(const void *d_depth, int64_t depth_len, const void *d_offsets, const void *d_headers, int n, int R,
+                             const tsdf_cam *cam, int layout, void *out_tsdf, int aabb_only, const tsdf_labels *labels) {
+  return tsdf_test_check_entry_args(d_depth, depth_len, d_offsets, d_headers, n, R, cam, layout, out_tsdf, aabb_only, labels, 0,
+                                    nullptr, nullptr, nullptr, nullptr, 0, nullptr, nullptr, nullptr, nullptr);
 }
 
 int tsdf_test_slot_acquire(uintptr_t stream, int per_thread) {

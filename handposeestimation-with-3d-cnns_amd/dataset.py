@@ -36,7 +36,7 @@ import torch
 import torch.utils.data as data
 
 from . import packing, shard
-from .voxelize import (TsdfBatch, denormalize_joints, normalize_joints, voxelize, voxelize_indexed,  # noqa: F401
+from .voxelize import (TsdfBatch, denormalize_joints, empty_batch, normalize_joints, voxelize, voxelize_indexed,  # noqa: F401
                        voxelize_labels)
 
 
@@ -564,10 +564,7 @@ class ResidentLoader:
         lab_shape = (cap,) + tuple(gt.shape[1:])
         blocks = []
         for _ in range(self.ring):
-            out = TsdfBatch(torch.empty((cap, 3, R, R, R), dtype=torch.float32, device=self.device),
-                            torch.empty((cap,), dtype=torch.float32, device=self.device),
-                            torch.empty((cap, 3), dtype=torch.float32, device=self.device),
-                            torch.empty((cap,), dtype=torch.int32, device=self.device))
+            out = empty_batch(cap, R, self.device)
             gt_nor = torch.empty(lab_shape, dtype=torch.float32, device=self.device)
             g = torch.empty(lab_shape, dtype=torch.float32, device=self.device)
             views = [self._view(out, gt_nor, g, j * self.bs, (j + 1) * self.bs) for j in range(self.prefetch)]

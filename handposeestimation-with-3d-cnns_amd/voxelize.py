@@ -73,8 +73,8 @@ def _dev_check(name, t, dtype, device=None, host_ok=False):
         raise ValueError(f"{name} is on {t.device}, expected {device}")
 
 
-def _check_inputs(L, depth, offsets, headers, res, layout):
-    """Shared validation of the packed-frame inputs; returns (device, n, R)."""
+def _pack(L, depth, offsets, headers, res=None, layout="czyx"):
+    """The one validation of a packed-frame triple; returns (device, n, R) — R is None without ``res``."""
     if layout not in _lib.LAYOUTS:
         raise ValueError("layout must be 'czyx' or 'cxyz'")
     _dev_check("depth", depth, torch.float32)
@@ -86,21 +86,50 @@ def _check_inputs(L, depth, offsets, headers, res, layout):
     n = headers.shape[0]
     if offsets.numel() != n + 1:
         raise ValueError("offsets must have n+1 entries")
+    if res is None:
+        return dev, n, None
     if not L.tsdf_resolution_supported(int(res)):
         raise ValueError(f"unsupported grid resolution {res} (multiple of 4 in 4..128)")
     return dev, n, int(res)
 
 
+def _coords(name, t, rows) -> int:
+    """``t`` holds ``rows`` frames of 3*J float32 coordinates, 1 <= J <= 170, as [rows, 3J] or [rows, J, 3] (any trailing
+    shape with 3*J elements): returns 3*J — or 0 for ``rows == 0``, where there is nothing to count and the caller has
+    its own default."""
+    if t.shape[0] != rows:
+        raise ValueError(f"{name} must have shape [{rows}, 3*J] or [{rows}, J, 3]")
+    nc = t.numel() // rows if rows else 0
+    if rows and (nc % 3 or not 1 <= nc // 3 <= 170):
+        raise ValueError(f"{name} must hold 1..170 joints of 3 coordinates per frame")
+    return nc
+
+
+def _shaped(name, t, shape, dtype, dev):
+    """A caller's tensor whose data pointer goes straight to the kernel: device, dtype, contiguity, shape.  A per-frame
+    vector (``shape`` [n]) is checked by its element count only, as it always was: [n, 1] passes."""
+    _dev_check(name, t, dtype, dev)
+    if tuple(t.shape) != shape and (len(shape) != 1 or t.numel() != shape[0]):
+        raise ValueError(f"{name} must have shape {shape}")
+    return t
+
+
+def _out(name, t, shape, dtype, dev):
+    """An output: allocated when ``t`` is None, else the caller's, validated."""
+    return torch.empty(shape, dtype=dtype, device=dev) if t is None else _shaped(name, t, shape, dtype, dev)
+
+
+def empty_batch(n: int, R: int, dev) -> TsdfBatch:
+    """Uninitialised outputs of n frames at resolution R on ``dev`` (what ``out=`` of the voxelizers takes)."""
+    return TsdfBatch(_out("tsdf", None, (n, 3, R, R, R), torch.float32, dev), _out("max_l", None, (n,), torch.float32, dev),
+                     _out("mid_p", None, (n, 3), torch.float32, dev), _out("status", None, (n,), torch.int32, dev))
+
+
 def _make_out(out, n, R, dev) -> "TsdfBatch":
-    """Allocate the outputs, or validate caller-supplied ones (device, dtype, contiguity, shape): their
-    data pointers go straight to the kernel."""
+    """Allocate the outputs, or validate caller-supplied ones.  (The latter is every step of a loader that reuses its
+    buffers: what _shaped would do per field is written out, four calls and one expression.)"""
     if out is None:
-        return TsdfBatch(
-            torch.empty((n, 3, R, R, R), dtype=torch.float32, device=dev),
-            torch.empty((n,), dtype=torch.float32, device=dev),
-            torch.empty((n, 3), dtype=torch.float32, device=dev),
-            torch.empty((n,), dtype=torch.int32, device=dev),
-        )
+        return empty_batch(n, R, dev)
     _dev_check("out.tsdf", out.tsdf, torch.float32, dev)
     _dev_check("out.max_l", out.max_l, torch.float32, dev)
     _dev_check("out.mid_p", out.mid_p, torch.float32, dev)
@@ -111,24 +140,39 @@ def _make_out(out, n, R, dev) -> "TsdfBatch":
     return out
 
 
-def _labels_struct(gt, n, dev, clamp, out_gt_nor=None, want_aug=False):
-    """Validate the label tensors and build the ``tsdf_labels`` struct (kept alive by the caller)."""
+def _cam(cam):
+    return ctypes.byref(cam) if cam is not None else None
+
+
+def _ptr(t):
+    return t.data_ptr() if t is not None else None
+
+
+def _head(depth, offsets, headers, n, R, cam, layout) -> list:
+    """The nine arguments every packed-frame entry starts with; the stream (position 8) is filled in by _call."""
+    return [depth.data_ptr(), depth.numel(), offsets.data_ptr(), headers.data_ptr(), n, R, _cam(cam), _lib.LAYOUTS[layout],
+            None]
+
+
+def _call(dev, fn, args: list, stream_at: int) -> None:
+    """The one place an entry is called: ``dev`` is made current, ``args[stream_at]`` becomes the raw handle of ITS current
+    stream (read while it is current), and a failure is reported under the name of the entry that failed."""
+    with _Current(dev):
+        args[stream_at] = _raw_stream(dev)
+        rc = fn(*args)
+    _lib.check(rc, fn.__name__)
+
+
+def _labels_struct(gt, n_src, n, dev, clamp, out_gt_nor=None, out_gt=None, want_gt=False):
+    """Validate the label tensors and build the ``tsdf_labels`` struct (kept alive by the caller): ``gt`` holds the labels
+    of ``n_src`` frames, the outputs those of the ``n`` frames of the batch (the same frames unless the entry is indexed).
+    Returns (struct, gt_nor, gt written by the launch or None)."""
     _dev_check("gt", gt, torch.float32, dev, host_ok=True)
-    if gt.shape[0] != n or gt.numel() % (3 * max(n, 1)) != 0 and n > 0:
-        raise ValueError("gt must have shape [n, 3*J] or [n, J, 3]")
-    nc = gt.numel() // n if n else 63
-    if nc % 3 or not 1 <= nc // 3 <= 170:
-        raise ValueError("gt must hold 1..170 joints of 3 coordinates per frame")
-    if out_gt_nor is None:
-        out_gt_nor = torch.empty(gt.shape, dtype=torch.float32, device=dev)
-    else:
-        _dev_check("out_gt_nor", out_gt_nor, torch.float32, dev)
-        if out_gt_nor.shape != gt.shape:
-            raise ValueError("out_gt_nor must have gt's shape")
-    gt_aug = torch.empty(gt.shape, dtype=torch.float32, device=dev) if want_aug else None
-    lab = _lib.TsdfLabels(gt.data_ptr(), nc // 3, 1 if clamp else 0, out_gt_nor.data_ptr(),
-                          gt_aug.data_ptr() if gt_aug is not None else None)
-    return lab, out_gt_nor, gt_aug
+    nc = _coords("gt", gt, n_src) or 63
+    shape = (n,) + tuple(gt.shape[1:])
+    gt_nor = _out("out_gt_nor", out_gt_nor, shape, torch.float32, dev)
+    gt_dev = _out("out_gt", out_gt, shape, torch.float32, dev) if want_gt or out_gt is not None else None
+    return _lib.TsdfLabels(gt.data_ptr(), nc // 3, 1 if clamp else 0, gt_nor.data_ptr(), _ptr(gt_dev)), gt_nor, gt_dev
 
 
 def voxelize(depth: torch.Tensor, offsets: torch.Tensor, headers: torch.Tensor, res: int = 32,
@@ -146,17 +190,11 @@ def voxelize(depth: torch.Tensor, offsets: torch.Tensor, headers: torch.Tensor, 
     Enqueues on ``torch.cuda.current_stream()`` and returns without synchronising.
     """
     L = _lib.load()
-    dev, n, R = _check_inputs(L, depth, offsets, headers, res, layout)
+    dev, n, R = _pack(L, depth, offsets, headers, res, layout)
     out = _make_out(out, n, R, dev)
-    if n == 0:
-        return out
-    with _Current(dev):
-        stream = _raw_stream(dev)
-        rc = L.tsdf_voxelize_hip(depth.data_ptr(), depth.numel(), offsets.data_ptr(), headers.data_ptr(), n, R,
-                                 ctypes.byref(cam) if cam is not None else None,
-                                 _lib.LAYOUTS[layout], stream, out.tsdf.data_ptr(),
-                                 out.max_l.data_ptr(), out.mid_p.data_ptr(), out.status.data_ptr())
-    _lib.check(rc, "tsdf_voxelize_hip")
+    if n:
+        _call(dev, L.tsdf_voxelize_hip, _head(depth, offsets, headers, n, R, cam, layout) +
+              [out.tsdf.data_ptr(), out.max_l.data_ptr(), out.mid_p.data_ptr(), out.status.data_ptr()], 8)
     return out
 
 
@@ -177,26 +215,20 @@ def voxelize_labels(depth: torch.Tensor, offsets: torch.Tensor, headers: torch.T
     unclamped labels to the same launch (``tsdf_voxelize_labels_pca_hip``): ``gt_pca`` float32[n, k] is appended to the
     returned tuple."""
     L = _lib.load()
-    dev, n, R = _check_inputs(L, depth, offsets, headers, res, layout)
+    dev, n, R = _pack(L, depth, offsets, headers, res, layout)
     out = _make_out(out, n, R, dev)
-    lab, gt_nor, gt_dev = _labels_struct(gt, n, dev, clamp, out_gt_nor, want_aug=gt_copy)
+    lab, gt_nor, gt_dev = _labels_struct(gt, n, n, dev, clamp, out_gt_nor, want_gt=gt_copy)
     pst = gt_pca = None
     if pca is not None:
         pst, gt_pca = _pca_struct(pca, k, n, lab.n_joints, dev)
-    res_t = ((out, gt_nor, gt_dev) if gt_copy else (out, gt_nor)) + ((gt_pca,) if pca is not None else ())
-    if n == 0:
-        return res_t
-    with _Current(dev):
-        stream = _raw_stream(dev)
-        head = (depth.data_ptr(), depth.numel(), offsets.data_ptr(), headers.data_ptr(), n, R,
-                ctypes.byref(cam) if cam is not None else None, _lib.LAYOUTS[layout], stream)
-        tail = (out.tsdf.data_ptr(), out.max_l.data_ptr(), out.mid_p.data_ptr(), out.status.data_ptr(), ctypes.byref(lab))
+    if n:
+        head = _head(depth, offsets, headers, n, R, cam, layout)
+        tail = [out.tsdf.data_ptr(), out.max_l.data_ptr(), out.mid_p.data_ptr(), out.status.data_ptr(), ctypes.byref(lab)]
         if pst is None:
-            rc = L.tsdf_voxelize_labels_hip(*head, *tail)
+            _call(dev, L.tsdf_voxelize_labels_hip, head + tail, 8)
         else:
-            rc = L.tsdf_voxelize_labels_pca_hip(*head, None, *tail, ctypes.byref(pst))
-    _lib.check(rc, "tsdf_voxelize_labels_hip")
-    return res_t
+            _call(dev, L.tsdf_voxelize_labels_pca_hip, head + [None] + tail + [ctypes.byref(pst)], 8)
+    return ((out, gt_nor, gt_dev) if gt_copy else (out, gt_nor)) + ((gt_pca,) if pca is not None else ())
 
 
 def voxelize_indexed(depth: torch.Tensor, offsets: torch.Tensor, headers: torch.Tensor, index: torch.Tensor,
@@ -226,7 +258,7 @@ def voxelize_indexed(depth: torch.Tensor, offsets: torch.Tensor, headers: torch.
         _dev_check("index", index, torch.int64, depth.device if isinstance(depth, torch.Tensor) else None, host_ok=True)
     if index.dim() != 1:
         raise ValueError("index must have shape [n]")
-    dev, n_pack, R = _check_inputs(L, depth, offsets, headers, res, layout)
+    dev, n_pack, R = _pack(L, depth, offsets, headers, res, layout)
     n = index.numel()
     out = _make_out(out, n, R, dev)
     lab = gt_nor = gt_dev = None
@@ -236,46 +268,32 @@ def voxelize_indexed(depth: torch.Tensor, offsets: torch.Tensor, headers: torch.
             raise ValueError("xforms must have shape [n, 24] (forward rows then inverse rows)")
     if gt is not None:
         _dev_check("gt", gt, torch.float32, dev, host_ok=True)
-        if gt.dim() < 2 or gt.shape[0] != n_pack:
+        # (the labels of a PACK are at least 2-D even when the pack is empty; every other site takes what _coords takes)
+        if gt.dim() < 2:
             raise ValueError("gt must hold the labels of every frame of the pack: [N, 3*J] or [N, J, 3]")
-        nc = gt.numel() // n_pack if n_pack else 63
-        if nc % 3 or not 1 <= nc // 3 <= 170:
-            raise ValueError("gt must hold 1..170 joints of 3 coordinates per frame")
-        shape = (n,) + tuple(gt.shape[1:])
-        for name, t in (("out_gt_nor", out_gt_nor), ("out_gt", out_gt)):
-            if t is not None:
-                _dev_check(name, t, torch.float32, dev)
-                if tuple(t.shape) != shape:
-                    raise ValueError(f"{name} must have shape {shape}")
-        gt_nor = out_gt_nor if out_gt_nor is not None else torch.empty(shape, dtype=torch.float32, device=dev)
-        gt_copy = gt_copy or out_gt is not None
-        gt_dev = out_gt if out_gt is not None else (torch.empty_like(gt_nor) if gt_copy else None)
-        lab = _lib.TsdfLabels(gt.data_ptr(), nc // 3, 1 if clamp else 0, gt_nor.data_ptr(),
-                              gt_dev.data_ptr() if gt_dev is not None else None)
+        lab, gt_nor, gt_dev = _labels_struct(gt, n_pack, n, dev, clamp, out_gt_nor, out_gt, want_gt=gt_copy)
+        gt_copy = gt_dev is not None
     pst = gt_pca = None
     if pca is not None:
         if gt is None:
             raise ValueError("pca= needs gt (the projection is of the batch's labels)")
         pst, gt_pca = _pca_struct(pca, k, n, lab.n_joints, dev)
     if n:
-        with _Current(dev):
-            head = (depth.data_ptr(), depth.numel(), offsets.data_ptr(), headers.data_ptr(), n_pack, index.data_ptr(), n, R,
-                    ctypes.byref(cam) if cam is not None else None, _lib.LAYOUTS[layout], _raw_stream(dev))
-            tail = (out.tsdf.data_ptr(), out.max_l.data_ptr(), out.mid_p.data_ptr(), out.status.data_ptr(),
-                    ctypes.byref(lab) if lab is not None else None)
-            if pst is not None:
-                if by_value:
-                    rc = L.tsdf_voxelize_indexed_host_pca_hip(*head, *tail, ctypes.byref(pst))
-                else:
-                    rc = L.tsdf_voxelize_indexed_pca_hip(*head, xforms.data_ptr() if xforms is not None else None, *tail,
-                                                         ctypes.byref(pst))
-            elif by_value:
-                rc = L.tsdf_voxelize_indexed_host_hip(*head, *tail)
-            elif xforms is None:
-                rc = L.tsdf_voxelize_indexed_hip(*head, *tail)
+        head = _head(depth, offsets, headers, n, R, cam, layout)
+        head[4:5] = [n_pack, index.data_ptr(), n]   # the indexed entries' prefix: the stream is at position 10
+        tail = [out.tsdf.data_ptr(), out.max_l.data_ptr(), out.mid_p.data_ptr(), out.status.data_ptr(),
+                ctypes.byref(lab) if lab is not None else None]
+        if pst is not None:
+            if by_value:
+                _call(dev, L.tsdf_voxelize_indexed_host_pca_hip, head + tail + [ctypes.byref(pst)], 10)
             else:
-                rc = L.tsdf_voxelize_indexed_aug_hip(*head, xforms.data_ptr(), *tail)
-        _lib.check(rc, "tsdf_voxelize_indexed_hip")
+                _call(dev, L.tsdf_voxelize_indexed_pca_hip, head + [_ptr(xforms)] + tail + [ctypes.byref(pst)], 10)
+        elif by_value:
+            _call(dev, L.tsdf_voxelize_indexed_host_hip, head + tail, 10)
+        elif xforms is None:
+            _call(dev, L.tsdf_voxelize_indexed_hip, head + tail, 10)
+        else:
+            _call(dev, L.tsdf_voxelize_indexed_aug_hip, head + [xforms.data_ptr()] + tail, 10)
     if gt is None:
         return out
     return ((out, gt_nor, gt_dev) if gt_copy else (out, gt_nor)) + ((gt_pca,) if pca is not None else ())
@@ -288,13 +306,19 @@ def _pca_struct(pca, k, n, n_joints, dev, out=None):
     if pca.n_coords != 3 * n_joints:
         raise ValueError(f"the PCA basis is for {pca.n_coords} coordinates, the labels have {3 * n_joints}")
     mean, coeff = pca.device_tensors(dev)
-    if out is None:
-        out = torch.empty((n, k), dtype=torch.float32, device=dev)
-    else:
-        _dev_check("out", out, torch.float32, dev)
-        if tuple(out.shape) != (n, k):
-            raise ValueError(f"out must have shape {(n, k)}")
+    out = _out("out", out, (n, k), torch.float32, dev)
     return _lib.TsdfPca(mean.data_ptr(), coeff.data_ptr(), k, out.data_ptr()), out
+
+
+def _frames(name, x, max_l, mid_p):
+    """``x`` float32[n, ...] on the GPU with the placement of its n frames: returns (device, n)."""
+    _dev_check(name, x, torch.float32)
+    dev, n = x.device, x.shape[0]
+    _dev_check("max_l", max_l, torch.float32, dev)
+    _dev_check("mid_p", mid_p, torch.float32, dev)
+    if max_l.numel() != n or tuple(mid_p.shape) != (n, 3):
+        raise ValueError("max_l must be [n] and mid_p [n,3]")
+    return dev, n
 
 
 def project_joints(gt: torch.Tensor, max_l: torch.Tensor, mid_p: torch.Tensor, pca, k: Optional[int] = None,
@@ -303,22 +327,12 @@ def project_joints(gt: torch.Tensor, max_l: torch.Tensor, mid_p: torch.Tensor, p
     with ``max_l`` / ``mid_p`` (no clamp; ``max_l == 0`` gives 0.5) and projected on the first ``k`` components of
     ``pca`` — bit-identical to the ``gt_pca`` the fused voxelizer entries write.  gt [n, 3J] or [n, J, 3] -> [n, k]."""
     L = _lib.load()
-    _dev_check("gt", gt, torch.float32)
-    dev = gt.device
-    n = gt.shape[0]
-    _dev_check("max_l", max_l, torch.float32, dev)
-    _dev_check("mid_p", mid_p, torch.float32, dev)
-    if max_l.numel() != n or tuple(mid_p.shape) != (n, 3):
-        raise ValueError("max_l must be [n] and mid_p [n,3]")
-    nc = gt.numel() // n if n else pca.n_coords
-    if n and (gt.numel() != n * nc or nc % 3 or not 1 <= nc // 3 <= 170):
-        raise ValueError("gt must have shape [n, 3*J] or [n, J, 3]")
+    dev, n = _frames("gt", gt, max_l, mid_p)
+    nc = _coords("gt", gt, n) or pca.n_coords
     pst, out = _pca_struct(pca, k, n, nc // 3, dev, out)
     if n:
-        with _Current(dev):
-            rc = L.tsdf_project_joints_hip(gt.data_ptr(), max_l.data_ptr(), mid_p.data_ptr(), n, nc // 3,
-                                           ctypes.byref(pst), _raw_stream(dev))
-        _lib.check(rc, "tsdf_project_joints_hip")
+        _call(dev, L.tsdf_project_joints_hip, [gt.data_ptr(), max_l.data_ptr(), mid_p.data_ptr(), n, nc // 3,
+                                               ctypes.byref(pst), None], 6)
     return out
 
 
@@ -347,9 +361,7 @@ def pose_error(pred: torch.Tensor, gt: torch.Tensor, max_l: torch.Tensor, mid_p:
     _dev_check("mid_p", mid_p, torch.float32, dev)
     if gt.shape[0] != n or max_l.numel() != n or tuple(mid_p.shape) != (n, 3):
         raise ValueError("pred, gt, max_l [n] and mid_p [n,3] must describe the same n frames")
-    nc = gt.numel() // n if n else (pca.n_coords if pca is not None else 63)
-    if n and (gt.numel() != n * nc or nc % 3 or not 1 <= nc // 3 <= 170):
-        raise ValueError("gt must have shape [n, 3*J] or [n, J, 3]")
+    nc = _coords("gt", gt, n) or (pca.n_coords if pca is not None else 63)
     nj = nc // 3
     pst = None
     if pca is not None:
@@ -362,17 +374,15 @@ def pose_error(pred: torch.Tensor, gt: torch.Tensor, max_l: torch.Tensor, mid_p:
         pst = _lib.TsdfPca(mean.data_ptr(), coeff.data_ptr(), k, None)
     elif pred.numel() != n * nc:
         raise ValueError("pred must hold 3*J normalised coordinates per frame (or pass pca=)")
-    err = torch.empty((n, nj), dtype=torch.float32, device=dev)
-    fmean = torch.empty(n, dtype=torch.float32, device=dev)
-    fmax = torch.empty(n, dtype=torch.float32, device=dev)
-    jt = torch.empty((n, nc), dtype=torch.float32, device=dev) if joints else None
+    res = PoseError(_out("err", None, (n, nj), torch.float32, dev), _out("frame_mean", None, (n,), torch.float32, dev),
+                    _out("frame_max", None, (n,), torch.float32, dev),
+                    _out("joints", None, (n, nc), torch.float32, dev) if joints else None)
     if n:
-        with _Current(dev):
-            rc = L.tsdf_pose_error_hip(pred.data_ptr(), ctypes.byref(pst) if pst is not None else None, max_l.data_ptr(),
-                                       mid_p.data_ptr(), gt.data_ptr(), n, nj, _raw_stream(dev), err.data_ptr(),
-                                       fmean.data_ptr(), fmax.data_ptr(), jt.data_ptr() if jt is not None else None)
-        _lib.check(rc, "tsdf_pose_error_hip")
-    return PoseError(err, fmean, fmax, jt)
+        _call(dev, L.tsdf_pose_error_hip,
+              [pred.data_ptr(), ctypes.byref(pst) if pst is not None else None, max_l.data_ptr(), mid_p.data_ptr(),
+               gt.data_ptr(), n, nj, None, res.err.data_ptr(), res.frame_mean.data_ptr(), res.frame_max.data_ptr(),
+               _ptr(res.joints)], 7)
+    return res
 
 
 def joints_within(err: torch.Tensor, mm: float = 20.0) -> torch.Tensor:
@@ -404,32 +414,15 @@ def denormalize_joints(pred: torch.Tensor, max_l: torch.Tensor, mid_p: torch.Ten
 
 def _norm_call(x, max_l, mid_p, clamp, inverse, out):
     L = _lib.load()
-    _dev_check("joints", x, torch.float32)
-    dev = x.device
-    n = x.shape[0]
-    _dev_check("max_l", max_l, torch.float32, dev)
-    _dev_check("mid_p", mid_p, torch.float32, dev)
-    if max_l.numel() != n or tuple(mid_p.shape) != (n, 3):
-        raise ValueError("max_l must be [n] and mid_p [n,3]")
-    nc = x.numel() // n if n else 63
-    if n and (x.numel() != n * nc or nc % 3 or not 1 <= nc // 3 <= 170):
-        raise ValueError("joints must have shape [n, 3*J] or [n, J, 3]")
-    if out is None:
-        out = torch.empty_like(x)
-    else:
-        _dev_check("out", out, torch.float32, dev)
-        if out.shape != x.shape:
-            raise ValueError("out must have the input's shape")
+    dev, n = _frames("joints", x, max_l, mid_p)
+    nc = _coords("joints", x, n) or 63
+    out = _out("out", out, tuple(x.shape), torch.float32, dev)
     if n:
-        with _Current(dev):
-            stream = _raw_stream(dev)
-            if inverse:
-                rc = L.tsdf_denormalize_joints_hip(x.data_ptr(), max_l.data_ptr(), mid_p.data_ptr(), n, nc // 3,
-                                                   stream, out.data_ptr())
-            else:
-                rc = L.tsdf_normalize_joints_hip(x.data_ptr(), max_l.data_ptr(), mid_p.data_ptr(), n, nc // 3,
-                                                 1 if clamp else 0, stream, out.data_ptr())
-        _lib.check(rc, "tsdf_(de)normalize_joints_hip")
+        args = [x.data_ptr(), max_l.data_ptr(), mid_p.data_ptr(), n, nc // 3]
+        if inverse:
+            _call(dev, L.tsdf_denormalize_joints_hip, args + [None, out.data_ptr()], 5)
+        else:
+            _call(dev, L.tsdf_normalize_joints_hip, args + [1 if clamp else 0, None, out.data_ptr()], 6)
     return out
 
 
@@ -449,22 +442,15 @@ def voxel_pixels(depth: torch.Tensor, offsets: torch.Tensor, headers: torch.Tens
     gathers.  Runs in the DEBUG build of the library (``_lib.load_debug()``: the product does not carry the hook).
     Returns ``(tsdf, pixmap int32[n,R,R,R] indexed [z,y,x], status)``; pixmap values as in include/tsdf_debug.h."""
     L = _lib.load_debug()
-    dev, n, R = _check_inputs(L, depth, offsets, headers, res, layout)
+    dev, n, R = _pack(L, depth, offsets, headers, res, layout)
     if grid is not None:
-        _dev_check("grid", grid, torch.float32, dev)
-        if tuple(grid.shape) != (n, 8):
-            raise ValueError("grid must have shape [n, 8]")
-    tsdf = torch.empty((n, 3, R, R, R), dtype=torch.float32, device=dev)
-    pm = torch.empty((n, R, R, R), dtype=torch.int32, device=dev)
-    st = torch.empty((n,), dtype=torch.int32, device=dev)
+        _shaped("grid", grid, (n, 8), torch.float32, dev)
+    tsdf = _out("tsdf", None, (n, 3, R, R, R), torch.float32, dev)
+    pm = _out("pixmap", None, (n, R, R, R), torch.int32, dev)
+    st = _out("status", None, (n,), torch.int32, dev)
     if n:
-        with _Current(dev):
-            stream = _raw_stream(dev)
-            rc = L.tsdf_debug_pixmap_hip(depth.data_ptr(), depth.numel(), offsets.data_ptr(), headers.data_ptr(), n, R,
-                                         ctypes.byref(cam) if cam is not None else None, _lib.LAYOUTS[layout], stream,
-                                         grid.data_ptr() if grid is not None else None, tsdf.data_ptr(),
-                                         pm.data_ptr(), st.data_ptr())
-        _lib.check(rc, "tsdf_debug_pixmap_hip")
+        _call(dev, L.tsdf_debug_pixmap_hip, _head(depth, offsets, headers, n, R, cam, layout) +
+              [_ptr(grid), tsdf.data_ptr(), pm.data_ptr(), st.data_ptr()], 8)
     return tsdf, pm, st
 
 
@@ -479,29 +465,14 @@ def aabb(depth: torch.Tensor, offsets: torch.Tensor, headers: torch.Tensor, res:
          cam: Optional[_lib.TsdfCam] = None) -> AabbBatch:
     """Phase 1 + glue only: min_max_kernel + host numpy of pre/tsdf_numba.py:75-116,135-147."""
     L = _lib.load()
-    _dev_check("depth", depth, torch.float32)
-    dev = depth.device
-    _dev_check("offsets", offsets, torch.int64, dev, host_ok=True)
-    _dev_check("headers", headers, torch.int32, dev, host_ok=True)
-    if headers.dim() != 2 or headers.shape[1] != 6:
-        raise ValueError("headers must have shape [n, 6]")
-    n = headers.shape[0]
-    if offsets.numel() != n + 1:
-        raise ValueError("offsets must have n+1 entries")
-    if not L.tsdf_resolution_supported(int(res)):
-        raise ValueError(f"unsupported grid resolution {res} (multiple of 4 in 4..128)")
-    ab = torch.empty((n, 6), dtype=torch.float32, device=dev)
-    grid = torch.empty((n, 8), dtype=torch.float32, device=dev)
-    ori = torch.empty((n, 3), dtype=torch.float32, device=dev)
-    st = torch.empty((n,), dtype=torch.int32, device=dev)
+    dev, n, R = _pack(L, depth, offsets, headers, res)
+    out = AabbBatch(_out("aabb", None, (n, 6), torch.float32, dev), _out("grid", None, (n, 8), torch.float32, dev),
+                    _out("ori", None, (n, 3), torch.float32, dev), _out("status", None, (n,), torch.int32, dev))
     if n:
-        with _Current(dev):
-            stream = _raw_stream(dev)
-            rc = L.tsdf_aabb_hip(depth.data_ptr(), depth.numel(), offsets.data_ptr(), headers.data_ptr(), n, int(res),
-                                 ctypes.byref(cam) if cam is not None else None, stream,
-                                 ab.data_ptr(), grid.data_ptr(), ori.data_ptr(), st.data_ptr())
-        _lib.check(rc, "tsdf_aabb_hip")
-    return AabbBatch(ab, grid, ori, st)
+        _call(dev, L.tsdf_aabb_hip, [depth.data_ptr(), depth.numel(), offsets.data_ptr(), headers.data_ptr(), n, R, _cam(cam),
+                                     None, out.aabb.data_ptr(), out.grid.data_ptr(), out.ori.data_ptr(),
+                                     out.status.data_ptr()], 7)
+    return out
 
 
 def voxelize_grid(depth: torch.Tensor, offsets: torch.Tensor, headers: torch.Tensor, grid: torch.Tensor,
@@ -513,20 +484,13 @@ def voxelize_grid(depth: torch.Tensor, offsets: torch.Tensor, headers: torch.Ten
     Returns (tsdf float32[n,3,R,R,R], status int32[n]).
     """
     L = _lib.load()
-    dev, n, R = _check_inputs(L, depth, offsets, headers, res, layout)
-    _dev_check("grid", grid, torch.float32, dev)
-    if tuple(grid.shape) != (n, 8):
-        raise ValueError("grid must have shape [n, 8]")
-    tsdf = torch.empty((n, 3, R, R, R), dtype=torch.float32, device=dev)
-    st = torch.empty((n,), dtype=torch.int32, device=dev)
+    dev, n, R = _pack(L, depth, offsets, headers, res, layout)
+    _shaped("grid", grid, (n, 8), torch.float32, dev)
+    tsdf = _out("tsdf", None, (n, 3, R, R, R), torch.float32, dev)
+    st = _out("status", None, (n,), torch.int32, dev)
     if n:
-        with _Current(dev):
-            stream = _raw_stream(dev)
-            rc = L.tsdf_voxelize_grid_hip(depth.data_ptr(), depth.numel(), offsets.data_ptr(), headers.data_ptr(), n, R,
-                                          ctypes.byref(cam) if cam is not None else None,
-                                          _lib.LAYOUTS[layout], stream, grid.data_ptr(), tsdf.data_ptr(),
-                                          st.data_ptr())
-        _lib.check(rc, "tsdf_voxelize_grid_hip")
+        _call(dev, L.tsdf_voxelize_grid_hip, _head(depth, offsets, headers, n, R, cam, layout) +
+              [grid.data_ptr(), tsdf.data_ptr(), st.data_ptr()], 8)
     return tsdf, st
 
 
@@ -544,25 +508,19 @@ def voxelize_aug(depth: torch.Tensor, offsets: torch.Tensor, headers: torch.Tens
     ``(TsdfBatch, gt_nor, gt_aug)`` when ``gt`` is given.
     """
     L = _lib.load()
-    dev, n, R = _check_inputs(L, depth, offsets, headers, res, layout)
-    _dev_check("xforms", xforms, torch.float64, dev)
-    if tuple(xforms.shape) != (n, 24):
-        raise ValueError("xforms must have shape [n, 24]")
+    dev, n, R = _pack(L, depth, offsets, headers, res, layout)
+    _shaped("xforms", xforms, (n, 24), torch.float64, dev)
     out = _make_out(out, n, R, dev)
     lab = gt_nor = gt_aug = None
     if gt is not None:
-        lab, gt_nor, gt_aug = _labels_struct(gt, n, dev, clamp, want_aug=True)
+        lab, gt_nor, gt_aug = _labels_struct(gt, n, n, dev, clamp, want_gt=True)
     if n:
-        with _Current(dev):
-            stream = _raw_stream(dev)
-            args = (depth.data_ptr(), depth.numel(), offsets.data_ptr(), headers.data_ptr(), n, R,
-                    ctypes.byref(cam) if cam is not None else None, _lib.LAYOUTS[layout], stream, xforms.data_ptr(),
-                    out.tsdf.data_ptr(), out.max_l.data_ptr(), out.mid_p.data_ptr(), out.status.data_ptr())
-            if lab is None:
-                rc = L.tsdf_voxelize_aug_hip(*args)
-            else:
-                rc = L.tsdf_voxelize_aug_labels_hip(*args, ctypes.byref(lab))
-        _lib.check(rc, "tsdf_voxelize_aug_hip")
+        args = _head(depth, offsets, headers, n, R, cam, layout) + \
+            [xforms.data_ptr(), out.tsdf.data_ptr(), out.max_l.data_ptr(), out.mid_p.data_ptr(), out.status.data_ptr()]
+        if lab is None:
+            _call(dev, L.tsdf_voxelize_aug_hip, args, 8)
+        else:
+            _call(dev, L.tsdf_voxelize_aug_labels_hip, args + [ctypes.byref(lab)], 8)
     return out if gt is None else (out, gt_nor, gt_aug)
 
 
@@ -584,15 +542,7 @@ def point_clouds(depth: torch.Tensor, offsets: torch.Tensor, headers: torch.Tens
     Returns :class:`PointCloudBatch`; frames that are not OK get all-zero rows.  Enqueues on the current stream and
     returns without synchronising."""
     L = _lib.load()
-    _dev_check("depth", depth, torch.float32)
-    dev = depth.device
-    _dev_check("offsets", offsets, torch.int64, dev, host_ok=True)
-    _dev_check("headers", headers, torch.int32, dev, host_ok=True)
-    if headers.dim() != 2 or headers.shape[1] != 6:
-        raise ValueError("headers must have shape [n, 6]")
-    n = headers.shape[0]
-    if offsets.numel() != n + 1:
-        raise ValueError("offsets must have n+1 entries")
+    dev, n, _ = _pack(L, depth, offsets, headers)
     P = int(points)
     if not 1 <= P <= 0x7fffffff:
         raise ValueError("points must be in 1..2^31-1")
@@ -602,26 +552,17 @@ def point_clouds(depth: torch.Tensor, offsets: torch.Tensor, headers: torch.Tens
     if not -2 ** 63 <= frame_base < 2 ** 63:
         raise ValueError("frame_base must fit int64")
     if xforms is not None:
-        _dev_check("xforms", xforms, torch.float64, dev)
-        if tuple(xforms.shape) != (n, 24):
-            raise ValueError("xforms must have shape [n, 24]")
+        _shaped("xforms", xforms, (n, 24), torch.float64, dev)
+    fields = (("points", (n, P, 3), torch.float64), ("count", (n,), torch.int32), ("status", (n,), torch.int32))
     if out is None:
-        out = PointCloudBatch(torch.empty((n, P, 3), dtype=torch.float64, device=dev),
-                              torch.empty(n, dtype=torch.int32, device=dev),
-                              torch.empty(n, dtype=torch.int32, device=dev))
+        out = PointCloudBatch(*[_out(name, None, shape, dtype, dev) for name, shape, dtype in fields])
     else:
-        _dev_check("out.points", out.points, torch.float64, dev)
-        _dev_check("out.count", out.count, torch.int32, dev)
-        _dev_check("out.status", out.status, torch.int32, dev)
-        if tuple(out.points.shape) != (n, P, 3) or out.count.numel() != n or out.status.numel() != n:
-            raise ValueError("out tensors have the wrong shape")
+        for name, shape, dtype in fields:
+            _shaped("out." + name, getattr(out, name), shape, dtype, dev)
     if n:
-        with _Current(dev):
-            rc = L.tsdf_point_clouds_hip(depth.data_ptr(), depth.numel(), offsets.data_ptr(), headers.data_ptr(), n, P,
-                                         ctypes.byref(cam) if cam is not None else None, seed, frame_base,
-                                         xforms.data_ptr() if xforms is not None else None, _raw_stream(dev),
-                                         out.points.data_ptr(), out.count.data_ptr(), out.status.data_ptr())
-        _lib.check(rc, "tsdf_point_clouds_hip")
+        _call(dev, L.tsdf_point_clouds_hip,
+              [depth.data_ptr(), depth.numel(), offsets.data_ptr(), headers.data_ptr(), n, P, _cam(cam), seed, frame_base,
+               _ptr(xforms), None, out.points.data_ptr(), out.count.data_ptr(), out.status.data_ptr()], 10)
     return out
 
 
@@ -652,17 +593,13 @@ def cloud_grids(points: torch.Tensor, res: int = 32, cam: Optional[_lib.TsdfCam]
         raise ValueError("points must hold 1..2^31-1 points per frame")
     if not L.tsdf_resolution_supported(int(res)):
         raise ValueError(f"unsupported grid resolution {res} (multiple of 4 in 4..128)")
-    out = CloudGridBatch(torch.empty((n, 8), dtype=torch.float32, device=dev),
-                         torch.empty(n, dtype=torch.float32, device=dev),
-                         torch.empty((n, 3), dtype=torch.float32, device=dev),
-                         torch.empty((n, 6), dtype=torch.float32, device=dev),
-                         torch.empty(n, dtype=torch.int32, device=dev))
+    out = CloudGridBatch(_out("grid", None, (n, 8), torch.float32, dev), _out("max_l", None, (n,), torch.float32, dev),
+                         _out("mid_p", None, (n, 3), torch.float32, dev), _out("aabb", None, (n, 6), torch.float32, dev),
+                         _out("status", None, (n,), torch.int32, dev))
     if n:
-        with _Current(dev):
-            rc = L.tsdf_cloud_grid_hip(points.data_ptr(), n, P, int(res), ctypes.byref(cam) if cam is not None else None,
-                                       _raw_stream(dev), out.grid.data_ptr(), out.max_l.data_ptr(), out.mid_p.data_ptr(),
-                                       out.aabb.data_ptr(), out.status.data_ptr())
-        _lib.check(rc, "tsdf_cloud_grid_hip")
+        _call(dev, L.tsdf_cloud_grid_hip, [points.data_ptr(), n, P, int(res), _cam(cam), None, out.grid.data_ptr(),
+                                           out.max_l.data_ptr(), out.mid_p.data_ptr(), out.aabb.data_ptr(),
+                                           out.status.data_ptr()], 5)
     return out
 
 

@@ -100,6 +100,44 @@ assert ok(labels=ctypes.pointer(Labels(64, 21, 1, 64, 0))) == 0 and ok(labels=ct
 assert ok(labels=ctypes.pointer(Labels(0, 21, 1, 64, 0))) == -1 and ok(labels=ctypes.pointer(Labels(0, 21, 1, 0, 0)), n=0) == 1
 assert ok(labels=ctypes.pointer(Labels(64, 171, 1, 64, 0)), n=0) == -1
 
+# ---- the same check with what an entry requires on top (the kNeed* bits of tsdf_host.inc): rows of tests/test_abi.py's
+# table, here under the sanitizers
+class Pca(ctypes.Structure):
+    _fields_ = [("d_mean", vp), ("d_coeff", vp), ("n_components", ctypes.c_int), ("d_out_gt_pca", vp)]
+
+
+L.tsdf_test_check_entry_args.restype = ctypes.c_int
+L.tsdf_test_check_entry_args.argtypes = L.tsdf_test_check_run_args.argtypes + [ctypes.c_uint, vp, vp, vp, vp, i64, vp,
+                                                                               ctypes.POINTER(Pca), vp, vp]
+chk = lambda **kw: L.tsdf_test_check_entry_args(*[kw.get(k, d) for k, d in (
+    ("depth", one), ("depth_len", 16), ("offsets", one), ("headers", one), ("n", 1), ("R", 32), ("cam", None),
+    ("layout", 0), ("out", one), ("aabb_only", 0), ("labels", None), ("needs", 0), ("max_l", one), ("mid_p", one),
+    ("index", None), ("h_index", None), ("n_pack", 0), ("xforms", None), ("pca", None), ("grid_in", None), ("pixmap", None))])
+assert chk() == ok() == 0 and chk(n=0) == ok(n=0) == 1 and chk(out=null) == ok(out=null) == -1
+PLACE, INDEX, HOST_INDEX, XFORMS, LABELS, PCA, GRID_IN, PIXMAP = (1 << b for b in range(8))
+lab, pca = ctypes.pointer(Labels(64, 21, 1, 64, 0)), ctypes.pointer(Pca(64, 64, 10, 64))
+assert chk(needs=PLACE) == 0 and chk(needs=PLACE, max_l=null) == -1 and chk(needs=PLACE, mid_p=null) == -1
+assert chk(needs=PLACE, max_l=null, n=0) == 1
+hidx = (ctypes.c_int64 * 64)()
+for need, field in ((INDEX, "index"), (HOST_INDEX, "h_index")):
+    good = {"needs": need, field: ctypes.cast(hidx, vp), "n_pack": 4}
+    assert chk(**good) == 0 and chk(**dict(good, **{field: null})) == -1 and chk(**dict(good, **{field: null, "n": 0})) == 1
+    assert chk(**dict(good, n_pack=0)) == -1 and chk(**dict(good, n_pack=0, n=0)) == 1
+    assert chk(**dict(good, n_pack=-1)) == -1 and chk(**dict(good, n_pack=-1, n=0)) == -1      # before "nothing to do"
+    assert chk(**dict(good, n=33)) == (-1 if need == HOST_INDEX else 0) and chk(**dict(good, n=32)) == 0
+assert chk(needs=XFORMS, xforms=one) == 0 and chk(needs=XFORMS) == -1 and chk(needs=XFORMS, n=0) == 1
+assert chk(xforms=vp(12)) == -1 and chk(xforms=vp(12), n=0) == -1 and chk(xforms=vp(72)) == 0   # alignment: also when optional
+assert chk(needs=LABELS, labels=lab) == 0 and chk(needs=LABELS) == -1 and chk(needs=LABELS, n=0) == -1
+assert chk(needs=LABELS | PCA, labels=lab, pca=pca) == 0 and chk(needs=LABELS | PCA, labels=lab, pca=pca, n=0) == 1
+for bad in (None, ctypes.pointer(Pca(64, 64, 0, 64)), ctypes.pointer(Pca(64, 64, 64, 64))):
+    assert chk(needs=LABELS | PCA, labels=lab, pca=bad) == -1 and chk(needs=LABELS | PCA, labels=lab, pca=bad, n=0) == -1
+for bad in (Pca(0, 64, 10, 64), Pca(64, 0, 10, 64), Pca(64, 64, 10, 0)):
+    assert chk(needs=LABELS | PCA, labels=lab, pca=ctypes.pointer(bad)) == -1
+    assert chk(needs=LABELS | PCA, labels=lab, pca=ctypes.pointer(bad), n=0) == 1
+assert chk(needs=PCA, pca=pca) == -1 and chk(needs=PCA, pca=pca, n=0) == -1                     # a projection needs labels
+assert chk(needs=GRID_IN, grid_in=one) == 0 and chk(needs=GRID_IN) == -1 and chk(needs=GRID_IN, n=0) == 1
+assert chk(needs=PIXMAP, pixmap=one) == 0 and chk(needs=PIXMAP) == -1 and chk(needs=PIXMAP, max_l=null, mid_p=null, pixmap=one) == 0
+
 # ---- the per-stream slot table -----------------------------------------------------------------------------------------
 a, b = L.tsdf_test_slot_acquire(0xA0, 0), L.tsdf_test_slot_acquire(0xB0, 0)
 assert a >= 0 and b >= 0 and a != b and L.tsdf_test_slot_acquire(0xA0, 0) == a
