@@ -85,8 +85,14 @@ INLINE_INDEX_MAX = 32   # TSDF_INLINE_INDEX_MAX of include/tsdf.h
 # test hooks of include/tsdf_debug.h.  Never loaded unless somebody asks for a hook.
 DEBUG_LIB_PATH = os.path.join(os.path.dirname(_HERE), "build", "libtsdf_hip_debug.so")
 
+# The extension library of include/tsdf_augment.h (make -C csrc augment): the augmentation's draws and maps on the GPU.
+# A binary of its own, because the ABI of libtsdf_hip.so is frozen.
+AUGMENT_LIB_PATH = os.path.join(_HERE, "libtsdf_augment.so")
+AUGMENT_VERSION = 1
+
 _lib = None
 _debug_lib = None
+_augment_lib = None
 
 
 def _bind(L, path: str, debug: bool = False):
@@ -167,6 +173,28 @@ def load_debug():
                           "(__graft_entry__.build() does)")
     L = _bind(ctypes.CDLL(DEBUG_LIB_PATH), DEBUG_LIB_PATH, debug=True)
     _debug_lib = L
+    return L
+
+
+def load_augment():
+    """Load libtsdf_augment.so once and declare its two entry points; raise loudly if it is not there."""
+    global _augment_lib
+    if _augment_lib is not None:
+        return _augment_lib
+    if not os.path.exists(AUGMENT_LIB_PATH):
+        raise ImportError(f"{AUGMENT_LIB_PATH} not found: build it with `make -C handposeestimation-with-3d-cnns_amd/csrc "
+                          "augment` (__graft_entry__.build() does). There is no CPU fallback.")
+    L = ctypes.CDLL(AUGMENT_LIB_PATH)
+    L.tsdf_augment_version.restype = ctypes.c_int
+    L.tsdf_augment_version.argtypes = []
+    if L.tsdf_augment_version() != AUGMENT_VERSION:
+        raise ImportError(f"{AUGMENT_LIB_PATH} has version {L.tsdf_augment_version()}, this package needs "
+                          f"{AUGMENT_VERSION}: rebuild it")
+    vp = ctypes.c_void_p
+    L.tsdf_aug_draw_hip.restype = ctypes.c_int
+    # centres, n_src, index, n, key, counter0, stream, xforms, stretch, rot
+    L.tsdf_aug_draw_hip.argtypes = [vp, ctypes.c_int64, vp, ctypes.c_int, ctypes.c_uint64, ctypes.c_uint64, vp, vp, vp, vp]
+    _augment_lib = L
     return L
 
 

@@ -113,6 +113,47 @@ def random_affines(centres: np.ndarray, rng=None):
     return affines_from_params(m, stretch, rot_xy, rot_z), dict(stretch=stretch, rot_xy=rot_xy, rot_z=rot_z)
 
 
+# ---- the counter-based draws of tsdf_aug_draw_hip (include/tsdf_augment.h), restated ----
+_M64 = (1 << 64) - 1
+
+
+def _mix(z: int) -> int:
+    """splitmix64 on a Python integer, every operation mod 2^64."""
+    z = (z + 0x9E3779B97F4A7C15) & _M64
+    z = ((z ^ (z >> 30)) * 0xBF58476D1CE4E5B9) & _M64
+    z = ((z ^ (z >> 27)) * 0x94D049BB133111EB) & _M64
+    return z ^ (z >> 31)
+
+
+def _mix_np(z: np.ndarray) -> np.ndarray:
+    """splitmix64 on uint64 arrays (numpy's unsigned arithmetic wraps mod 2^64)."""
+    z = z + np.uint64(0x9E3779B97F4A7C15)
+    z = (z ^ (z >> np.uint64(30))) * np.uint64(0xBF58476D1CE4E5B9)
+    z = (z ^ (z >> np.uint64(27))) * np.uint64(0x94D049BB133111EB)
+    return z ^ (z >> np.uint64(31))
+
+
+def device_key(seed: int, epoch: int, rank: int) -> int:
+    """The key ``ResidentLoader(augment="device")`` draws under: ``mix(mix(mix(seed) + epoch) + rank)`` mod 2^64."""
+    return _mix(_mix(_mix(int(seed) & _M64) + int(epoch)) + int(rank))
+
+
+def device_draws_np(key: int, counters):
+    """What ``tsdf_aug_draw_hip`` draws for ``counters`` (any integers, taken mod 2^64) under ``key``:
+    ``(stretch float64[n], rot_xy int64[n], rot_z int64[n])`` — the reference's distributions (pre/process.py:209-216)
+    from ``h = mix(key + c)``: ``stretch = 2/3 + (mix(h) >> 11)·2^-53·(3/2 - 2/3)`` (multiply, round, add, round), each angle
+    ``-30 + (((mix(h + k) >> 32)·60) >> 32)`` with k = 1, 2."""
+    c = np.array([int(v) & _M64 for v in np.asarray(counters, dtype=object).reshape(-1)], dtype=np.uint64)
+    with np.errstate(over="ignore"):
+        h = _mix_np(c + np.uint64(int(key) & _M64))
+        u = (_mix_np(h) >> np.uint64(11)).astype(np.float64) * 2.0 ** -53
+        lo = 2.0 / 3.0
+        stretch = lo + u * (1.5 - lo)
+        rot = [((_mix_np(h + np.uint64(k)) >> np.uint64(32)) * np.uint64(60) >> np.uint64(32)).astype(np.int64) - 30
+               for k in (1, 2)]
+    return stretch, rot[0], rot[1]
+
+
 def apply_affine(points: np.ndarray, xforms: np.ndarray) -> np.ndarray:
     """T(p) for points [n,k,3] (or [n,63] joint rows) with xforms [n,24]; returns the input's shape."""
     pts = np.asarray(points, np.float64)

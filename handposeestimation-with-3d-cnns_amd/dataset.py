@@ -29,15 +29,15 @@ import os
 import sys
 import queue
 import threading
-from typing import Iterator, List, NamedTuple, Optional, Sequence, Tuple
+from typing import Iterator, List, NamedTuple, Optional, Sequence, Tuple, Union
 
 import numpy as np
 import torch
 import torch.utils.data as data
 
 from . import packing, shard
-from .voxelize import (TsdfBatch, denormalize_joints, empty_batch, normalize_joints, voxelize, voxelize_indexed,  # noqa: F401
-                       voxelize_labels)
+from .voxelize import (TsdfBatch, aug_xforms, denormalize_joints, empty_batch, normalize_joints, voxelize,  # noqa: F401
+                       voxelize_indexed, voxelize_labels)
 
 
 def _subset(size: str) -> Tuple[int, int]:
@@ -471,21 +471,31 @@ class ResidentLoader:
     stream that was current when the block was launched — a consumer on that stream can never observe the overwrite;
     clone what you keep).  ``augment=True`` draws its maps per batch exactly as without prefetch.  The ``augment`` draws
     use numpy's ``Generator`` seeded per (seed, epoch, rank, batch): the reference's distributions, not its legacy stream.
+
+    ``augment="device"`` draws the maps on the GPU instead (:func:`voxelize.aug_xforms`, one small launch before the
+    voxelizer's, on the same stream): the grid centres stay on the device, nothing is drawn, inverted or copied on the
+    host.  Frame p of the rank's epoch (its position in the flat order of the epoch's batches) draws from
+    ``(augment.device_key(seed, epoch, rank), p)``, so the batches do not depend on ``prefetch``.  Same distributions as
+    ``augment=True``, another stream of draws.
     """
 
     def __init__(self, dataset: MSRADepthDataset, batch_size: int, device, res: int = 32, shuffle: bool = False,
                  seed: int = 0, drop_last: bool = False, rank: int = 0, world: int = 1, labels: bool = True,
-                 clamp: bool = True, layout: str = "czyx", augment: bool = False, balance: str = "frames",
+                 clamp: bool = True, layout: str = "czyx", augment: Union[bool, str] = False, balance: str = "frames",
                  prefetch: int = 1, ring: int = 2):
         """``augment=True``: every frame of every batch gets a fresh 3-D augmentation with the reference's distributions
         (``augment.random_affines``, pre/process.py:209-216) about its own un-augmented grid centre, fused into the
         voxelizer (BASELINE configs[4]); the yielded ``gt`` are then the mapped joints, ``gt_nor`` their labels.
+        ``augment="device"``: the same, with the maps drawn on the GPU (class docstring).
         ``balance``: see :func:`plan_batches` (``"frames"``: every rank yields the same number of batches)."""
         if not dataset.packed:
             raise ValueError("ResidentLoader needs a pack-backed dataset (packing.pack_tree + packed_dir=, or from_packs)")
         if prefetch < 1 or ring < 2:
             raise ValueError("prefetch must be >= 1 and ring >= 2")
+        if isinstance(augment, str) and augment != "device":
+            raise ValueError(f"augment must be False, True or 'device', got {augment!r}")
         self.augment = bool(augment)
+        self.device_draws = augment == "device"
         self.balance = balance
         self.prefetch, self.ring = int(prefetch), int(ring)
         self.ds, self.bs, self.device, self.res = dataset, int(batch_size), torch.device(device), res
@@ -516,8 +526,14 @@ class ResidentLoader:
         if self.augment:   # the centres the maps turn about: every frame's own grid centre, one AABB launch over the pack
             from .voxelize import aabb
             d, o, h, _ = self._dev
-            self._mid = aabb(d, o, h, res=self.res).grid[:, :3].cpu().numpy().astype(np.float64)
-            self._xf = [torch.empty((self.bs, 24), dtype=torch.float64).pin_memory() for _ in range(2)]
+            mid = aabb(d, o, h, res=self.res).grid[:, :3]
+            if self.device_draws:   # the centres stay where the launch left them; one map buffer per launch in flight
+                self._mid = mid.contiguous()
+                self._xf = torch.empty((self.ring if self.prefetch > 1 else 2, self.bs * self.prefetch, 24),
+                                       dtype=torch.float64, device=self.device)
+            else:
+                self._mid = mid.cpu().numpy().astype(np.float64)
+                self._xf = [torch.empty((self.bs, 24), dtype=torch.float64).pin_memory() for _ in range(2)]
 
     def _batches(self) -> List[np.ndarray]:
         return plan_batches(len(self.ds), self.bs, self.rank, self.world, self.shuffle, self.seed, self.epoch,
@@ -537,6 +553,10 @@ class ResidentLoader:
 
     def _iter_single(self, batches, epoch) -> Iterator[VoxelBatch]:
         depth, off, hdr, gt = self._dev
+        key, pos = 0, 0
+        if self.device_draws:
+            from . import augment as _aug
+            key = _aug.device_key(self.seed, epoch, self.rank)
         for k, b in enumerate(batches):
             cur = torch.cuda.current_stream(self.device)   # (per batch: the consumer may have switched streams)
             h_idx, done = self._idx[k & 1]
@@ -546,7 +566,10 @@ class ResidentLoader:
             gidx = self._g[b]
             h_idx.numpy()[:n] = gidx
             xf = None
-            if self.augment:
+            if self.device_draws:   # (the buffer's last reader is the voxelizer launch `done` was recorded after)
+                xf = aug_xforms(self._mid, index=h_idx[:n], key=key, counter0=pos, out=self._xf[k & 1, :n])
+                pos += n
+            elif self.augment:
                 from . import augment as _aug
                 h_xf = self._xf[k & 1]
                 h_xf.numpy()[:n] = _aug.random_affines(self._mid[gidx], rng=(self.seed, epoch, self.rank, k))[0]
@@ -587,7 +610,11 @@ class ResidentLoader:
         gidx = self._g[flat]
         d_idx = torch.from_numpy(np.ascontiguousarray(gidx)).to(self.device)
         d_xf = None
-        if self.augment:   # the same draws as without prefetch: one generator per batch
+        key = 0
+        if self.device_draws:
+            from . import augment as _aug
+            key = _aug.device_key(self.seed, epoch, self.rank)
+        elif self.augment:   # the same draws as without prefetch: one generator per batch
             from . import augment as _aug
             xf = np.empty((flat.size, 24), np.float64)
             pos = 0
@@ -607,9 +634,12 @@ class ResidentLoader:
             else:      # the epoch's last block: the leading part of the ring entry
                 o = TsdfBatch(out.tsdf[:nfr], out.max_l[:nfr], out.mid_p[:nfr], out.status[:nfr])
                 gn, gg = gt_nor[:nfr], g[:nfr]
+            xf = None if d_xf is None else d_xf[pos:pos + nfr]
+            if self.device_draws:   # one launch for the block's maps, into the ring entry's buffer, on the launch stream
+                xf = aug_xforms(self._mid, index=d_idx[pos:pos + nfr], key=key, counter0=pos,
+                                out=self._xf[blk % self.ring, :nfr])
             voxelize_indexed(depth, off, hdr, d_idx[pos:pos + nfr], gt, res=self.res, layout=self.layout, clamp=self.clamp,
-                             out=o, out_gt_nor=gn, out_gt=gg,
-                             xforms=None if d_xf is None else d_xf[pos:pos + nfr])
+                             out=o, out_gt_nor=gn, out_gt=gg, xforms=xf)
             pos += nfr
             if full:
                 yield from views

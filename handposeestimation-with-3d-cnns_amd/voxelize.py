@@ -524,6 +524,48 @@ def voxelize_aug(depth: torch.Tensor, offsets: torch.Tensor, headers: torch.Tens
     return out if gt is None else (out, gt_nor, gt_aug)
 
 
+def aug_xforms(centres: torch.Tensor, n: Optional[int] = None, index: Optional[torch.Tensor] = None, key: int = 0,
+               counter0: int = 0, out: Optional[torch.Tensor] = None, want_params: bool = False):
+    """The maps of a batch of fused augmentations, drawn on the GPU (``tsdf_aug_draw_hip`` of libtsdf_augment.so, one small
+    launch on the current stream; include/tsdf_augment.h has the contract).
+
+    centres   float32[N,3] on the GPU: every frame's un-augmented grid centre (``aabb(...).grid[:, :3]`` / ``mid_p``)
+    index     int64[n] (device or page-locked host memory): batch position i turns about ``centres[index[i]]``; without
+              it position i uses frame i and ``n`` defaults to N
+    key, counter0   position i draws from ``(key, counter0 + i)`` alone (integers mod 2^64;
+              ``augment.device_draws_np(key, counter0 + arange(n))`` restates the draws, ``augment.device_key`` makes a key)
+    out       optional float64[n,24] to write into (it is returned)
+    Returns ``xforms`` float64[n,24] — what :func:`voxelize_aug` / :func:`voxelize_indexed` take —, or with ``want_params``
+    ``(xforms, stretch float64[n], rot int32[n,2])``, rot = (rot_xy, rot_z) in degrees.  A position whose index is outside
+    [0, N) gets the identity map and a NaN stretch."""
+    A = _lib.load_augment()
+    _dev_check("centres", centres, torch.float32)
+    dev = centres.device
+    if centres.dim() != 2 or centres.shape[1] != 3:
+        raise ValueError("centres must have shape [N, 3]")
+    n_src = centres.shape[0]
+    if index is not None:
+        _dev_check("index", index, torch.int64, dev, host_ok=True)
+        if index.dim() != 1:
+            raise ValueError("index must have shape [n]")
+        if n is not None and int(n) != index.numel():
+            raise ValueError("n must be the length of index")
+        n = index.numel()
+    n = n_src if n is None else int(n)
+    if n < 0:
+        raise ValueError("n must be >= 0")
+    if n and n_src < 1:
+        raise ValueError("centres holds no frame")
+    xf = _out("out", out, (n, 24), torch.float64, dev)
+    stretch = _out("stretch", None, (n,), torch.float64, dev) if want_params else None
+    rot = _out("rot", None, (n, 2), torch.int32, dev) if want_params else None
+    if n:
+        m64 = (1 << 64) - 1
+        _call(dev, A.tsdf_aug_draw_hip, [centres.data_ptr(), n_src, _ptr(index), n, int(key) & m64, int(counter0) & m64, None,
+                                         xf.data_ptr(), _ptr(stretch), _ptr(rot)], 6)
+    return (xf, stretch, rot) if want_params else xf
+
+
 class PointCloudBatch(NamedTuple):
     points: torch.Tensor  # float64[n, P, 3]
     count: torch.Tensor   # int32[n]  valid pixels of the frame (m)
