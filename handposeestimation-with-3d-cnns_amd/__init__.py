@@ -6,6 +6,8 @@ behind the C ABI of include/tsdf.h.  Nothing here falls back to a CPU implementa
 
 Batched API (torch tensors on the GPU):  voxelize, voxelize_grid, voxelize_aug (fused 3-D augmentation), aabb
 Augmentation drawn on the GPU:           aug_xforms (libtsdf_augment.so, include/tsdf_augment.h), ResidentLoader(augment="device")
+... from counters in device memory:      aug_xforms_at, aug_state, AugmentedStep (libtsdf_augstep.so, include/tsdf_augstep.h),
+                                         MSRA_Dataset(aug="device"), ResidentLoader(augment="device", graph=True)
 Reference-signature shims:               tsdf_numba.cal_tsdf_cuda, tsdf_for.tsdf_f / tsdf_cal,
                                          process.DataProcess
 Host side:                               packing (MSRA .bin reader / batch packer), shard, synth,
@@ -18,8 +20,8 @@ The reference's process(), batched:      cloud_grids (grid placed on a cloud's e
 """
 from . import _lib  # noqa: F401
 from ._lib import TsdfCam, TsdfError, default_cam  # noqa: F401
-from .voxelize import (AabbBatch, CloudGridBatch, PointCloudBatch, PoseError, ProcessBatch, TsdfBatch, aabb,  # noqa: F401
-                       aug_xforms, cloud_grids, denormalize_joints, empty_batch,
+from .voxelize import (AabbBatch, AugmentedStep, CloudGridBatch, PointCloudBatch, PoseError, ProcessBatch, TsdfBatch, aabb,  # noqa: F401
+                       aug_state, aug_xforms, aug_xforms_at, cloud_grids, denormalize_joints, empty_batch,
                        frames_within, joints_within, normalize_joints, point_clouds, pose_error, process_batch,
                        project_joints, release_stream, voxel_pixels,
                        voxelize, voxelize_aug, voxelize_grid, voxelize_indexed, voxelize_labels)
@@ -34,4 +36,5 @@ __all__ = ["voxelize", "voxelize_labels", "voxelize_indexed", "ResidentLoader", 
            "default_cam", "cal_tsdf_cuda", "tsdf_f", "tsdf_cal", "DataProcess", "packing", "shard",
            "synth", "dataset", "MSRADepthDataset", "MSRA_Dataset", "VoxelLoader", "VoxelBatch", "normalize_joints", "denormalize_joints",
            "pca", "JointPCA", "fit_joint_pca", "project_joints", "pose_error", "PoseError", "joints_within", "frames_within",
-           "point_clouds", "PointCloudBatch", "cloud_grids", "CloudGridBatch", "process_batch", "ProcessBatch", "aug_xforms"]
+           "point_clouds", "PointCloudBatch", "cloud_grids", "CloudGridBatch", "process_batch", "ProcessBatch", "aug_xforms",
+           "aug_xforms_at", "aug_state", "AugmentedStep"]

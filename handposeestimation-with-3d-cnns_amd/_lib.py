@@ -90,9 +90,15 @@ DEBUG_LIB_PATH = os.path.join(os.path.dirname(_HERE), "build", "libtsdf_hip_debu
 AUGMENT_LIB_PATH = os.path.join(_HERE, "libtsdf_augment.so")
 AUGMENT_VERSION = 1
 
+# The extension library of include/tsdf_augstep.h (make -C csrc augstep): the same draws from a key and counters that
+# live in device memory.  Again a binary of its own: libtsdf_augment.so is frozen at its two exports.
+AUGSTEP_LIB_PATH = os.path.join(_HERE, "libtsdf_augstep.so")
+AUGSTEP_VERSION = 1
+
 _lib = None
 _debug_lib = None
 _augment_lib = None
+_augstep_lib = None
 
 
 def _bind(L, path: str, debug: bool = False):
@@ -195,6 +201,28 @@ def load_augment():
     # centres, n_src, index, n, key, counter0, stream, xforms, stretch, rot
     L.tsdf_aug_draw_hip.argtypes = [vp, ctypes.c_int64, vp, ctypes.c_int, ctypes.c_uint64, ctypes.c_uint64, vp, vp, vp, vp]
     _augment_lib = L
+    return L
+
+
+def load_augstep():
+    """Load libtsdf_augstep.so once and declare its two entry points; raise loudly if it is not there."""
+    global _augstep_lib
+    if _augstep_lib is not None:
+        return _augstep_lib
+    if not os.path.exists(AUGSTEP_LIB_PATH):
+        raise ImportError(f"{AUGSTEP_LIB_PATH} not found: build it with `make -C handposeestimation-with-3d-cnns_amd/csrc "
+                          "augstep` (__graft_entry__.build() does). There is no CPU fallback.")
+    L = ctypes.CDLL(AUGSTEP_LIB_PATH)
+    L.tsdf_augstep_version.restype = ctypes.c_int
+    L.tsdf_augstep_version.argtypes = []
+    if L.tsdf_augstep_version() != AUGSTEP_VERSION:
+        raise ImportError(f"{AUGSTEP_LIB_PATH} has version {L.tsdf_augstep_version()}, this package needs "
+                          f"{AUGSTEP_VERSION}: rebuild it")
+    vp = ctypes.c_void_p
+    L.tsdf_aug_draw_at_hip.restype = ctypes.c_int
+    # centres, n_src, index, n, state, counters, stream, xforms, stretch, rot
+    L.tsdf_aug_draw_at_hip.argtypes = [vp, ctypes.c_int64, vp, ctypes.c_int, vp, vp, vp, vp, vp, vp]
+    _augstep_lib = L
     return L
 
 

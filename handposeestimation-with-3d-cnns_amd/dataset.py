@@ -477,12 +477,18 @@ class ResidentLoader:
     host.  Frame p of the rank's epoch (its position in the flat order of the epoch's batches) draws from
     ``(augment.device_key(seed, epoch, rank), p)``, so the batches do not depend on ``prefetch``.  Same distributions as
     ``augment=True``, another stream of draws.
+
+    ``graph=True`` (with ``augment="device"`` and ``prefetch=1``) sends every full batch through one
+    :class:`voxelize.AugmentedStep`: the two launches of the step are captured once and replayed, the batch's frame
+    numbers and ``{key, counter}`` go up in one small copy.  The batches equal those of ``graph=False`` bit for bit; their
+    tensors are the step's static outputs, valid until the next batch is drawn (clone what you keep).  The epoch's short
+    last batch takes the eager path.
     """
 
     def __init__(self, dataset: MSRADepthDataset, batch_size: int, device, res: int = 32, shuffle: bool = False,
                  seed: int = 0, drop_last: bool = False, rank: int = 0, world: int = 1, labels: bool = True,
                  clamp: bool = True, layout: str = "czyx", augment: Union[bool, str] = False, balance: str = "frames",
-                 prefetch: int = 1, ring: int = 2):
+                 prefetch: int = 1, ring: int = 2, graph: bool = False):
         """``augment=True``: every frame of every batch gets a fresh 3-D augmentation with the reference's distributions
         (``augment.random_affines``, pre/process.py:209-216) about its own un-augmented grid centre, fused into the
         voxelizer (BASELINE configs[4]); the yielded ``gt`` are then the mapped joints, ``gt_nor`` their labels.
@@ -494,8 +500,14 @@ class ResidentLoader:
             raise ValueError("prefetch must be >= 1 and ring >= 2")
         if isinstance(augment, str) and augment != "device":
             raise ValueError(f"augment must be False, True or 'device', got {augment!r}")
+        if graph is not False and graph is not True:
+            raise ValueError(f"graph must be False or True, got {graph!r}")
+        if graph and (augment != "device" or prefetch != 1):
+            raise ValueError("graph=True replays the augmented step: it needs augment='device' and prefetch=1")
         self.augment = bool(augment)
         self.device_draws = augment == "device"
+        self.graph = graph
+        self._step = None  # graph=True: the AugmentedStep of full batches
         self.balance = balance
         self.prefetch, self.ring = int(prefetch), int(ring)
         self.ds, self.bs, self.device, self.res = dataset, int(batch_size), torch.device(device), res
@@ -564,6 +576,15 @@ class ResidentLoader:
                 done.synchronize()          # the launch that read this index buffer two batches ago
             n = int(b.size)
             gidx = self._g[b]
+            if self.graph and n == self.bs:   # the captured step: index and {key, counter} in, its static outputs out
+                if self._step is None:
+                    from .voxelize import AugmentedStep
+                    self._step = AugmentedStep(depth, off, hdr, n, gt=gt, centres=self._mid, res=self.res,
+                                               layout=self.layout, clamp=self.clamp)
+                out, gt_nor, g = self._step.step(gidx, key, pos)
+                pos += n
+                yield VoxelBatch(out.tsdf, g, out.max_l, out.mid_p, out.status, gt_nor if self.labels else None)
+                continue
             h_idx.numpy()[:n] = gidx
             xf = None
             if self.device_draws:   # (the buffer's last reader is the voxelizer launch `done` was recorded after)
@@ -762,6 +783,13 @@ class MSRA_Dataset(data.Dataset):
     grid.  With ``aug=True`` every batch goes through the augmented entry — plain items with the identity map, whose
     volumes equal the plain entry's to the float32 rounding (grid, zero mask, sign and z component bit for bit).
 
+    ``aug="device"``: the same items, with the maps drawn on the GPU.  The augmented twin of frame g draws from
+    ``(augment.device_key(aug_seed, 0, 0), g)`` — a function of ``(aug_seed, g)`` alone, whatever batch the item appears in
+    (``augment.device_draws_np(key, [g])`` restates it): the same distributions as ``aug=True``, another stream of draws.
+    Nothing is drawn on the host and there is no table of maps: the grid centres stay on the device and one small launch
+    per batch (:func:`voxelize.aug_xforms_at`, counters ``item mod n``) writes the batch's maps before the voxelizer's;
+    plain items get the identity map from the same launch.
+
     Under the reference's own ``DataLoader(dataset, batch_size=B, shuffle=True)`` (train.py:36,86-91; ``num_workers=0``:
     the items are GPU tensors) the loader hands the batch's indices to :meth:`__getitems__`, which voxelizes exactly
     those B frames in ONE launch and returns them ALREADY BATCHED (``prebatched=True``, the default on a resident
@@ -782,7 +810,10 @@ class MSRA_Dataset(data.Dataset):
     def __init__(self, root_path, opt=None, train=True, aug=False, device="cuda", block: int = 1024,
                  packed_dir: Optional[str] = None, resident: Optional[bool] = None, prebatched: Optional[bool] = None,
                  ring: Optional[int] = None, aug_seed: int = 0, _raw: Optional[MSRADepthDataset] = None, pca=None):
+        if isinstance(aug, str) and aug != "device":
+            raise ValueError(f"aug must be False, True or 'device', got {aug!r}")
         self.AUG = bool(aug)
+        self.aug_device = aug == "device"
         self.aug_seed = aug_seed
         self.size = getattr(opt, "size", "small")
         self.test_idx = int(getattr(opt, "test_index", 2))
@@ -808,7 +839,13 @@ class MSRA_Dataset(data.Dataset):
         self._n = len(self.raw)
         self._aug_params = None  # aug=True: (stretch, rot_xy, rot_z) of every frame, drawn once
         self._xf_table = None    # ... and, resident, the maps of all 2n items (identity for the first n), float64[2n,24]
-        if self.AUG:
+        self._aug_key = 0        # aug="device": the key every augmented item draws under; its counter is the frame number
+        self._aug_state = None   # ... {key, 0} on the device, and the grid centres of the resident packs' frames
+        self._aug_mid = None
+        if self.aug_device:
+            from . import augment as _aug
+            self._aug_key = _aug.device_key(aug_seed, 0, 0)
+        elif self.AUG:
             from . import augment as _aug
             self._aug_params = _aug.draw_params(self._n, aug_seed)
         # full mode (3D_CNN/dataset.py:165-180): the joint-PCA basis, and gt_pca as the item's fifth element
@@ -846,20 +883,47 @@ class MSRA_Dataset(data.Dataset):
                 from . import augment as _aug
                 from .voxelize import aabb
                 rp = self._rp
-                mid = aabb(rp.depth, rp.offsets, rp.headers).grid[:, :3].cpu().numpy().astype(np.float64)[rp.frame]
-                self._xf_table = np.ascontiguousarray(np.concatenate(
-                    [_aug.identity_affines(self._n), _aug.affines_from_params(mid, *self._aug_params)]))
+                mid = aabb(rp.depth, rp.offsets, rp.headers).grid[:, :3]
                 self._frame2 = np.ascontiguousarray(np.concatenate([rp.frame, rp.frame]))
+                if self.aug_device:   # the centres stay on the device; an item's row of these two tables goes to the draw
+                    self._aug_mid = mid.contiguous()
+                    self._draw_frame = np.ascontiguousarray(np.concatenate([np.full(self._n, -1, np.int64), rp.frame]))
+                    self._draw_counter = np.ascontiguousarray(np.tile(np.arange(self._n, dtype=np.int64), 2))
+                else:
+                    mid = mid.cpu().numpy().astype(np.float64)[rp.frame]
+                    self._xf_table = np.ascontiguousarray(np.concatenate(
+                        [_aug.identity_affines(self._n), _aug.affines_from_params(mid, *self._aug_params)]))
         return self._rp
+
+    def _device_state(self) -> torch.Tensor:
+        if self._aug_state is None:
+            from .voxelize import aug_state
+            self._aug_state = aug_state(self._aug_key, 0, self.device)
+        return self._aug_state
+
+    def _device_maps(self, idx: np.ndarray) -> torch.Tensor:
+        """aug="device", resident: the maps of items ``idx`` (identity for the plain ones), one launch."""
+        from .voxelize import aug_xforms_at
+        return aug_xforms_at(self._aug_mid, self._device_state(),
+                             index=torch.from_numpy(self._draw_frame[idx]).to(self.device),
+                             counters=torch.from_numpy(self._draw_counter[idx]).to(self.device))
 
     def _aug_batch_host_fed(self, idx: np.ndarray):
         """aug=True on a dataset that is not resident: upload the frames, one AABB launch for their centres, then the
         augmented entry (identity maps for the plain items)."""
         from . import augment as _aug
-        from .voxelize import aabb, voxelize_aug
+        from .voxelize import aabb, aug_xforms_at, voxelize_aug
         src = idx % self._n
         pk = self.raw.take(src)
         depth, offsets, headers = pk.to_torch(self.device, pin=False, non_blocking=False)
+        if self.aug_device:   # AABB -> draw -> augmented entry: the centres and the maps never leave the device
+            mid = aabb(depth, offsets, headers).grid[:, :3].contiguous()
+            pos = np.where(idx < self._n, -1, np.arange(idx.size)).astype(np.int64)   # plain items: the identity map
+            xf = aug_xforms_at(mid, self._device_state(), index=torch.from_numpy(pos).to(self.device),
+                               counters=torch.from_numpy(np.ascontiguousarray(src, np.int64)).to(self.device))
+            gt = torch.from_numpy(np.ascontiguousarray(pk.gt)).to(self.device)
+            out, _, gt_aug = voxelize_aug(depth, offsets, headers, xf, res=32, gt=gt)
+            return out, gt_aug
         mid = aabb(depth, offsets, headers).grid[:, :3].cpu().numpy().astype(np.float64)
         st, rxy, rz = (p[src] for p in self._aug_params)
         xf = _aug.affines_from_params(mid, st, rxy, rz)
@@ -897,7 +961,8 @@ class MSRA_Dataset(data.Dataset):
                     rp = self._rp
                     out, u = voxelize_indexed(rp.depth, rp.offsets, rp.headers,
                                               torch.from_numpy(self._frame2[idx]).to(dev), rp.gt, clamp=False,
-                                              xforms=torch.from_numpy(self._xf_table[idx]).to(dev))
+                                              xforms=self._device_maps(idx) if self.aug_device else
+                                              torch.from_numpy(self._xf_table[idx]).to(dev))
                 else:
                     out, gt_aug = self._aug_batch_host_fed(idx)
                     u = normalize_joints(gt_aug, out.max_l, out.mid_p, clamp=False)
@@ -952,7 +1017,8 @@ class MSRA_Dataset(data.Dataset):
         kGroup = 16
         pca, k = None, 0   # (class defaults: full mode is set per instance)
 
-        def __init__(self, rp: "ResidentPacks", bs: int, ring: int, device, frame=None, xf_table=None, pca=None, k=0):
+        def __init__(self, rp: "ResidentPacks", bs: int, ring: int, device, frame=None, xf_table=None, pca=None, k=0,
+                     draw=None):
             import ctypes
             from . import _lib
             self._ctypes, self._lib = ctypes, _lib
@@ -995,7 +1061,7 @@ class MSRA_Dataset(data.Dataset):
             # batches of at most INLINE_INDEX_MAX frames: the index goes to the GPU inside the kernel arguments
             # (tsdf_voxelize_indexed_host_hip reads it during the call) — no page-locked slot, no event, and the launch
             # does not start with a read over the link
-            self.by_value = xf_table is None and bs <= _lib.INLINE_INDEX_MAX
+            self.by_value = xf_table is None and draw is None and bs <= _lib.INLINE_INDEX_MAX
             self.fn_host = self.L.tsdf_voxelize_indexed_host_hip if pca is None else \
                 self.L.tsdf_voxelize_indexed_host_pca_hip
             self.idx_buf = np.empty(bs, np.int64)
@@ -1008,6 +1074,23 @@ class MSRA_Dataset(data.Dataset):
                 self.xf_rows = [self.h_xf_np[k] for k in range(self.iring)]
                 self.xf_ptr = [self.h_xf[k].data_ptr() for k in range(self.iring)]
                 self.xf_take = xf_table.take
+            # aug="device": per index slot, the draw's frame numbers (-1: a plain item) and counters in page-locked memory
+            # next to the voxelizer's index, and the slot's maps on the device; `draw` = (centres, state, frames, counters)
+            self.draw = None
+            if draw is not None:
+                centres, state, frames, counters = draw
+                self.fn_aug = self.L.tsdf_voxelize_indexed_aug_hip if pca is None else self.L.tsdf_voxelize_indexed_pca_hip
+                self.fn_draw = _lib.load_augstep().tsdf_aug_draw_at_hip
+                self.draw = (centres, state)      # (kept alive: the launches read them by raw pointer)
+                self.draw_head = (centres.data_ptr(), int(centres.shape[0]))
+                self.state_ptr = state.data_ptr()
+                self.h_draw = torch.empty((self.iring, 2, bs), dtype=torch.int64).pin_memory()
+                self.h_draw_np = self.h_draw.numpy()
+                self.draw_rows = [(self.h_draw_np[k, 0], self.h_draw_np[k, 1]) for k in range(self.iring)]
+                self.draw_ptrs = [(self.h_draw[k, 0].data_ptr(), self.h_draw[k, 1].data_ptr()) for k in range(self.iring)]
+                self.d_xf = torch.empty((self.iring, bs, 24), dtype=torch.float64, device=self.device)
+                self.xf_ptr = [self.d_xf[k].data_ptr() for k in range(self.iring)]
+                self.frame_take, self.counter_take = frames.take, counters.take
 
         def _fresh(self, k: int) -> None:
             """New tensors for slot k (at start-up, and whenever its previous batch is still held by the consumer)."""
@@ -1071,7 +1154,9 @@ class MSRA_Dataset(data.Dataset):
                 f.sync()      # launches that read the old ring's page-locked words must be done before it goes away
             f = self._fast = MSRA_Dataset._Fast(self._rp, n, self._ring_size(n), self.device,
                                                 frame=self._frame2 if self.AUG else None, xf_table=self._xf_table,
-                                                pca=self.pca, k=self.PCA_SZ)
+                                                pca=self.pca, k=self.PCA_SZ,
+                                                draw=(self._aug_mid, self._device_state(), self._draw_frame,
+                                                      self._draw_counter) if self.aug_device else None)
         k = f.next_slot()
         a = f.args[k]
         if f.by_value:                        # (the epoch's short last batch, or another current device)
@@ -1095,7 +1180,23 @@ class MSRA_Dataset(data.Dataset):
             f.take(indices, out=f.rows[ki])
         else:
             f.h_idx_np[ki, :n] = f.take(indices)
-        if f.xf_take is not None:     # aug=True: the batch's maps next to its indices
+        if f.draw is not None:        # aug="device": one launch draws the batch's maps, the next one reads them
+            fr, cn = f.draw_rows[ki]
+            if n == f.bs:
+                f.frame_take(indices, out=fr)
+                f.counter_take(indices, out=cn)
+            else:
+                fr[:n] = f.frame_take(indices)
+                cn[:n] = f.counter_take(indices)
+            with torch.cuda.device(f.device):
+                stream = f.raw_stream(f.dev_index)
+                rc = f.fn_draw(*f.draw_head, f.draw_ptrs[ki][0], n, f.state_ptr, f.draw_ptrs[ki][1], stream, f.xf_ptr[ki],
+                               None, None)
+                if rc != 0:
+                    from . import _lib
+                    _lib.check(rc, "tsdf_aug_draw_at_hip")
+                rc = f.fn_aug(*f.head, f.idx_ptrs[ki], n, 32, None, 0, stream, f.xf_ptr[ki], *a)
+        elif f.xf_take is not None:   # aug=True: the batch's maps next to its indices
             if n == f.bs:
                 f.xf_take(indices, axis=0, out=f.xf_rows[ki])
             else:
@@ -1156,7 +1257,7 @@ class MSRA_Dataset(data.Dataset):
         if self.AUG:
             if self.resident:
                 rp = self._rp
-                xf = torch.from_numpy(self._xf_table[idx]).to(self.device)
+                xf = self._device_maps(idx) if self.aug_device else torch.from_numpy(self._xf_table[idx]).to(self.device)
                 r = voxelize_indexed(rp.depth, rp.offsets, rp.headers, torch.from_numpy(self._frame2[idx]).to(self.device),
                                      rp.gt, gt_copy=True, xforms=xf, **kw)
                 out, gt = r[0], r[2]

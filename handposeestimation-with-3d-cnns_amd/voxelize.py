@@ -566,6 +566,171 @@ def aug_xforms(centres: torch.Tensor, n: Optional[int] = None, index: Optional[t
     return (xf, stretch, rot) if want_params else xf
 
 
+def _i64(v: int) -> int:
+    """An integer mod 2^64 as the int64 with the same bits (torch has no arithmetic on uint64 tensors)."""
+    v = int(v) & ((1 << 64) - 1)
+    return v - (1 << 64) if v >> 63 else v
+
+
+def aug_state(key: int, counter0: int = 0, device=None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``{key, counter0}`` (integers mod 2^64) as the int64[2] tensor :func:`aug_xforms_at` reads on the device — a new one
+    on ``device``, or written into ``out`` by a copy on the current stream (the launches queued before it on that stream
+    still see the old state, those after it the new one)."""
+    h = torch.tensor([_i64(key), _i64(counter0)], dtype=torch.int64)
+    if out is None:
+        return h.to(device)
+    if out.dtype is not torch.int64 or out.numel() != 2:
+        raise ValueError("state must be an int64 tensor of 2 elements")
+    out.view(-1).copy_(h)
+    return out
+
+
+def aug_xforms_at(centres: torch.Tensor, state: torch.Tensor, n: Optional[int] = None,
+                  index: Optional[torch.Tensor] = None, counters: Optional[torch.Tensor] = None,
+                  out: Optional[torch.Tensor] = None, return_params: bool = False):
+    """:func:`aug_xforms` with the key and the counters read ON THE DEVICE (``tsdf_aug_draw_at_hip`` of libtsdf_augstep.so,
+    one small launch on the current stream; include/tsdf_augstep.h has the contract): the same draws and maps for the same
+    ``(key, counter)``, centre and index, bit for bit.
+
+    centres   float32[N,3] on the GPU, as for :func:`aug_xforms`
+    state     int64[2] on the GPU: ``{key, counter0}`` as 64-bit patterns (:func:`aug_state` makes one).  The KERNEL reads
+              it: whatever was written to it earlier on the same stream is what the launch uses, so a launch captured into
+              a graph draws anew at every replay whose state was rewritten before it (:class:`AugmentedStep`)
+    index     int64[n] (device or page-locked host memory) or None, as for :func:`aug_xforms`
+    counters  int64[n] (device or page-locked host memory) or None: position i draws from
+              ``(key, counter0 + counters[i])`` mod 2^64 (negative values wrap) instead of ``(key, counter0 + i)`` — a batch
+              of arbitrary frames, each with a draw of its own, in one launch
+              (``augment.device_draws_np(key, counter0 + counters)`` restates the draws)
+    out       optional float64[n,24] to write into (it is returned)
+    ``n`` defaults to the length of ``index``, else of ``counters``, else N.  Returns ``xforms`` float64[n,24], or with
+    ``return_params`` ``(xforms, stretch float64[n], rot int32[n,2])``.  A position whose index is outside [0, N) gets the
+    identity map and a NaN stretch."""
+    A = _lib.load_augstep()
+    _dev_check("centres", centres, torch.float32)
+    dev = centres.device
+    if centres.dim() != 2 or centres.shape[1] != 3:
+        raise ValueError("centres must have shape [N, 3]")
+    n_src = centres.shape[0]
+    _dev_check("state", state, torch.int64, dev)
+    if state.numel() != 2:
+        raise ValueError("state must hold 2 elements: {key, counter0}")
+    for name, t in (("index", index), ("counters", counters)):
+        if t is None:
+            continue
+        _dev_check(name, t, torch.int64, dev, host_ok=True)
+        if t.dim() != 1:
+            raise ValueError(f"{name} must have shape [n]")
+        if n is not None and int(n) != t.numel():
+            raise ValueError(f"n must be the length of {name}" if t is index else "counters must have n entries")
+        n = t.numel()
+    n = n_src if n is None else int(n)
+    if n < 0:
+        raise ValueError("n must be >= 0")
+    if n and n_src < 1:
+        raise ValueError("centres holds no frame")
+    xf = _out("out", out, (n, 24), torch.float64, dev)
+    stretch = _out("stretch", None, (n,), torch.float64, dev) if return_params else None
+    rot = _out("rot", None, (n, 2), torch.int32, dev) if return_params else None
+    if n:
+        _call(dev, A.tsdf_aug_draw_at_hip, [centres.data_ptr(), n_src, _ptr(index), n, state.data_ptr(), _ptr(counters), None,
+                                            xf.data_ptr(), _ptr(stretch), _ptr(rot)], 6)
+    return (xf, stretch, rot) if return_params else xf
+
+
+class AugmentedStep:
+    """The augmented training step — :func:`aug_xforms_at` then :func:`voxelize_indexed` ``(..., xforms=...)`` — over static
+    buffers, captured ONCE into a graph and replayed: a step's host side is one small copy (the batch's frame numbers and
+    ``{key, counter0}``) and one graph launch instead of two C calls with their argument marshalling.
+
+    One object serves one configuration: the resident pack ``depth`` / ``offsets`` / ``headers`` (``gt``: with labels), a
+    batch of exactly ``n`` frames, ``res``, ``layout``, ``clamp``.  ``centres`` float32[N,3] are the frames' un-augmented grid
+    centres (default: one :func:`aabb` launch over the pack).  It owns an int64[n] index, the int64[2] state, float64[n,24]
+    maps and ONE set of outputs; ``step`` returns those outputs, so a step's results are valid until the next ``step``
+    (queued on the same stream, the next step cannot overtake their readers; clone what you keep).
+
+    The graph is the linear sequence of the two kernels on one stream: no branches, no copies inside, and the voxelizer
+    takes the queue form it always takes under stream capture.  The draw kernel reads the state from device memory, which
+    is what lets a replay draw anew.  ``graph=False`` issues the same two calls eagerly on the same buffers."""
+
+    def __init__(self, depth: torch.Tensor, offsets: torch.Tensor, headers: torch.Tensor, n: int,
+                 gt: Optional[torch.Tensor] = None, centres: Optional[torch.Tensor] = None, res: int = 32,
+                 layout: str = "czyx", clamp: bool = True, cam: Optional[_lib.TsdfCam] = None, graph: bool = True):
+        if graph not in (False, True):
+            raise ValueError(f"graph must be False or True, got {graph!r}")
+        n = int(n)
+        if n < 1:
+            raise ValueError("n must be >= 1")
+        dev, n_pack, R = _pack(_lib.load(), depth, offsets, headers, res, layout)
+        self.n, self.res, self.layout, self.clamp, self.cam, self.device = n, R, layout, clamp, cam, dev
+        self._pack_args = (depth, offsets, headers)
+        self._gt = gt
+        self.centres = aabb(depth, offsets, headers, res=R, cam=cam).grid[:, :3].contiguous() if centres is None else centres
+        _shaped("centres", self.centres, (n_pack, 3), torch.float32, dev)
+        # index and state share one buffer, so that a step whose index comes from the host uploads both with one copy
+        self._in = torch.zeros(n + 2, dtype=torch.int64, device=dev)
+        self.index, self.state = self._in[:n], self._in[n:]
+        self._h = [torch.zeros(n + 2, dtype=torch.int64).pin_memory() for _ in range(2)]   # staging, used in turn
+        self._h_done = [None, None]   # the event after the copy that last read each staging buffer
+        self._turn = 0
+        self.xforms = torch.empty((n, 24), dtype=torch.float64, device=dev)
+        self.out = empty_batch(n, R, dev)
+        self.gt_nor = self.gt_aug = None
+        if gt is not None:
+            _dev_check("gt", gt, torch.float32, dev, host_ok=True)
+            shape = (n,) + tuple(gt.shape[1:])
+            self.gt_nor = torch.empty(shape, dtype=torch.float32, device=dev)
+            self.gt_aug = torch.empty(shape, dtype=torch.float32, device=dev)
+        self.graph = None
+        self._run()                      # eagerly once: argument checks, library loads and the device check happen here
+        if graph:
+            torch.cuda.synchronize(dev)
+            side = torch.cuda.Stream(dev)
+            g = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(g, stream=side):
+                self._run()
+            self.graph = g
+
+    def _run(self):
+        aug_xforms_at(self.centres, self.state, index=self.index, out=self.xforms)
+        d, o, h = self._pack_args
+        voxelize_indexed(d, o, h, self.index, self._gt, res=self.res, layout=self.layout, cam=self.cam, clamp=self.clamp,
+                         out=self.out, xforms=self.xforms, out_gt_nor=self.gt_nor, out_gt=self.gt_aug)
+
+    def step(self, index, key: int, counter0: int = 0):
+        """Voxelize pack frames ``index`` (n frame numbers: an int64 tensor on the device or the host, or any sequence of
+        integers), position i under the augmentation drawn from ``(key, counter0 + i)``.  Returns the object's outputs:
+        ``TsdfBatch``, or ``(TsdfBatch, gt_nor, gt_of_the_batch)`` with labels.  Enqueues on the current stream and does not
+        synchronise."""
+        n = self.n
+        k = self._turn & 1
+        self._turn += 1
+        h = self._h[k]
+        if self._h_done[k] is not None:
+            self._h_done[k].synchronize()     # the copy that read this staging buffer two steps ago
+        hn = h.numpy()
+        hn[n] = _i64(key)
+        hn[n + 1] = _i64(counter0)
+        with _Current(self.device):
+            if isinstance(index, torch.Tensor) and index.is_cuda:
+                _shaped("index", index, (n,), torch.int64, self.device)
+                self.index.copy_(index)
+                self.state.copy_(h[n:], non_blocking=True)
+            else:
+                src = index.numpy() if isinstance(index, torch.Tensor) else index
+                if len(src) != n:
+                    raise ValueError(f"index must hold {n} frame numbers")
+                hn[:n] = src
+                self._in.copy_(h, non_blocking=True)
+            if self._h_done[k] is None:
+                self._h_done[k] = torch.cuda.Event()
+            self._h_done[k].record(torch.cuda.current_stream(self.device))
+            if self.graph is not None:
+                self.graph.replay()
+            else:
+                self._run()
+        return self.out if self._gt is None else (self.out, self.gt_nor, self.gt_aug)
+
+
 class PointCloudBatch(NamedTuple):
     points: torch.Tensor  # float64[n, P, 3]
     count: torch.Tensor   # int32[n]  valid pixels of the frame (m)
