@@ -17,13 +17,16 @@ Full mode and evaluation:                pca (JointPCA, fit_joint_pca), project_
 Point clouds:                            point_clouds (back-projected, resampled on the device), export.preprocess_tree
 The reference's process(), batched:      cloud_grids (grid placed on a cloud's extremes), process_batch (point_clouds ->
                                          cloud_grids -> voxelize_grid)
+... and its augmented half:              voxelize_aug_grid (the augmented voxelizer on a caller-supplied grid), transform_joints
+                                         (libtsdf_auggrid.so, include/tsdf_auggrid.h), process_batch_aug
 """
 from . import _lib  # noqa: F401
 from ._lib import TsdfCam, TsdfError, default_cam  # noqa: F401
-from .voxelize import (AabbBatch, AugmentedStep, CloudGridBatch, PointCloudBatch, PoseError, ProcessBatch, TsdfBatch, aabb,  # noqa: F401
+from .voxelize import (AabbBatch, AugmentedStep, CloudGridBatch, PointCloudBatch, PoseError, ProcessAugBatch, ProcessBatch, TsdfBatch,  # noqa: F401
+                       aabb,
                        aug_state, aug_xforms, aug_xforms_at, cloud_grids, denormalize_joints, empty_batch,
-                       frames_within, joints_within, normalize_joints, point_clouds, pose_error, process_batch,
-                       project_joints, release_stream, voxel_pixels,
+                       frames_within, joints_within, normalize_joints, point_clouds, pose_error, process_batch, process_batch_aug,
+                       project_joints, release_stream, transform_joints, voxel_pixels, voxelize_aug_grid,
                        voxelize, voxelize_aug, voxelize_grid, voxelize_indexed, voxelize_labels)
 from .pca import JointPCA, fit_joint_pca  # noqa: F401
 from . import augment, dataset, export, packing, pca, shard, synth  # noqa: F401
@@ -37,4 +40,5 @@ __all__ = ["voxelize", "voxelize_labels", "voxelize_indexed", "ResidentLoader", 
            "synth", "dataset", "MSRADepthDataset", "MSRA_Dataset", "VoxelLoader", "VoxelBatch", "normalize_joints", "denormalize_joints",
            "pca", "JointPCA", "fit_joint_pca", "project_joints", "pose_error", "PoseError", "joints_within", "frames_within",
            "point_clouds", "PointCloudBatch", "cloud_grids", "CloudGridBatch", "process_batch", "ProcessBatch", "aug_xforms",
-           "aug_xforms_at", "aug_state", "AugmentedStep"]
+           "aug_xforms_at", "aug_state", "AugmentedStep", "voxelize_aug_grid", "transform_joints", "process_batch_aug",
+           "ProcessAugBatch"]

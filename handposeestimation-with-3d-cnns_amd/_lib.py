@@ -95,10 +95,16 @@ AUGMENT_VERSION = 1
 AUGSTEP_LIB_PATH = os.path.join(_HERE, "libtsdf_augstep.so")
 AUGSTEP_VERSION = 1
 
+# The extension library of include/tsdf_auggrid.h (make -C csrc auggrid): the augmented voxelization on a caller-supplied
+# grid and the augmented labels on their own.  A binary of its own again: everything above is frozen.
+AUGGRID_LIB_PATH = os.path.join(_HERE, "libtsdf_auggrid.so")
+AUGGRID_VERSION = 1
+
 _lib = None
 _debug_lib = None
 _augment_lib = None
 _augstep_lib = None
+_auggrid_lib = None
 
 
 def _bind(L, path: str, debug: bool = False):
@@ -223,6 +229,31 @@ def load_augstep():
     # centres, n_src, index, n, state, counters, stream, xforms, stretch, rot
     L.tsdf_aug_draw_at_hip.argtypes = [vp, ctypes.c_int64, vp, ctypes.c_int, vp, vp, vp, vp, vp, vp]
     _augstep_lib = L
+    return L
+
+
+def load_auggrid():
+    """Load libtsdf_auggrid.so once and declare its three entry points; raise loudly if it is not there."""
+    global _auggrid_lib
+    if _auggrid_lib is not None:
+        return _auggrid_lib
+    if not os.path.exists(AUGGRID_LIB_PATH):
+        raise ImportError(f"{AUGGRID_LIB_PATH} not found: build it with `make -C handposeestimation-with-3d-cnns_amd/csrc "
+                          "auggrid` (__graft_entry__.build() does). There is no CPU fallback.")
+    L = ctypes.CDLL(AUGGRID_LIB_PATH)
+    L.tsdf_auggrid_version.restype = ctypes.c_int
+    L.tsdf_auggrid_version.argtypes = []
+    if L.tsdf_auggrid_version() != AUGGRID_VERSION:
+        raise ImportError(f"{AUGGRID_LIB_PATH} has version {L.tsdf_auggrid_version()}, this package needs "
+                          f"{AUGGRID_VERSION}: rebuild it")
+    vp, i = ctypes.c_void_p, ctypes.c_int
+    L.tsdf_voxelize_aug_grid_hip.restype = i
+    # depth, depth_len, offsets, headers, n, R, cam, layout, stream, xforms, grid, tsdf, status
+    L.tsdf_voxelize_aug_grid_hip.argtypes = [vp, ctypes.c_int64, vp, vp, i, i, ctypes.POINTER(TsdfCam), i, vp, vp, vp, vp, vp]
+    L.tsdf_transform_joints_hip.restype = i
+    # gt, xforms, n, n_joints, stream, gt_aug
+    L.tsdf_transform_joints_hip.argtypes = [vp, vp, i, i, vp, vp]
+    _auggrid_lib = L
     return L
 
 

@@ -22,9 +22,13 @@ Differences from the reference writer, all deliberate, each with the switch that
     resample ``DataProcess.process()`` uses — the files do not depend on the draw.  ``placement="cloud"`` gives the
     reference's rule back: ``TSDF/<g>.npz`` is then voxelized on the grid of the very cloud that is written to
     ``Point_Cloud/<g>.npy`` (``voxelize.cloud_grids`` + ``voxelize_grid``), so the saved ``max_l`` / ``mid_p`` are a
-    function of the saved cloud, as in the reference's files.  It needs ``point_clouds`` on.  The ``_aug`` twins keep
-    the all-pixels placement of the augmented voxelizer (it has no entry with a caller-supplied grid); their maps are
-    centred on the ``mid_p`` that was written, and ``pca_dir`` uses the ``max_l`` / ``mid_p`` that were written;
+    function of the saved cloud, as in the reference's files.  It needs ``point_clouds`` on.  The ``_aug`` twins have a
+    switch of their own, independent of this one: with ``aug_placement="pixels"`` (the default) they keep the all-pixels
+    placement of the fused augmented voxelizer; with ``aug_placement="cloud"`` ``TSDF_aug/<g>.npz`` is voxelized on the
+    grid of the very cloud that is written to ``Point_Cloud_aug/<g>.npy`` (``voxelize.cloud_grids`` +
+    ``voxelize_aug_grid``), so ``max_l_aug`` / ``mid_p_aug`` belong to the cloud saved next to them.  Either way their
+    maps are centred on the plain ``mid_p`` that was written, and ``pca_dir`` uses the ``max_l`` / ``mid_p`` that were
+    written;
   * arrays are float32 (the reader casts to float32 anyway, 3D_CNN/dataset.py:101-103); ``dtype=np.float64``
     gives the reference's ``np.empty`` default back;
   * layout is ``[c,x,y,z]`` — what the reference writer produced, since it went through the CPU loop
@@ -39,7 +43,8 @@ Differences from the reference writer, all deliberate, each with the switch that
 ``aug=True`` writes the twins too (``DataProcess(aug=True)`` re-specified, process.py): each frame's map comes from
 ``augment.random_affines`` centred on the frame's plain grid centre ``mid_p``; ``TSDF_aug`` is the fused augmented
 voxelization under that map (``voxelize_aug``, same res / layout / dtype, plus ``status`` and the map itself as ``xform``
-float64[n,24]), ``ground_truth_aug`` the joints under the same map, ``Point_Cloud_aug`` the mapped cloud.
+float64[n,24]; with ``aug_placement="cloud"`` the same map on the grid of the saved augmented cloud, ``voxelize_aug_grid``),
+``ground_truth_aug`` the joints under the same map, ``Point_Cloud_aug`` the mapped cloud.
 ``data_num-<subject>.npy`` keeps counting plain frames, as the reference does.
 
 Random draws.  ``rng`` feeds the plain files only and ``aug_rng`` the augmented ones, so ``aug=True`` leaves every
@@ -49,6 +54,7 @@ plain file byte-identical to an ``aug=False`` run with the same ``rng``.  Per ge
   * ``point_clouds="device"``: the plain cloud is ``voxelize.point_clouds(seed=rng.integers(0, 2**63))``; the maps
     come from ``aug_rng``, then the augmented cloud is ``point_clouds(seed=aug_rng.integers(0, 2**63), xforms=maps)``;
     both with ``frame_base=0``.  Replaying the two generators reproduces every file.
+``aug_placement`` changes neither the draws nor their order: the voxelization draws nothing.
 
 ``pca_dir`` adds what ``read_MSRA.main()`` ends with (``joint_pca(aug=False)``, pre/joint_pca.py): the nine
 leave-one-subject-out joint-PCA fits ``<pca_dir>/<fold>.npz``, fold t fitted on the normalised labels of every subject
@@ -111,6 +117,28 @@ def _default_voxelize_cloud(pk: packing.PackedFrames, cloud: np.ndarray, res: in
     status = torch.where(cg.status != 0, cg.status, st)
     torch.cuda.synchronize(depth.device)
     return tsdf.cpu().numpy(), cg.max_l.cpu().numpy(), cg.mid_p.cpu().numpy(), status.cpu().numpy()
+
+
+def _default_voxelize_aug_cloud(pk: packing.PackedFrames, xforms: np.ndarray, cloud_aug: np.ndarray, gt: np.ndarray,
+                                res: int, layout: str, device):
+    """Upload the pack, its maps and its augmented clouds; grid placement from each cloud, the augmented volumes on that
+    placement and the joints under the maps: host arrays (tsdf, max_l, mid_p, status, gt_aug), status being the first
+    non-zero of the two stages."""
+    import torch
+
+    from .voxelize import cloud_grids, transform_joints, voxelize_aug_grid
+
+    depth, offsets, headers = pk.to_torch(device, pin=True, non_blocking=True)
+    xf = torch.from_numpy(np.ascontiguousarray(xforms, np.float64)).to(depth.device)
+    pts = torch.from_numpy(np.ascontiguousarray(cloud_aug, np.float64)).to(depth.device)
+    g = torch.from_numpy(np.ascontiguousarray(np.asarray(gt, np.float32).reshape(len(pk), -1))).to(depth.device)
+    cg = cloud_grids(pts, res=res)
+    tsdf, st = voxelize_aug_grid(depth, offsets, headers, xf, cg.grid, res=res, layout=layout)
+    gt_aug = transform_joints(g, xf)
+    status = torch.where(cg.status != 0, cg.status, st)
+    torch.cuda.synchronize(depth.device)
+    return (tsdf.cpu().numpy(), cg.max_l.cpu().numpy(), cg.mid_p.cpu().numpy(), status.cpu().numpy(),
+            gt_aug.cpu().numpy())
 
 
 def device_point_clouds(pk: packing.PackedFrames, points_num: int, seed: int, xforms: Optional[np.ndarray] = None,
@@ -207,7 +235,8 @@ def preprocess_tree(db_dir: str, save_dir: str, *, res: int = 32, layout: str = 
                     pca_dir: Optional[str] = None, aug: bool = False,
                     aug_rng: Optional[np.random.Generator] = None,
                     voxelize_aug_fn: Optional[Callable] = None, placement: str = "pixels",
-                    voxelize_cloud_fn: Optional[Callable] = None) -> Dict[str, int]:
+                    voxelize_cloud_fn: Optional[Callable] = None, aug_placement: str = "pixels",
+                    voxelize_aug_cloud_fn: Optional[Callable] = None) -> Dict[str, int]:
     """Replacement for ``read_MSRA.main()`` (pre/read_MSRA.py:37-140): voxelize a whole MSRA tree into ``save_dir`` in
     the reference's schema (with ``aug=True`` its AUG=True schema).  Returns ``{subject: frames}``.
 
@@ -221,6 +250,13 @@ def preprocess_tree(db_dir: str, save_dir: str, *, res: int = 32, layout: str = 
     ``voxelize_cloud_fn(pack, cloud, res, layout, device) -> (tsdf, max_l, mid_p, status)``, ``cloud`` being the host
     ``float64[n, points_num, 3]`` array that is saved (default: ``voxelize.cloud_grids`` + ``voxelize_grid``), and
     ``voxelize_fn`` is not called.  The random draws and their order are those of the module docstring either way.
+
+    ``aug_placement`` (the ``_aug`` twins, independent of ``placement``): "pixels" (default: the fused augmented voxelizer,
+    grid on all mapped valid pixels) or "cloud" (the grid on the augmented cloud that is written to ``Point_Cloud_aug``;
+    needs ``aug=True`` and ``point_clouds``).  With "cloud" the augmented volumes and labels come from
+    ``voxelize_aug_cloud_fn(pack, xforms, cloud_aug, gt, res, layout, device) -> (tsdf, max_l, mid_p, status, gt_aug)``,
+    ``cloud_aug`` being the host array that is saved (default: ``voxelize.cloud_grids`` + ``voxelize_aug_grid`` +
+    ``transform_joints``), and ``voxelize_aug_fn`` is not called.
 
     ``point_clouds``: True / "host" (``resample_point_clouds`` on the host), "device" (``voxelize.point_clouds``) or
     False (no cloud files).  The draws of each are in the module docstring.
@@ -236,7 +272,13 @@ def preprocess_tree(db_dir: str, save_dir: str, *, res: int = 32, layout: str = 
         raise ValueError('placement must be "pixels" or "cloud"')
     if placement == "cloud" and not point_clouds:
         raise ValueError('placement="cloud" places the grid on the saved cloud: it needs point_clouds="host" or "device"')
+    if aug_placement not in ("pixels", "cloud"):
+        raise ValueError('aug_placement must be "pixels" or "cloud"')
+    if aug_placement == "cloud" and not (aug and point_clouds):
+        raise ValueError('aug_placement="cloud" places the grid on the saved augmented cloud: it needs aug=True and '
+                         'point_clouds="host" or "device"')
     vox = voxelize_fn if voxelize_fn is not None else _default_voxelize
+    vox_aug_cloud = voxelize_aug_cloud_fn if voxelize_aug_cloud_fn is not None else _default_voxelize_aug_cloud
     vox_cloud = voxelize_cloud_fn if voxelize_cloud_fn is not None else _default_voxelize_cloud
     vox_aug = voxelize_aug_fn if voxelize_aug_fn is not None else _default_voxelize_aug
     rng = rng if rng is not None else np.random.default_rng()
@@ -275,16 +317,19 @@ def preprocess_tree(db_dir: str, save_dir: str, *, res: int = 32, layout: str = 
             if aug:
                 from .augment import random_affines
                 xf = random_affines(np.asarray(mid_p, np.float64), rng=aug_rng)[0]
-                tsdf_a, max_l_a, mid_p_a, status_a, gt_a = vox_aug(pk, xf, gt, res, layout, device)
-                if pca_dir is not None:
-                    from .pca import normalize_labels_np
-                    ok = np.asarray(status_a) == 0
-                    labels_aug.setdefault(sub, []).append(normalize_labels_np(gt_a, max_l_a, mid_p_a)[ok])
+                if aug_placement == "pixels":
+                    tsdf_a, max_l_a, mid_p_a, status_a, gt_a = vox_aug(pk, xf, gt, res, layout, device)
                 pc_a = None
                 if point_clouds == "host":
                     pc_a = resample_point_clouds(pk, points_num, aug_rng, xforms=xf)
                 elif point_clouds == "device":
                     pc_a = device_point_clouds(pk, points_num, int(aug_rng.integers(0, 2 ** 63)), xf, device=device)
+                if aug_placement == "cloud":
+                    tsdf_a, max_l_a, mid_p_a, status_a, gt_a = vox_aug_cloud(pk, xf, pc_a, gt, res, layout, device)
+                if pca_dir is not None:
+                    from .pca import normalize_labels_np
+                    ok = np.asarray(status_a) == 0
+                    labels_aug.setdefault(sub, []).append(normalize_labels_np(gt_a, max_l_a, mid_p_a)[ok])
                 write_gesture_aug(sub_out, ges, np.asarray(tsdf_a, dtype), np.asarray(max_l_a, dtype),
                                   np.asarray(mid_p_a, dtype), gt_a, status_a, xf, pc_a, gt_3d)
             total += bin_num

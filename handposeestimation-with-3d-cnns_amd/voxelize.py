@@ -835,3 +835,90 @@ def process_batch(depth: torch.Tensor, offsets: torch.Tensor, headers: torch.Ten
     tsdf, st = voxelize_grid(depth, offsets, headers, cg.grid, res=res, layout=layout, cam=cam)
     status = torch.where(pc.status != 0, pc.status, torch.where(cg.status != 0, cg.status, st))
     return ProcessBatch(pc.points, tsdf, cg.max_l, cg.mid_p, status, pc.count)
+
+
+def voxelize_aug_grid(depth: torch.Tensor, offsets: torch.Tensor, headers: torch.Tensor, xforms: torch.Tensor,
+                      grid: torch.Tensor, res: int = 32, layout: str = "czyx", cam: Optional[_lib.TsdfCam] = None):
+    """:func:`voxelize_aug` on a grid the caller supplies — the augmented twin of :func:`voxelize_grid`
+    (``tsdf_voxelize_aug_grid_hip`` of libtsdf_auggrid.so; include/tsdf_auggrid.h has the contract).
+
+    xforms  float64[n,24] on the GPU: forward rows then inverse rows, as for :func:`voxelize_aug`
+    grid    float32[n,8] on the GPU: vox_ori[3], voxel_len, trunc_dis, 3 pad words per frame, in the MAPPED frame — what
+            :func:`cloud_grids` returns for the mapped cloud
+    Returns ``(tsdf float32[n,3,R,R,R], status int32[n])``.  A frame with a bad header (2) or an unusable grid row (1:
+    ``trunc_dis`` not positive, or anything non-finite) gets a zero volume; the crop is not scanned, so a frame without a
+    valid pixel gets a zero volume with status 0.  One launch on the current stream, no synchronisation."""
+    G = _lib.load_auggrid()
+    dev, n, R = _pack(_lib.load(), depth, offsets, headers, res, layout)
+    _shaped("xforms", xforms, (n, 24), torch.float64, dev)
+    _shaped("grid", grid, (n, 8), torch.float32, dev)
+    tsdf = _out("tsdf", None, (n, 3, R, R, R), torch.float32, dev)
+    st = _out("status", None, (n,), torch.int32, dev)
+    if n:
+        _call(dev, G.tsdf_voxelize_aug_grid_hip, _head(depth, offsets, headers, n, R, cam, layout) +
+              [xforms.data_ptr(), grid.data_ptr(), tsdf.data_ptr(), st.data_ptr()], 8)
+    return tsdf, st
+
+
+def transform_joints(gt: torch.Tensor, xforms: torch.Tensor) -> torch.Tensor:
+    """The joints under each frame's forward map, on their own (``tsdf_transform_joints_hip`` of libtsdf_auggrid.so):
+    ``fma(A_i0, x, fma(A_i1, y, fma(A_i2, z, b_i)))`` in float64, rounded to float32 — bit-identical to the ``gt_aug``
+    :func:`voxelize_aug` ``(..., gt=)`` returns.  gt float32[n,3J] or [n,J,3] on the GPU, xforms float64[n,24]; the result
+    has gt's shape."""
+    G = _lib.load_auggrid()
+    _dev_check("gt", gt, torch.float32)
+    if gt.dim() < 2:
+        raise ValueError("gt must have shape [n, 3*J] or [n, J, 3]")
+    dev, n = gt.device, gt.shape[0]
+    nc = _coords("gt", gt, n)
+    _shaped("xforms", xforms, (n, 24), torch.float64, dev)
+    out = _out("gt_aug", None, tuple(gt.shape), torch.float32, dev)
+    if n:
+        _call(dev, G.tsdf_transform_joints_hip, [gt.data_ptr(), xforms.data_ptr(), n, nc // 3, None, out.data_ptr()], 4)
+    return out
+
+
+class ProcessAugBatch(NamedTuple):
+    points: torch.Tensor       # float64[n, P, 3]  the resampled clouds
+    tsdf: torch.Tensor         # float32[n, 3, R, R, R]
+    max_l: torch.Tensor        # float32[n]
+    mid_p: torch.Tensor        # float32[n, 3]
+    points_aug: torch.Tensor   # float64[n, P, 3]  the mapped clouds, resampled with their own draw
+    tsdf_aug: torch.Tensor     # float32[n, 3, R, R, R]  on the grid of points_aug
+    max_l_aug: torch.Tensor    # float32[n]
+    mid_p_aug: torch.Tensor    # float32[n, 3]
+    gt_aug: Optional[torch.Tensor]   # the joints under the map (gt's shape), or None without gt
+    status: torch.Tensor       # int32[n]  first non-zero status of the plain stages
+    status_aug: torch.Tensor   # int32[n]  first non-zero status of the augmented stages
+    count: torch.Tensor        # int32[n]  valid pixels of the frame
+    xforms: torch.Tensor       # float64[n, 24]  the maps that were used
+
+
+def process_batch_aug(depth: torch.Tensor, offsets: torch.Tensor, headers: torch.Tensor,
+                      xforms: Optional[torch.Tensor] = None, gt: Optional[torch.Tensor] = None, points: int = 6000,
+                      seed: int = 0, aug_seed: int = 0, key: int = 0, frame_base: int = 0, res: int = 32,
+                      layout: str = "czyx", cam: Optional[_lib.TsdfCam] = None) -> ProcessAugBatch:
+    """``DataProcess(aug=True).process()`` (pre/process.py:13-28) for n packed frames: the nine entries of the reference's
+    dictionary plus the bookkeeping, every stage on the current stream, no synchronisation, nothing on the host.
+
+    The plain half is :func:`process_batch` (``points, tsdf, max_l, mid_p, status, count`` equal it bit for bit).  The
+    augmented half (pre/process.py:19-24: data_aug, set_length, tsdf_f on the augmented resampled cloud):
+      1. ``xforms`` (float64[n,24]) or, when None, ``aug_xforms(mid_p, key=key, counter0=frame_base)``: every frame is turned
+         about its own plain cloud-grid centre, position i drawing from ``(key, frame_base + i)``;
+      2. ``points_aug = point_clouds(..., seed=aug_seed, frame_base=frame_base, xforms=xforms)``;
+      3. ``cloud_grids(points_aug)`` gives ``max_l_aug`` / ``mid_p_aug`` and the grid;
+      4. ``tsdf_aug = voxelize_aug_grid(..., xforms, grid)``;
+      5. ``gt_aug = transform_joints(gt, xforms)`` when ``gt`` (float32[n,3J] or [n,J,3]) is given.
+    ``status_aug`` is the first non-zero status among the augmented cloud, grid and volume stages.  A batch split over
+    several calls with ``frame_base`` gives the same result as one call."""
+    pb = process_batch(depth, offsets, headers, points=points, seed=seed, frame_base=frame_base, res=res, layout=layout,
+                       cam=cam)
+    if xforms is None:
+        xforms = aug_xforms(pb.mid_p, key=key, counter0=frame_base)
+    pa = point_clouds(depth, offsets, headers, points=points, seed=aug_seed, frame_base=frame_base, xforms=xforms, cam=cam)
+    cg = cloud_grids(pa.points, res=res, cam=cam)
+    tsdf_aug, st = voxelize_aug_grid(depth, offsets, headers, xforms, cg.grid, res=res, layout=layout, cam=cam)
+    status_aug = torch.where(pa.status != 0, pa.status, torch.where(cg.status != 0, cg.status, st))
+    gt_aug = transform_joints(gt, xforms) if gt is not None else None
+    return ProcessAugBatch(pb.points, pb.tsdf, pb.max_l, pb.mid_p, pa.points, tsdf_aug, cg.max_l, cg.mid_p, gt_aug,
+                           pb.status, status_aug, pb.count, xforms)

@@ -1,0 +1,339 @@
+"""CPU tier of the augmented voxelization on a caller-supplied grid (include/tsdf_auggrid.h): libtsdf_auggrid.so as far as
+it goes without a GPU — exports, version, argument checks before device work —, the refusals of the Python wrappers and of
+export.preprocess_tree(aug_placement=...), the soundness of the tests' own reference (tests/auggrid_ref.py) and the file
+handling of aug_placement="cloud" through its hook.  Nothing here touches a GPU."""
+import ctypes
+import importlib
+import os
+import re
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import auggrid_ref as ar  # noqa: E402
+import cloud_grid_ref as cg  # noqa: E402
+
+torch = pytest.importorskip("torch")
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+PKG = "handposeestimation-with-3d-cnns_amd"
+TOL = ar.TOL
+
+
+def declared_functions(header):
+    text = open(os.path.join(ROOT, "include", header)).read()
+    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
+    return sorted(set(re.findall(r"\b(tsdf_\w+)\s*\(", text)))
+
+
+def exported(path):
+    out = subprocess.run(["nm", "-D", "--defined-only", path], capture_output=True, text=True, check=True).stdout
+    rows = [ln.split() for ln in out.splitlines() if ln.strip()]
+    return sorted(r[-1] for r in rows if r[-2] in "TtWw"), sorted(r[-1] for r in rows if r[-1].startswith("tsdf_"))
+
+
+def test_library_exports_exactly_its_header(pkg):
+    want = ["tsdf_auggrid_version", "tsdf_transform_joints_hip", "tsdf_voxelize_aug_grid_hip"]
+    assert declared_functions("tsdf_auggrid.h") == want
+    funcs, named = exported(pkg._lib.AUGGRID_LIB_PATH)
+    assert funcs == want and named == want
+    G = pkg._lib.load_auggrid()
+    assert G.tsdf_auggrid_version() == 1 == pkg._lib.AUGGRID_VERSION
+    assert pkg._lib.load_auggrid() is G
+    assert pkg._lib.load().tsdf_version() == 7          # the product beside it is what it was
+    assert pkg.voxelize_aug_grid and pkg.transform_joints and pkg.process_batch_aug
+    assert pkg.ProcessAugBatch._fields == ("points", "tsdf", "max_l", "mid_p", "points_aug", "tsdf_aug", "max_l_aug",
+                                           "mid_p_aug", "gt_aug", "status", "status_aug", "count", "xforms")
+
+
+def test_missing_library_names_the_make_target(pkg, monkeypatch):
+    monkeypatch.setattr(pkg._lib, "_auggrid_lib", None)
+    monkeypatch.setattr(pkg._lib, "AUGGRID_LIB_PATH", os.path.join(ROOT, "build", "no_such_libtsdf_auggrid.so"))
+    with pytest.raises(ImportError, match="csrc auggrid"):
+        pkg._lib.load_auggrid()
+
+
+def test_argument_validation_happens_before_device_work(pkg):
+    G = pkg._lib.load_auggrid()
+    null, one, odd8, odd16 = ctypes.c_void_p(0), ctypes.c_void_p(64), ctypes.c_void_p(68), ctypes.c_void_p(72)
+    vox = G.tsdf_voxelize_aug_grid_hip
+
+    def call(depth=one, depth_len=100, offsets=one, headers=one, n=1, R=32, layout=0, xforms=one, grid=one, tsdf=one,
+             status=one):
+        return vox(depth, depth_len, offsets, headers, n, R, None, layout, null, xforms, grid, tsdf, status)
+
+    assert call(n=-1) == -1
+    for name in ("depth", "offsets", "headers", "xforms", "grid", "tsdf"):
+        assert call(**{name: null}) == -1, name
+    assert call(depth_len=-1) == -1
+    for R in (0, 2, 30, 33, 132, -32):
+        assert call(R=R) == -1, R
+    for layout in (-1, 2, 7):
+        assert call(layout=layout) == -1, layout
+    assert call(xforms=odd8) == -1            # not 8-byte aligned
+    assert call(tsdf=odd8) == -1              # not 16-byte aligned
+    assert call(tsdf=odd16) == -1             # 8-byte aligned only
+    # n == 0 is a no-op, whatever else is passed
+    assert call(n=0) == 0
+    assert vox(null, -5, null, null, 0, 31, None, 9, null, odd8, null, odd8, null) == 0
+
+    tj = G.tsdf_transform_joints_hip          # gt, xforms, n, n_joints, stream, out
+    assert tj(one, one, -1, 21, null, one) == -1
+    assert tj(null, one, 1, 21, null, one) == -1
+    assert tj(one, null, 1, 21, null, one) == -1
+    assert tj(one, one, 1, 21, null, null) == -1
+    assert tj(one, one, 1, 0, null, one) == -1
+    assert tj(one, one, 1, 171, null, one) == -1
+    assert tj(one, odd8, 1, 21, null, one) == -1
+    assert tj(null, odd8, 0, 0, null, null) == 0
+
+
+def test_wrappers_refuse_host_tensors_and_bad_modes_before_any_device(pkg, synth, tmp_path):
+    depth, off, hdr = (torch.from_numpy(x) for x in synth.synth_batch(2, "crop", seed0=3))
+    xf = torch.from_numpy(ar.identity_xforms(2))
+    grid = torch.zeros((2, 8), dtype=torch.float32)
+    with pytest.raises(ValueError, match="GPU"):
+        pkg.voxelize_aug_grid(depth, off, hdr, xf, grid)
+    with pytest.raises(ValueError):
+        pkg.voxelize_aug_grid(depth, off, hdr, xf, grid, layout="zyxc")
+    with pytest.raises(TypeError):
+        pkg.voxelize_aug_grid(depth.numpy(), off, hdr, xf, grid)
+    with pytest.raises(ValueError, match="GPU"):
+        pkg.transform_joints(torch.zeros((2, 63)), xf)
+    with pytest.raises(TypeError):
+        pkg.transform_joints(np.zeros((2, 63), np.float32), xf)
+    with pytest.raises(ValueError, match="GPU"):
+        pkg.process_batch_aug(depth, off, hdr)
+    with pytest.raises(ValueError):
+        pkg.process_batch_aug(depth, off, hdr, layout="bogus")
+
+    export = importlib.import_module(PKG + ".export")
+    db = str(tmp_path / "db")
+    synth.synth_msra_tree(db, n_sub=1, n_ges=1, n_frames=2, seed=1)
+
+    def never(*a, **k):
+        raise AssertionError("a hook ran although the arguments are refused")
+
+    hooks = dict(voxelize_fn=never, voxelize_aug_fn=never, voxelize_cloud_fn=never, voxelize_aug_cloud_fn=never)
+    for kw in (dict(aug_placement="points", aug=True), dict(aug_placement="Cloud", aug=True), dict(aug_placement=None),
+               dict(aug_placement="cloud", aug=False), dict(aug_placement="cloud", aug=True, point_clouds=False),
+               dict(aug_placement="cloud", aug=True, point_clouds=None)):
+        out = str(tmp_path / "refused")
+        with pytest.raises(ValueError):
+            export.preprocess_tree(db, out, res=4, **hooks, **kw)
+        assert not os.path.exists(out)                      # before anything is written
+    assert 'aug_placement="cloud"' in export.__doc__ and "it has no entry with a caller-supplied grid" not in export.__doc__
+
+
+@pytest.fixture(scope="module")
+def crops(pkg, synth):
+    """The 10 crops and their maps: random_affines about the plain grid centres, rng=5."""
+    import oracle
+
+    depth, off, hdr = synth.synth_batch(10, "crop", seed0=1200)
+    plain = oracle.voxelize(depth, off, hdr, R=32, want_tsdf=False)
+    assert not plain["status"].any()
+    xf = pkg.augment.random_affines(plain["mid_p"].astype(np.float64), rng=5)[0]
+    return depth, off, hdr, xf
+
+
+@pytest.mark.parametrize("R", [8, 12, 32])
+def test_helper_reproduces_the_fused_oracle_on_its_own_grid(crops, R):
+    import oracle
+
+    depth, off, hdr, xf = crops
+    grid, max_l, mid_p = ar.pixel_grids(depth, off, hdr, xf, R)
+    for layout in (0, 1):
+        want = oracle.voxelize_aug(depth, off, hdr, xf, R=R, layout=layout)
+        got, status = ar.voxelize_aug_grid_ref(depth, off, hdr, xf, grid, R, layout)
+        assert not status.any() and not want["status"].any()
+        assert np.array_equal(got.view(np.uint32), want["tsdf"].view(np.uint32))
+        assert np.array_equal(max_l, want["max_l"]) and np.array_equal(mid_p, want["mid_p"])
+    near, nonzero = ar.near_counts(got)
+    print(f"R={R}: fewest near voxels {near.min()}, fewest non-zero voxels {nonzero.min()}")
+    assert near.min() >= 100                      # the parity tests do not compare zeros
+    assert near.min() >= {8: 174, 12: 434, 32: 3262}[R] and nonzero.min() >= {8: 298, 12: 1044, 32: 19415}[R]
+
+
+@pytest.mark.parametrize("R", [8, 32])
+def test_helper_with_the_identity_map_is_the_plain_oracle(crops, R):
+    import oracle
+
+    depth, off, hdr, _ = crops
+    n = len(hdr)
+    plain = oracle.voxelize(depth, off, hdr, R=R, want_tsdf=False, extras=True)
+    grid = np.zeros((n, 8), np.float32)
+    grid[:, :3], grid[:, 3], grid[:, 4] = plain["ori"], plain["grid"][:, 4], plain["grid"][:, 5]
+    for layout in (0, 1):
+        got, status = ar.voxelize_aug_grid_ref(depth, off, hdr, ar.identity_xforms(n), grid, R, layout)
+        assert not status.any()
+        for i in range(n):
+            want = oracle.voxels(depth[off[i]:off[i + 1]], hdr[i], grid[i, :3], grid[i, 3], grid[i, 4], R=R, layout=layout)
+            assert np.array_equal(got[i] == 0, want == 0) and np.array_equal(np.signbit(got[i]), np.signbit(want))
+            assert np.array_equal(got[i, 2].view(np.uint32), want[2].view(np.uint32))
+            assert np.abs(got[i, :2] - want[:2]).max() <= TOL
+
+
+def test_helper_status_rules(crops):
+    depth, off, hdr, xf = crops
+    depth, off, hdr, xf = depth[:off[4]], off[:5].copy(), hdr[:4].copy(), xf[:4]
+    grid = ar.pixel_grids(depth, off, hdr, xf, 8)[0]
+    rows = np.repeat(grid[:1], 6, axis=0)
+    rows[1] = 0
+    rows[2, 4] = -1
+    rows[3, 1] = np.inf
+    rows[4, 3] = np.nan
+    rows[5, 4] = np.inf
+    assert [ar.grid_ok(r) for r in rows] == [True, False, False, False, False, False]
+    bad = hdr.copy()
+    bad[1, 4] = bad[1, 2]                                            # right == left
+    t, st = ar.voxelize_aug_grid_ref(depth, off, bad, xf, grid, 8, "czyx", depth_len=off[3])   # frame 3 outside
+    assert list(st) == [0, 2, 0, 2] and not t[[1, 3]].any() and t[0].any() and t[2].any()
+    g2 = grid.copy()
+    g2[2] = 0
+    t2, st = ar.voxelize_aug_grid_ref(depth, off, hdr, xf, g2, 8, "czyx")
+    assert list(st) == [0, 0, 1, 0] and not t2[2].any() and np.array_equal(t2[0], t[0])
+
+
+def _files(root):
+    out = {}
+    for dp, _, fs in os.walk(root):
+        for f in fs:
+            out[os.path.relpath(os.path.join(dp, f), root)] = open(os.path.join(dp, f), "rb").read()
+    return out
+
+
+def _same_file(name, a, b, tmp):
+    """npy files byte for byte; npz archives (their members carry time stamps) array for array."""
+    if not name.endswith(".npz"):
+        return a == b
+    pa, pb = os.path.join(tmp, "a.npz"), os.path.join(tmp, "b.npz")
+    open(pa, "wb").write(a)
+    open(pb, "wb").write(b)
+    za, zb = np.load(pa), np.load(pb)
+    return sorted(za.files) == sorted(zb.files) and all(
+        za[k].dtype == zb[k].dtype and za[k].tobytes() == zb[k].tobytes() for k in za.files)
+
+
+def _hooks():
+    import oracle
+
+    lay = {"czyx": 0, "cxyz": 1}
+
+    def vox(pk, res, layout, device):
+        r = oracle.voxelize(pk.depth, pk.offsets, pk.headers, R=res, layout=lay[layout])
+        return r["tsdf"], r["max_l"], r["mid_p"], r["status"]
+
+    def vox_aug(pk, xf, gt, res, layout, device):
+        r = oracle.voxelize_aug(pk.depth, pk.offsets, pk.headers, xf, R=res, layout=lay[layout])
+        return r["tsdf"], r["max_l"], r["mid_p"], r["status"], oracle.transform_joints(gt, xf)
+
+    def vox_cloud(pk, cloud, res, layout, device):
+        grid, max_l, mid_p, _, status = cg.cloud_grids(cloud, R=res)
+        tsdf = np.zeros((len(pk), 3, res, res, res), np.float32)
+        for i in range(len(pk)):
+            if status[i] == 0:
+                h, d = pk.frame(i)
+                tsdf[i] = oracle.voxels(d, h, grid[i, :3], grid[i, 3], grid[i, 4], R=res, layout=lay[layout])
+        return tsdf, max_l, mid_p, status
+
+    calls = []
+
+    def vox_aug_cloud(pk, xf, cloud_aug, gt, res, layout, device):
+        grid, max_l, mid_p, _, status = cg.cloud_grids(cloud_aug, R=res)
+        tsdf, st = ar.voxelize_aug_grid_ref(pk.depth, pk.offsets, pk.headers, xf, grid, res, layout)
+        status = np.where(status != 0, status, st).astype(np.int32)
+        ret = (tsdf, max_l, mid_p, status, oracle.transform_joints(np.asarray(gt, np.float32).reshape(len(pk), -1), xf))
+        calls.append((np.array(xf), np.array(cloud_aug), ret))
+        return ret
+    return vox, vox_aug, vox_cloud, vox_aug_cloud, calls
+
+
+def test_preprocess_tree_aug_placement_cloud_through_the_hooks(pkg, synth, tmp_path):
+    export = importlib.import_module(PKG + ".export")
+    db = str(tmp_path / "db")
+    synth.synth_msra_tree(db, n_sub=2, n_ges=2, n_frames=3, seed=4)
+    vox, vox_aug, vox_cloud, vox_aug_cloud, calls = _hooks()
+    old = dict(res=8, points_num=200, voxelize_fn=vox, voxelize_aug_fn=vox_aug, voxelize_cloud_fn=vox_cloud, aug=True)
+    new = dict(old, voxelize_aug_cloud_fn=vox_aug_cloud)
+    dirs = {k: str(tmp_path / k) for k in ("today", "pixels", "cloud", "today_pc", "cloud_pc")}
+    rngs = {}
+
+    def run(name, **kw):
+        rngs[name] = (np.random.default_rng(7), np.random.default_rng(8))
+        export.preprocess_tree(db, dirs[name], rng=rngs[name][0], aug_rng=rngs[name][1], **kw)
+
+    run("today", **old)                                         # the call as it was
+    run("pixels", aug_placement="pixels", **new)
+    assert not calls                                            # the new hook is for aug_placement="cloud" only
+    run("cloud", aug_placement="cloud", **new)
+    assert len(calls) == 4
+    run("today_pc", placement="cloud", **old)                   # the two switches are independent
+    run("cloud_pc", placement="cloud", aug_placement="cloud", **new)
+    assert len(calls) == 8
+    files = {k: _files(v) for k, v in dirs.items()}
+    scratch = str(tmp_path)
+    assert all(sorted(files[k]) == sorted(files["today"]) for k in files)
+    # aug_placement="pixels" is today's output, file for file
+    assert all(_same_file(k, files["today"][k], files["pixels"][k], scratch) for k in files["today"])
+    # both generators were consumed identically in every mode
+    for name in ("pixels", "cloud", "today_pc", "cloud_pc"):
+        for a, b in zip(rngs[name], rngs["today"]):
+            assert a.bit_generator.state == b.bit_generator.state, name
+    # with "cloud" only TSDF_aug differs: plain files, clouds, labels and counts are those of the run without it
+    for mode, base in (("cloud", "today"), ("cloud_pc", "today_pc")):
+        for k in files[mode]:
+            if k.startswith("data_num") or k.split(os.sep)[1] != "TSDF_aug":
+                assert _same_file(k, files[mode][k], files[base][k], scratch), (mode, k)
+    differ = 0
+    for mode, first in (("cloud", 0), ("cloud_pc", 4)):
+        k = first
+        for s in ("P0", "P1"):
+            for g in ("1", "2"):
+                xf, cloud_aug, (tsdf, max_l, mid_p, status, gt_aug) = calls[k]
+                k += 1
+                sub = os.path.join(dirs[mode], s)
+                # the hook was handed the cloud that ends up in Point_Cloud_aug, and the maps that are stored
+                saved = np.load(os.path.join(sub, "Point_Cloud_aug", g + ".npy"))
+                assert saved.shape == (3, 200, 3) and np.array_equal(saved, cloud_aug)
+                z = np.load(os.path.join(sub, "TSDF_aug", g + ".npz"))
+                assert np.array_equal(z["xform"], xf)
+                # the files hold what the hook returned ...
+                assert z["tsdf"].dtype == np.float32 and np.array_equal(z["tsdf"], tsdf) and z["tsdf"].any()
+                assert np.array_equal(z["max_l"], max_l) and np.array_equal(z["mid_p"], mid_p)
+                assert np.array_equal(z["status"], status) and not status.any()
+                assert np.array_equal(np.load(os.path.join(sub, "ground_truth_aug", g + ".npy")), gt_aug)
+                # ... which is a function of the saved cloud
+                _, ml, mp, _, _ = cg.cloud_grids(saved, R=8)
+                assert np.array_equal(z["max_l"], ml) and np.array_equal(z["mid_p"], mp)
+                zp = np.load(os.path.join(dirs["today"], s, "TSDF_aug", g + ".npz"))
+                differ += int((z["max_l"] != zp["max_l"]).sum())
+    assert differ > 0                                           # frames with more than 200 valid pixels
+
+
+def test_preprocess_tree_aug_placement_cloud_feeds_the_pca_fit(pkg, synth, tmp_path):
+    export = importlib.import_module(PKG + ".export")
+    pca = importlib.import_module(PKG + ".pca")
+    db = str(tmp_path / "db")
+    synth.synth_msra_tree(db, n_sub=2, n_ges=1, n_frames=40, seed=2)
+    vox, vox_aug, vox_cloud, vox_aug_cloud, calls = _hooks()
+    out, pdir = str(tmp_path / "out"), str(tmp_path / "pca")
+    export.preprocess_tree(db, out, res=4, points_num=100, voxelize_fn=vox, voxelize_aug_cloud_fn=vox_aug_cloud, aug=True,
+                           aug_placement="cloud", rng=np.random.default_rng(1), aug_rng=np.random.default_rng(2),
+                           pca_dir=pdir)
+    labels = {}
+    for s in ("P0", "P1"):
+        z, za = (np.load(os.path.join(out, s, d, "1.npz")) for d in ("TSDF", "TSDF_aug"))
+        gt, gta = (np.load(os.path.join(out, s, d, "1.npy")) for d in ("ground_truth", "ground_truth_aug"))
+        labels[s] = [pca.normalize_labels_np(gt, z["max_l"], z["mid_p"])[z["status"] == 0],
+                     pca.normalize_labels_np(gta, za["max_l"], za["mid_p"])[za["status"] == 0]]
+    for t, other in enumerate(("P1", "P0")):
+        want = pca.fit_labels(np.concatenate(labels[other]), fold=t, aug=True)
+        got = np.load(os.path.join(pdir, "%d-aug.npz" % t))
+        ref_path = str(tmp_path / "want")
+        want.save(ref_path)
+        ref = np.load(os.path.join(ref_path, "%d-aug.npz" % t))
+        assert sorted(got.files) == sorted(ref.files) and all(np.array_equal(got[k], ref[k]) for k in got.files)
