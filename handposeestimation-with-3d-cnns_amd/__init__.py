@@ -19,6 +19,9 @@ The reference's process(), batched:      cloud_grids (grid placed on a cloud's e
                                          cloud_grids -> voxelize_grid)
 ... and its augmented half:              voxelize_aug_grid (the augmented voxelizer on a caller-supplied grid), transform_joints
                                          (libtsdf_auggrid.so, include/tsdf_auggrid.h), process_batch_aug
+Packs with 16-bit depth:                 packing.depth16_shift, PackedFrames.to_depth16 / to_float32 (TSDFPK02, lossless or
+                                         refused), widen_depth16 (libtsdf_depth16.so, include/tsdf_depth16.h); the loaders
+                                         upload uint16 and widen on the GPU
 """
 from . import _lib  # noqa: F401
 from ._lib import TsdfCam, TsdfError, default_cam  # noqa: F401
@@ -27,7 +30,7 @@ from .voxelize import (AabbBatch, AugmentedStep, CloudGridBatch, PointCloudBatch
                        aug_state, aug_xforms, aug_xforms_at, cloud_grids, denormalize_joints, empty_batch,
                        frames_within, joints_within, normalize_joints, point_clouds, pose_error, process_batch, process_batch_aug,
                        project_joints, release_stream, transform_joints, voxel_pixels, voxelize_aug_grid,
-                       voxelize, voxelize_aug, voxelize_grid, voxelize_indexed, voxelize_labels)
+                       voxelize, voxelize_aug, voxelize_grid, voxelize_indexed, voxelize_labels, widen_depth16)
 from .pca import JointPCA, fit_joint_pca  # noqa: F401
 from . import augment, dataset, export, packing, pca, shard, synth  # noqa: F401
 from .dataset import MSRA_Dataset, MSRADepthDataset, ResidentLoader, VoxelBatch, VoxelLoader  # noqa: F401
@@ -41,4 +44,4 @@ __all__ = ["voxelize", "voxelize_labels", "voxelize_indexed", "ResidentLoader", 
            "pca", "JointPCA", "fit_joint_pca", "project_joints", "pose_error", "PoseError", "joints_within", "frames_within",
            "point_clouds", "PointCloudBatch", "cloud_grids", "CloudGridBatch", "process_batch", "ProcessBatch", "aug_xforms",
            "aug_xforms_at", "aug_state", "AugmentedStep", "voxelize_aug_grid", "transform_joints", "process_batch_aug",
-           "ProcessAugBatch"]
+           "ProcessAugBatch", "widen_depth16"]

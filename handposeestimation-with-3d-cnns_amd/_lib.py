@@ -100,11 +100,18 @@ AUGSTEP_VERSION = 1
 AUGGRID_LIB_PATH = os.path.join(_HERE, "libtsdf_auggrid.so")
 AUGGRID_VERSION = 1
 
+# The extension library of include/tsdf_depth16.h (make -C csrc depth16): 16-bit depth (packing.py, TSDFPK02 packs) widened
+# to the float32 buffer the voxelizer reads, and the 16-bit twin of the host gather.  A binary of its own once more.
+DEPTH16_LIB_PATH = os.path.join(_HERE, "libtsdf_depth16.so")
+DEPTH16_VERSION = 1
+DEPTH16_MAX_SHIFT = 7   # TSDF_DEPTH16_MAX_SHIFT of include/tsdf_depth16.h
+
 _lib = None
 _debug_lib = None
 _augment_lib = None
 _augstep_lib = None
 _auggrid_lib = None
+_depth16_lib = None
 
 
 def _bind(L, path: str, debug: bool = False):
@@ -254,6 +261,31 @@ def load_auggrid():
     # gt, xforms, n, n_joints, stream, gt_aug
     L.tsdf_transform_joints_hip.argtypes = [vp, vp, i, i, vp, vp]
     _auggrid_lib = L
+    return L
+
+
+def load_depth16():
+    """Load libtsdf_depth16.so once and declare its two entry points; raise loudly if it is not there."""
+    global _depth16_lib
+    if _depth16_lib is not None:
+        return _depth16_lib
+    if not os.path.exists(DEPTH16_LIB_PATH):
+        raise ImportError(f"{DEPTH16_LIB_PATH} not found: build it with `make -C handposeestimation-with-3d-cnns_amd/csrc "
+                          "depth16` (__graft_entry__.build() does). There is no CPU fallback.")
+    L = ctypes.CDLL(DEPTH16_LIB_PATH)
+    L.tsdf_depth16_version.restype = ctypes.c_int
+    L.tsdf_depth16_version.argtypes = []
+    if L.tsdf_depth16_version() != DEPTH16_VERSION:
+        raise ImportError(f"{DEPTH16_LIB_PATH} has version {L.tsdf_depth16_version()}, this package needs "
+                          f"{DEPTH16_VERSION}: rebuild it")
+    vp, i, i64 = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64
+    L.tsdf_depth16_widen_hip.restype = i
+    # src, n_px, shift, dst, stream
+    L.tsdf_depth16_widen_hip.argtypes = [vp, i64, i, vp, vp]
+    L.tsdf_depth16_host_gather.restype = i
+    # src, src_len, src_offsets, n_src, index, n, dst, dst_len, dst_offsets, n_threads
+    L.tsdf_depth16_host_gather.argtypes = [vp, i64, vp, i64, vp, i64, vp, i64, vp, i]
+    _depth16_lib = L
     return L
 
 

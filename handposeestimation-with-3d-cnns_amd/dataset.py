@@ -37,7 +37,18 @@ import torch.utils.data as data
 
 from . import packing, shard
 from .voxelize import (TsdfBatch, aug_xforms, denormalize_joints, empty_batch, normalize_joints, voxelize,  # noqa: F401
-                       voxelize_indexed, voxelize_labels)
+                       voxelize_indexed, voxelize_labels, widen_depth16)
+
+
+def _common_depth_shift(packs: Sequence[packing.PackedFrames]) -> Optional[int]:
+    """The one ``depth_shift`` of a dataset's packs (None: float32 depth).  Packs of different forms or shifts are
+    refused: a batch is one buffer with one scale."""
+    forms = sorted({-1 if pk.depth_shift is None else int(pk.depth_shift) for pk in packs})
+    if len(forms) > 1:
+        names = ", ".join("float32" if f < 0 else f"16-bit with shift {f}" for f in forms)
+        raise ValueError(f"the packs of one dataset must share one depth form, these are {names}: repack them "
+                         "(packing.pack_tree(..., depth16=None) or one forced shift, overwrite=True)")
+    return None if not forms or forms[0] < 0 else forms[0]
 
 
 def _subset(size: str) -> Tuple[int, int]:
@@ -111,6 +122,7 @@ class MSRADepthDataset(data.Dataset):
                     bin_num, gt = packing.read_joint(g_dir)
                     self.paths += packing.gesture_bin_paths(g_dir, bin_num)
                     gts.append(gt)
+        self.depth_shift = _common_depth_shift(self.packs)   # None: float32 depth; k: every pack holds uint16 * 2^-k
         self.ground_truth = np.concatenate(gts) if gts else np.zeros((0, 63), np.float32)
 
     @classmethod
@@ -119,6 +131,7 @@ class MSRADepthDataset(data.Dataset):
         self = cls.__new__(cls)
         self.root_path, self.train, self.test_idx, self.subjects, self.paths = None, True, -1, [], []
         self.packs = list(packs)
+        self.depth_shift = _common_depth_shift(self.packs)
         self._pack_of = np.concatenate([np.full(len(pk), k, np.int32) for k, pk in enumerate(self.packs)])
         self._local = np.concatenate([np.arange(len(pk), dtype=np.int64) for pk in self.packs])
         self.ground_truth = np.concatenate([np.asarray(pk.gt) if pk.gt is not None else np.zeros((len(pk), 63), np.float32)
@@ -153,15 +166,15 @@ class MSRADepthDataset(data.Dataset):
     def pin_packs(self, limit_bytes: int = 32 << 30) -> bool:
         """Page-lock the packs' depth payloads (if they fit ``limit_bytes``) so that contiguous batches upload
         without a staging copy.  Returns whether the packs are pinned."""
-        if not self.packed or sum(int(pk.depth.size) * 4 for pk in self.packs) > limit_bytes:
+        if not self.packed or sum(int(pk.depth.nbytes) for pk in self.packs) > limit_bytes:
             return False
         for pk in self.packs:
             pk.pin()
         return True
 
     def contiguous_source(self, idx: np.ndarray):
-        """(pinned float32 tensor slice, PackedFrames view) when ``idx`` is a run of consecutive frames of one
-        pinned pack, else None."""
+        """(pinned tensor slice — float32, or uint16 over 16-bit packs —, PackedFrames view) when ``idx`` is a run of
+        consecutive frames of one pinned pack, else None."""
         idx = np.asarray(idx, np.int64)
         if not self.packed or idx.size == 0 or not (np.diff(idx) == 1).all():
             return None
@@ -175,8 +188,9 @@ class MSRADepthDataset(data.Dataset):
         return pk._pinned[int(pk.offsets[a]):int(pk.offsets[b])], view
 
     def take(self, idx: np.ndarray, depth_out: Optional[np.ndarray] = None) -> packing.PackedFrames:
-        """Frames ``idx`` as one packed batch (with labels).  Packed datasets gather straight from the memory
-        maps (one slice when the indices are consecutive inside a subject); otherwise the files are read."""
+        """Frames ``idx`` as one packed batch (with labels) in the dataset's depth form: uint16 over 16-bit packs
+        (``depth_out`` is then uint16 too), else float32.  Packed datasets gather straight from the memory maps (one slice
+        when the indices are consecutive inside a subject); otherwise the files are read."""
         idx = np.asarray(idx, np.int64)
         if self.packed and idx.size:
             ks = self._pack_of[idx]
@@ -184,6 +198,17 @@ class MSRADepthDataset(data.Dataset):
                 out = self.packs[int(ks[0])].take(self._local[idx], depth_out)
                 out.gt = self.ground_truth[idx]
                 return out
+            if self.depth_shift is not None:   # frames of several 16-bit packs (they share the shift): stay in 16 bits
+                raw = [self.packs[int(k)].raw_frame(int(l)) for k, l in zip(ks, self._local[idx])]
+                off = np.zeros(idx.size + 1, np.int64)
+                np.cumsum([d.size for _, d in raw], out=off[1:])
+                if depth_out is not None and depth_out.dtype != np.uint16:
+                    raise TypeError(f"depth_out is {depth_out.dtype}, the dataset's packs hold uint16 depth")
+                depth = depth_out[: off[-1]] if depth_out is not None else np.empty(int(off[-1]), np.uint16)
+                for k, (_, d) in enumerate(raw):
+                    depth[off[k]:off[k + 1]] = d
+                return packing.PackedFrames(depth, off, np.stack([np.asarray(h) for h, _ in raw]), self.ground_truth[idx],
+                                            depth_shift=self.depth_shift)
             pk = packing.pack_frames(self.packs[int(k)].frame(int(l)) for k, l in zip(ks, self._local[idx]))
             if depth_out is not None:
                 depth_out[: pk.depth.size] = pk.depth
@@ -283,8 +308,11 @@ def plan_batches(n: int, batch_size: int, rank: int = 0, world: int = 1, shuffle
 class _Staging:
     """One reusable set of pinned host buffers + device input tensors for a batch (two of them alternate)."""
 
-    def __init__(self, max_px: int, bs: int, device, with_gt: bool):
-        self.h_depth = torch.empty(max_px, dtype=torch.float32).pin_memory()
+    def __init__(self, max_px: int, bs: int, device, with_gt: bool, depth16: bool = False):
+        # over 16-bit packs the pinned buffer and the upload's target are uint16 (half the bytes over the link); the widen
+        # launch that follows the copy on the copy stream fills d_depth, and everything downstream is what it always was
+        self.h_depth = torch.empty(max_px, dtype=torch.uint16 if depth16 else torch.float32).pin_memory()
+        self.d_depth16 = torch.empty(max_px, dtype=torch.uint16, device=device) if depth16 else None
         self.h_off = torch.empty(bs + 1, dtype=torch.int64).pin_memory()
         self.h_hdr = torch.empty((bs, 6), dtype=torch.int32).pin_memory()
         self.h_gt = torch.empty((bs, 63), dtype=torch.float32).pin_memory() if with_gt else None
@@ -343,10 +371,12 @@ class VoxelLoader:
         batches = self._batches()
         self.epoch += 1
         if self._sets is None:
-            self._sets = [_Staging(self.max_px, self.bs, self.device, True) for _ in range(2)]
+            self._sets = [_Staging(self.max_px, self.bs, self.device, True, getattr(self.ds, "depth_shift", None) is not None)
+                          for _ in range(2)]
             if self.pin_packs:
                 self.ds.pin_packs()
         sets = self._sets
+        shift = getattr(self.ds, "depth_shift", None)   # 16-bit packs: upload uint16, widen on the copy stream
         for s in sets:
             if s.used:
                 s.consumed.synchronize()   # an abandoned previous epoch may still be reading this set
@@ -404,7 +434,11 @@ class VoxelLoader:
                 with torch.cuda.stream(copy_stream):
                     if k >= 2:
                         copy_stream.wait_event(s.consumed)   # the kernels that read this device set are done
-                    s.d_depth[:npx].copy_(s.src, non_blocking=True)
+                    if shift is None:
+                        s.d_depth[:npx].copy_(s.src, non_blocking=True)
+                    else:   # the one H2D copy at half the bytes, then the widen into d_depth, both on the copy stream
+                        s.d_depth16[:npx].copy_(s.src, non_blocking=True)
+                        widen_depth16(s.d_depth16[:npx], shift, out=s.d_depth[:npx])
                     s.copied.record(copy_stream)
                 cur.wait_event(s.copied)
                 # one launch: volumes, max_l / mid_p, normalised labels and the labels' device copy (which outlives the set)
@@ -438,7 +472,13 @@ class ResidentPacks:
         with warnings.catch_warnings():      # (a memory-mapped pack is read-only: torch warns, and we only read)
             warnings.simplefilter("ignore", UserWarning)
             for k, pk in enumerate(packs):   # (a memory-mapped pack is read here, once)
-                self.depth[int(pbase[k]):int(pbase[k + 1])].copy_(torch.from_numpy(np.ascontiguousarray(pk.depth)))
+                dst = self.depth[int(pbase[k]):int(pbase[k + 1])]
+                if pk.depth_shift is None:
+                    dst.copy_(torch.from_numpy(np.ascontiguousarray(pk.depth)))
+                else:   # a 16-bit pack goes up as uint16 and is widened into its slice; the temporary is then dropped
+                    tmp = torch.from_numpy(np.ascontiguousarray(pk.depth)).to(self.depth.device)
+                    widen_depth16(tmp, pk.depth_shift, out=dst)
+                    del tmp
         off = np.concatenate([np.asarray(pk.offsets[:-1], np.int64) + pbase[k] for k, pk in enumerate(packs)]
                              + [pbase[-1:]])
         hdr = np.concatenate([np.asarray(pk.headers, np.int32).reshape(-1, 6) for pk in packs])

@@ -27,7 +27,15 @@ HEADER_INTS = 6
 #   64  headers int32[n,6] | offsets int64[n+1] | gt float32[n,gt_cols] | group_start int64[n_groups+1] |
 #       group names (utf-8, '\n'-joined, length-prefixed int64) | depth float32[n_px]
 # "groups" are the gestures of a subject in file order (group_start[g] .. group_start[g+1] are its frames).
+#
+# A 16-bit pack ("TSDFPK02") has the same layout with the depth array as uint16[n_px]: q = depth * 2^k with ONE shift k in
+# 0..7 per pack; the first reserved header word is the payload code (0: float32, 1: uint16), the second is k.  Decoding is
+# float32(q) * float32(2^-k); both steps are exact in float32, and a pack is only ever encoded when the decoded value
+# equals the float32 depth bit for bit (depth16_shift, PackedFrames.to_depth16) — the format is lossless or refused.
 PACK_MAGIC = b"TSDFPK01"
+PACK_MAGIC16 = b"TSDFPK02"
+PAYLOAD_F32, PAYLOAD_U16 = 0, 1
+MAX_DEPTH_SHIFT = 7
 _ALIGN = 64
 
 
@@ -47,24 +55,27 @@ _GATHER_THREADS = _gather_threads()
 
 def _native_gather(pk, idx: np.ndarray, out: np.ndarray, off: np.ndarray) -> bool:
     """The shuffled-batch gather by ``tsdf_host_gather_frames`` (threads, one memcpy per frame instead of one numpy slice
-    assignment per frame: ~10 us of interpreter each).  False when the library is not built or the arrays are not plain
-    float32 / int64 memory — the caller then copies frame by frame in numpy.  Host memory only: not a compute path."""
+    assignment per frame: ~10 us of interpreter each) or, for a 16-bit pack, by its twin ``tsdf_depth16_host_gather``.
+    False when the library is not built or the arrays are not plain float32 (uint16) / int64 memory of ONE payload type —
+    the caller then copies frame by frame in numpy.  Host memory only: not a compute path."""
     if idx.size < 4:
+        return False
+    src, so = pk.depth, pk.offsets
+    dtype = np.dtype(np.float32 if pk.depth_shift is None else np.uint16)   # (never reinterpret one as the other)
+    if not (isinstance(src, np.ndarray) and src.dtype == dtype and src.flags.c_contiguous
+            and isinstance(so, np.ndarray) and so.dtype == np.int64 and so.flags.c_contiguous
+            and out.dtype == dtype and out.flags.c_contiguous and out.flags.writeable):
         return False
     try:
         from . import _lib
-        L = _lib.load()
+        fn = _lib.load().tsdf_host_gather_frames_n if pk.depth_shift is None else \
+            _lib.load_depth16().tsdf_depth16_host_gather
     except (ImportError, OSError):
-        return False
-    src, so = pk.depth, pk.offsets
-    if not (isinstance(src, np.ndarray) and src.dtype == np.float32 and src.flags.c_contiguous
-            and isinstance(so, np.ndarray) and so.dtype == np.int64 and so.flags.c_contiguous
-            and out.dtype == np.float32 and out.flags.c_contiguous and out.flags.writeable):
         return False
     idx = np.ascontiguousarray(idx, np.int64)
     off2 = np.empty_like(off)
-    rc = L.tsdf_host_gather_frames_n(src.ctypes.data, src.size, so.ctypes.data, so.size - 1, idx.ctypes.data, idx.size,
-                                     out.ctypes.data, out.size, off2.ctypes.data, _GATHER_THREADS)
+    rc = fn(src.ctypes.data, src.size, so.ctypes.data, so.size - 1, idx.ctypes.data, idx.size,
+            out.ctypes.data, out.size, off2.ctypes.data, _GATHER_THREADS)
     if rc != 0:
         raise ValueError("pack offsets do not describe its depth payload (damaged pack?)")
     return bool((off2 == off).all())
@@ -72,6 +83,47 @@ def _native_gather(pk, idx: np.ndarray, out: np.ndarray, off: np.ndarray) -> boo
 
 def _pad(n: int) -> int:
     return (n + _ALIGN - 1) // _ALIGN * _ALIGN
+
+
+# ---- the 16-bit depth encoding ----------------------------------------------------------------------------------------
+_CHUNK = 1 << 22   # elements per pass of the checks below (a subject's pack is ~10^8 pixels)
+
+
+def _check_shift(shift) -> int:
+    if isinstance(shift, (bool, np.bool_)) or not isinstance(shift, (int, np.integer)) or \
+            not 0 <= int(shift) <= MAX_DEPTH_SHIFT:
+        raise ValueError(f"a depth shift is an integer in 0..{MAX_DEPTH_SHIFT}, got {shift!r}")
+    return int(shift)
+
+
+def _encodable(d: np.ndarray, k: int) -> np.ndarray:
+    """Which float32 values are exactly ``q * 2^-k`` for a uint16 q: finite, sign bit clear (-0.0 would come back as
+    +0.0), ``d * 2^k`` an integer (the product by a power of two is exact) and at most 65535."""
+    with np.errstate(over="ignore", invalid="ignore"):
+        s = d * np.float32(1 << k)
+        return np.isfinite(d) & ~np.signbit(d) & (s == np.floor(s)) & (s <= np.float32(65535.0))
+
+
+def depth16_shift(depth) -> Optional[int]:
+    """The smallest shift k in 0..7 for which EVERY value of ``depth`` (float32) is exactly representable as
+    ``uint16 * 2^-k``, or None when there is none: a negative, NaN or infinite depth, a fraction finer than 1/128 mm, or
+    a value too large for the k its neighbours need.  Whole millimetres up to 65535 give 0."""
+    d = np.ascontiguousarray(depth, np.float32).reshape(-1)
+    k = 0
+    for a in range(0, d.size, _CHUNK):
+        c = d[a:a + _CHUNK]
+        while not _encodable(c, k).all():   # (a value that fits at k may exceed 65535 at k + 1: no chunk is skipped, and
+            k += 1                          # the final pass below checks the chunks that were seen at a smaller k)
+            if k > MAX_DEPTH_SHIFT:
+                return None
+    if k and not all(_encodable(d[a:a + _CHUNK], k).all() for a in range(0, d.size, _CHUNK)):
+        return None   # integers at k, but some value * 2^k leaves uint16 — and a larger k only makes that worse
+    return k
+
+
+def decode_depth16(q: np.ndarray, shift: int) -> np.ndarray:
+    """uint16 payload -> float32 depth: ``float32(q) * float32(2^-shift)`` (exact)."""
+    return np.asarray(q).astype(np.float32) * np.float32(2.0 ** -int(shift))
 
 
 def read_bin(f_name: str) -> Tuple[np.ndarray, np.ndarray]:
@@ -124,9 +176,61 @@ class PackedFrames:
     gt: Optional[np.ndarray] = None            # float32[n, 63] labels (joint.txt rows), when known
     group_start: Optional[np.ndarray] = None   # int64[g+1]: frame ranges of the gestures, when packed from a tree
     group_names: Optional[List[str]] = None
+    depth_shift: Optional[int] = None          # None: depth is float32; k: depth is uint16, the value is depth * 2^-k
 
     def __len__(self) -> int:
         return int(self.headers.shape[0])
+
+    # ---- the 16-bit form ----
+    def depth_f32(self) -> np.ndarray:
+        """The depth payload as float32, whatever the form: THE decode every reader of a pack's pixels goes through (a
+        float32 pack hands out its own array)."""
+        return self.depth if self.depth_shift is None else decode_depth16(self.depth, self.depth_shift)
+
+    def _like(self, depth: np.ndarray, shift: Optional[int]) -> "PackedFrames":
+        return PackedFrames(depth, self.offsets, self.headers, self.gt, self.group_start, self.group_names, shift)
+
+    def _locate(self, px: int) -> Tuple[int, int]:
+        f = int(np.searchsorted(np.asarray(self.offsets), px, side="right")) - 1
+        return f, px - int(self.offsets[f])
+
+    def to_depth16(self, shift: Optional[int] = None) -> "PackedFrames":
+        """The same frames with the depth as ``uint16 * 2^-shift`` (``shift=None``: the smallest exact shift,
+        :func:`depth16_shift`).  Lossless or refused: ValueError names the first frame and pixel that cannot be encoded."""
+        if self.depth_shift is not None:
+            return self if shift is None or _check_shift(shift) == self.depth_shift else self.to_float32().to_depth16(shift)
+        d = np.ascontiguousarray(self.depth, np.float32).reshape(-1)
+        k = depth16_shift(d) if shift is None else _check_shift(shift)
+        why, bad = "", np.zeros(0, bool)
+        if k is None:   # no shift serves every pixel: name a pixel no shift serves, else the first one too large for the rest
+            k = MAX_DEPTH_SHIFT
+            with np.errstate(over="ignore", invalid="ignore"):
+                s7 = d * np.float32(1 << MAX_DEPTH_SHIFT)
+                bad = ~(np.isfinite(d) & ~np.signbit(d) & (s7 == np.floor(s7)) & (d <= np.float32(65535.0)))
+                if not bad.any():
+                    k = next(j for j in range(MAX_DEPTH_SHIFT + 1)
+                             if (d * np.float32(1 << j) == np.floor(d * np.float32(1 << j))).all())
+                    bad = ~_encodable(d, k)
+                    why = f" (other pixels of the pack need shift {k})"
+        else:
+            for a in range(0, d.size, _CHUNK):
+                m = ~_encodable(d[a:a + _CHUNK], k)
+                if m.any():
+                    bad = np.concatenate([np.zeros(a, bool), m])
+                    break
+        if bad.any():
+            px = int(np.argmax(bad))
+            f, j = self._locate(px)
+            raise ValueError(f"frame {f}, pixel {j}: depth {float(d[px])!r} is not a uint16 times 2^-{k}{why}; "
+                             "the pack stays float32 (16-bit packs are lossless or refused)")
+        q = (d * np.float32(1 << k)).astype(np.uint16)
+        if not np.array_equal(decode_depth16(q, k).view(np.uint32), d.view(np.uint32)):
+            raise ValueError("the 16-bit encoding does not decode to the same float32 bits")   # (cannot happen)
+        return self._like(q, k)
+
+    def to_float32(self) -> "PackedFrames":
+        """The inverse of :meth:`to_depth16` (a float32 pack returns itself)."""
+        return self if self.depth_shift is None else self._like(self.depth_f32(), None)
 
     @property
     def pixels(self) -> np.ndarray:
@@ -138,12 +242,16 @@ class PackedFrames:
         a, b = int(a), int(b)
         off = self.offsets[a:b + 1] - self.offsets[a]
         return PackedFrames(self.depth[self.offsets[a]:self.offsets[b]], off.astype(np.int64),
-                            self.headers[a:b], None if self.gt is None else self.gt[a:b])
+                            self.headers[a:b], None if self.gt is None else self.gt[a:b], depth_shift=self.depth_shift)
 
     def take(self, idx: np.ndarray, depth_out: Optional[np.ndarray] = None) -> "PackedFrames":
-        """Frames ``idx`` (any order, e.g. a shuffled batch) as a packed batch.  ``depth_out`` (float32, large
-        enough) receives the depths — e.g. a pinned staging buffer — so the gather is the only copy."""
+        """Frames ``idx`` (any order, e.g. a shuffled batch) as a packed batch of the pack's own form.  ``depth_out``
+        (float32 — uint16 for a 16-bit pack —, large enough) receives the depths — e.g. a pinned staging buffer — so the
+        gather is the only copy."""
         idx = np.asarray(idx, dtype=np.int64)
+        dtype = np.dtype(np.float32 if self.depth_shift is None else np.uint16)
+        if depth_out is not None and depth_out.dtype != dtype and np.uint16 in (depth_out.dtype, dtype):
+            raise TypeError(f"depth_out is {depth_out.dtype}, this pack's payload is {dtype}")
         if idx.size and (np.diff(idx) == 1).all():  # contiguous: one slice, no gather
             a, b = int(idx[0]), int(idx[-1]) + 1
             sub = self.slice(a, b)
@@ -155,11 +263,12 @@ class PackedFrames:
         off = np.zeros(idx.size + 1, np.int64)
         np.cumsum(lens, out=off[1:])
         total = int(off[-1])
-        out = depth_out[:total] if depth_out is not None else np.empty(total, np.float32)
+        out = depth_out[:total] if depth_out is not None else np.empty(total, dtype)
         if not _native_gather(self, idx, out, off):
             for k, i in enumerate(idx):  # n slice copies (the index arithmetic above is vectorised)
                 out[off[k]:off[k + 1]] = self.depth[self.offsets[i]:self.offsets[i + 1]]
-        return PackedFrames(out, off, self.headers[idx], None if self.gt is None else self.gt[idx])
+        return PackedFrames(out, off, self.headers[idx], None if self.gt is None else self.gt[idx],
+                            depth_shift=self.depth_shift)
 
     def pin(self) -> "PackedFrames":
         """Move the depth payload into page-locked host memory (once): contiguous batches can then be uploaded by
@@ -167,7 +276,8 @@ class PackedFrames:
         import torch
 
         if getattr(self, "_pinned", None) is None:
-            t = torch.empty(int(self.depth.size), dtype=torch.float32).pin_memory()
+            t = torch.empty(int(self.depth.size),
+                            dtype=torch.float32 if self.depth_shift is None else torch.uint16).pin_memory()
             t.numpy()[:] = self.depth
             self._pinned = t
             self.depth = t.numpy()
@@ -175,11 +285,19 @@ class PackedFrames:
 
     # ---- one-file blob ----
     def save(self, path: str) -> None:
-        """Write the pack as one ``TSDFPK01`` file (layout at the top of this module)."""
+        """Write the pack as one file (layout at the top of this module): ``TSDFPK01`` for a float32 pack, exactly as
+        before there was another form, ``TSDFPK02`` for a 16-bit one."""
         n = len(self)
         headers = np.ascontiguousarray(self.headers, np.int32).reshape(n, HEADER_INTS)
         offsets = np.ascontiguousarray(self.offsets, np.int64)
-        depth = np.ascontiguousarray(self.depth, np.float32)
+        if self.depth_shift is None:
+            magic, form = PACK_MAGIC, (PAYLOAD_F32, 0)
+            depth = np.ascontiguousarray(self.depth, np.float32)
+        else:
+            magic, form = PACK_MAGIC16, (PAYLOAD_U16, _check_shift(self.depth_shift))
+            if np.asarray(self.depth).dtype != np.uint16:
+                raise ValueError("a pack with a depth_shift holds uint16 depth")
+            depth = np.ascontiguousarray(self.depth, np.uint16)
         if offsets.shape != (n + 1,) or offsets[0] != 0 or offsets[-1] != depth.size:
             raise ValueError("offsets do not describe the depth buffer")
         gt = None if self.gt is None else np.ascontiguousarray(self.gt, np.float32)
@@ -189,8 +307,8 @@ class PackedFrames:
         names = "\n".join(self.group_names or [""] * (gs.size - 1)).encode()
         tmp = path + ".tmp"
         with open(tmp, "wb") as f:
-            f.write(PACK_MAGIC)
-            f.write(struct.pack("<7q", n, depth.size, 0 if gt is None else gt.shape[1], gs.size - 1, 0, 0, 0))
+            f.write(magic)
+            f.write(struct.pack("<7q", n, depth.size, 0 if gt is None else gt.shape[1], gs.size - 1, *form, 0))
             for arr in (headers, offsets, gt, gs, np.frombuffer(struct.pack("<q", len(names)) + names, np.uint8), depth):
                 f.write(b"\0" * (_pad(f.tell()) - f.tell()))
                 if arr is not None:
@@ -199,13 +317,23 @@ class PackedFrames:
 
     @staticmethod
     def load(path: str, mmap: bool = True) -> "PackedFrames":
-        """Open a ``TSDFPK01`` file.  ``mmap=True`` maps the arrays (nothing is read until used, pages are shared
-        between loader processes); ``mmap=False`` reads them into memory."""
+        """Open a ``TSDFPK01`` (float32) or ``TSDFPK02`` (16-bit) file.  ``mmap=True`` maps the arrays (nothing is read
+        until used, pages are shared between loader processes); ``mmap=False`` reads them into memory."""
         with open(path, "rb") as f:
             head = f.read(64)
-        if head[:8] != PACK_MAGIC:
-            raise ValueError(f"{path}: not a TSDFPK01 pack")
-        n, n_px, gt_cols, n_groups = struct.unpack("<4q", head[8:40])
+        if head[:8] not in (PACK_MAGIC, PACK_MAGIC16) or len(head) < 64:
+            raise ValueError(f"{path}: not a TSDFPK01 / TSDFPK02 pack")
+        n, n_px, gt_cols, n_groups, payload, shift = struct.unpack("<6q", head[8:56])
+        if head[:8] == PACK_MAGIC:
+            if payload != PAYLOAD_F32 or shift != 0:
+                raise ValueError(f"{path}: a TSDFPK01 pack with payload code {payload}, shift {shift} (damaged pack)")
+            depth_dtype, depth_shift = np.float32, None
+        else:
+            if payload != PAYLOAD_U16:
+                raise ValueError(f"{path}: unknown payload code {payload} in a TSDFPK02 pack")
+            if not 0 <= shift <= MAX_DEPTH_SHIFT:
+                raise ValueError(f"{path}: depth shift {shift} outside 0..{MAX_DEPTH_SHIFT}")
+            depth_dtype, depth_shift = np.uint16, int(shift)
         size = os.path.getsize(path)
 
         def arr(pos, dtype, shape):
@@ -232,7 +360,7 @@ class PackedFrames:
         raw, pos2 = arr(pos + 8, np.uint8, (int(ln[0]),))
         names = bytes(np.asarray(raw)).decode().split("\n") if n_groups else []
         pos = _pad(pos + 8 + int(ln[0]))
-        depth, _ = arr(pos, np.float32, (n_px,))
+        depth, _ = arr(pos, depth_dtype, (n_px,))
         if n and (int(offsets[0]) != 0 or int(offsets[-1]) != n_px):
             raise ValueError(f"{path}: offsets do not match the depth payload")
         if n:   # every interior offset too, and every header against its payload (vectorised; reads n*32 bytes)
@@ -243,21 +371,33 @@ class PackedFrames:
             if ((h[:, 4] - h[:, 2]) * (h[:, 5] - h[:, 3]) != np.diff(o)).any() or (h[:, 4] <= h[:, 2]).any() \
                     or (h[:, 5] <= h[:, 3]).any():
                 raise ValueError(f"{path}: a header contradicts its payload (damaged pack)")
-        return PackedFrames(depth, offsets, headers, gt, np.asarray(gs), names)
+        return PackedFrames(depth, offsets, headers, gt, np.asarray(gs), names, depth_shift)
 
-    def frame(self, i: int) -> Tuple[np.ndarray, np.ndarray]:
+    def raw_frame(self, i: int) -> Tuple[np.ndarray, np.ndarray]:
+        """(header, depth) of frame i in the pack's own payload type (uint16 for a 16-bit pack)."""
         return self.headers[i], self.depth[self.offsets[i]:self.offsets[i + 1]]
 
+    def frame(self, i: int) -> Tuple[np.ndarray, np.ndarray]:
+        """(header int32[6], depth float32[N]) of frame i — decoded, whatever the pack's form."""
+        h, d = self.raw_frame(i)
+        return h, d if self.depth_shift is None else decode_depth16(d, self.depth_shift)
+
     def to_torch(self, device, pin: bool = False, non_blocking: bool = False):
-        """(depth, offsets, headers) as torch tensors on ``device`` (one H2D copy each)."""
+        """(depth float32, offsets, headers) as torch tensors on ``device`` (one H2D copy each).  A 16-bit pack goes up
+        as uint16 — half the bytes — and is widened on the GPU (``voxelize.widen_depth16``, on the current stream); on
+        ``"cpu"`` it is decoded with numpy."""
         import torch
 
+        on_gpu = torch.device(device).type == "cuda"
         ts = []
-        for a in (self.depth, self.offsets, self.headers):
+        for a in (self.depth if on_gpu else self.depth_f32(), self.offsets, self.headers):
             t = torch.from_numpy(np.ascontiguousarray(a))
             if pin:
                 t = t.pin_memory()
             ts.append(t.to(device, non_blocking=non_blocking))
+        if on_gpu and self.depth_shift is not None:
+            from .voxelize import widen_depth16
+            ts[0] = widen_depth16(ts[0], self.depth_shift)
         return tuple(ts)
 
 
@@ -324,9 +464,22 @@ def pack_bin_files_fast(paths: Sequence[str], threads: int = 8) -> PackedFrames:
     return PackedFrames(depth, offsets, np.ascontiguousarray(headers))
 
 
-def pack_subject(sub_dir: str, gestures: Optional[Sequence[str]] = None, threads: int = 8) -> PackedFrames:
+def _as_depth16(pk: PackedFrames, depth16, what: str) -> PackedFrames:
+    """``depth16`` of pack_subject / pack_tree: None (float32), "auto" (the smallest exact shift) or a shift."""
+    if depth16 is None:
+        return pk
+    shift = None if isinstance(depth16, str) and depth16 == "auto" else _check_shift(depth16)
+    try:
+        return pk.to_depth16(shift)
+    except ValueError as e:
+        raise ValueError(f"{what}: {e}") from None
+
+
+def pack_subject(sub_dir: str, gestures: Optional[Sequence[str]] = None, threads: int = 8, depth16=None) -> PackedFrames:
     """One MSRA subject directory ``<sub>/<gesture>/{joint.txt, 000000_depth.bin, ...}`` -> one pack with labels
-    and gesture boundaries (the per-gesture loop of pre/read_MSRA.py:78-106, minus the voxelization)."""
+    and gesture boundaries (the per-gesture loop of pre/read_MSRA.py:78-106, minus the voxelization).
+    ``depth16``: None (float32 depth, as always), ``"auto"`` (16-bit depth with the subject's smallest exact shift;
+    ValueError if it has none) or a shift 0..7 to force."""
     ges = list(gestures) if gestures is not None else sorted(
         g for g in os.listdir(sub_dir) if os.path.isdir(os.path.join(sub_dir, g)))
     packs, gts, starts = [], [], [0]
@@ -339,21 +492,23 @@ def pack_subject(sub_dir: str, gestures: Optional[Sequence[str]] = None, threads
     if not packs:
         pk = pack_frames([])
         pk.gt, pk.group_start, pk.group_names = np.zeros((0, 63), np.float32), np.zeros(1, np.int64), []
-        return pk
+        return _as_depth16(pk, depth16, sub_dir)
     offs = [np.zeros(1, np.int64)]
     base = 0
     for pk in packs:
         offs.append(pk.offsets[1:] + base)
         base += int(pk.offsets[-1])
-    return PackedFrames(np.concatenate([pk.depth for pk in packs]), np.concatenate(offs),
-                        np.concatenate([pk.headers for pk in packs]), np.concatenate(gts).astype(np.float32),
-                        np.asarray(starts, np.int64), ges)
+    return _as_depth16(PackedFrames(np.concatenate([pk.depth for pk in packs]), np.concatenate(offs),
+                                    np.concatenate([pk.headers for pk in packs]), np.concatenate(gts).astype(np.float32),
+                                    np.asarray(starts, np.int64), ges), depth16, sub_dir)
 
 
 def pack_tree(db_dir: str, out_dir: str, subjects: Optional[Sequence[str]] = None, threads: int = 8,
-              overwrite: bool = False) -> Dict[str, str]:
+              overwrite: bool = False, depth16=None) -> Dict[str, str]:
     """Pack every subject of an MSRA tree into ``<out_dir>/<subject>.tsdfpk`` (skipping packs that exist unless
-    ``overwrite``).  Returns {subject: path}.  Run once; ``dataset.MSRADepthDataset(packed_dir=...)`` then maps them."""
+    ``overwrite``).  Returns {subject: path}.  Run once; ``dataset.MSRADepthDataset(packed_dir=...)`` then maps them.
+    ``depth16`` as for :func:`pack_subject`; with ``"auto"`` the subjects may end up with different shifts, which a
+    dataset refuses — force one shift (the largest any subject needs) then."""
     os.makedirs(out_dir, exist_ok=True)
     subs = list(subjects) if subjects is not None else sorted(
         d for d in os.listdir(db_dir) if os.path.isdir(os.path.join(db_dir, d)))
@@ -361,7 +516,7 @@ def pack_tree(db_dir: str, out_dir: str, subjects: Optional[Sequence[str]] = Non
     for sub in subs:
         path = os.path.join(out_dir, sub + ".tsdfpk")
         if overwrite or not os.path.exists(path):
-            pack_subject(os.path.join(db_dir, sub), threads=threads).save(path)
+            pack_subject(os.path.join(db_dir, sub), threads=threads, depth16=depth16).save(path)
         out[sub] = path
     return out
 

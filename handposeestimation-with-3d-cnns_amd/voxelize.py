@@ -922,3 +922,20 @@ def process_batch_aug(depth: torch.Tensor, offsets: torch.Tensor, headers: torch
     gt_aug = transform_joints(gt, xforms) if gt is not None else None
     return ProcessAugBatch(pb.points, pb.tsdf, pb.max_l, pb.mid_p, pa.points, tsdf_aug, cg.max_l, cg.mid_p, gt_aug,
                            pb.status, status_aug, pb.count, xforms)
+
+
+def widen_depth16(src_u16: torch.Tensor, shift: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """16-bit depth -> the float32 depth the voxelizers read: ``out[i] = float(src_u16[i]) * 2^-shift``, exact, by one
+    launch on the current stream (``tsdf_depth16_widen_hip`` of libtsdf_depth16.so; include/tsdf_depth16.h has the
+    contract, ``packing`` the encoding).  ``src_u16``: uint16 on the GPU, contiguous — any slice of a larger buffer, no
+    alignment beyond the element's is asked; ``shift`` 0..7; ``out``: float32 of the same shape on the same device
+    (allocated when None), likewise any slice.  No synchronisation."""
+    D = _lib.load_depth16()
+    _dev_check("src_u16", src_u16, torch.uint16)
+    if isinstance(shift, bool) or not isinstance(shift, int) or not 0 <= shift <= _lib.DEPTH16_MAX_SHIFT:
+        raise ValueError(f"shift must be an integer in 0..{_lib.DEPTH16_MAX_SHIFT}, got {shift!r}")
+    dev = src_u16.device
+    out = _out("out", out, tuple(src_u16.shape), torch.float32, dev)
+    if src_u16.numel():
+        _call(dev, D.tsdf_depth16_widen_hip, [src_u16.data_ptr(), src_u16.numel(), shift, out.data_ptr(), None], 4)
+    return out
