@@ -9,6 +9,7 @@ from __future__ import annotations
 import contextlib
 import ctypes
 import os
+from typing import NamedTuple
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _DEFAULT_LIB = os.path.join(_HERE, "libtsdf_hip.so")
@@ -106,12 +107,52 @@ DEPTH16_LIB_PATH = os.path.join(_HERE, "libtsdf_depth16.so")
 DEPTH16_VERSION = 1
 DEPTH16_MAX_SHIFT = 7   # TSDF_DEPTH16_MAX_SHIFT of include/tsdf_depth16.h
 
+
+class _Ext(NamedTuple):
+    """A row of the extension table: libtsdf_<name>.so, built by ``make -C csrc <name>`` from include/tsdf_<name>.h."""
+    path: str
+    version_symbol: str
+    version: int
+    entries: dict   # {entry point: argtypes}; every entry returns a tsdf_status (int)
+
+
+_vp, _i, _i64, _u64 = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_uint64
+
+# Adding an extension library is a row here, a name in csrc/Makefile's EXTS and a one-line load_<name> below.
+_EXTS = {
+    "augment": _Ext(AUGMENT_LIB_PATH, "tsdf_augment_version", AUGMENT_VERSION, {
+        # centres, n_src, index, n, key, counter0, stream, xforms, stretch, rot
+        "tsdf_aug_draw_hip": [_vp, _i64, _vp, _i, _u64, _u64, _vp, _vp, _vp, _vp],
+    }),
+    "augstep": _Ext(AUGSTEP_LIB_PATH, "tsdf_augstep_version", AUGSTEP_VERSION, {
+        # centres, n_src, index, n, state, counters, stream, xforms, stretch, rot
+        "tsdf_aug_draw_at_hip": [_vp, _i64, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp],
+    }),
+    "auggrid": _Ext(AUGGRID_LIB_PATH, "tsdf_auggrid_version", AUGGRID_VERSION, {
+        # depth, depth_len, offsets, headers, n, R, cam, layout, stream, xforms, grid, tsdf, status
+        "tsdf_voxelize_aug_grid_hip": [_vp, _i64, _vp, _vp, _i, _i, ctypes.POINTER(TsdfCam), _i, _vp, _vp, _vp, _vp, _vp],
+        # gt, xforms, n, n_joints, stream, gt_aug
+        "tsdf_transform_joints_hip": [_vp, _vp, _i, _i, _vp, _vp],
+    }),
+    "depth16": _Ext(DEPTH16_LIB_PATH, "tsdf_depth16_version", DEPTH16_VERSION, {
+        # src, n_px, shift, dst, stream
+        "tsdf_depth16_widen_hip": [_vp, _i64, _i, _vp, _vp],
+        # src, src_len, src_offsets, n_src, index, n, dst, dst_len, dst_offsets, n_threads
+        "tsdf_depth16_host_gather": [_vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i],
+    }),
+}
+
 _lib = None
 _debug_lib = None
-_augment_lib = None
-_augstep_lib = None
-_auggrid_lib = None
-_depth16_lib = None
+_ext_libs = {}   # name -> the loaded extension library
+
+
+def _declare(L, entries: dict) -> None:
+    """``argtypes`` as given and ``restype`` int on every named entry point of a loaded library."""
+    for name, argtypes in entries.items():
+        fn = getattr(L, name)
+        fn.restype = ctypes.c_int
+        fn.argtypes = argtypes
 
 
 def _bind(L, path: str, debug: bool = False):
@@ -134,7 +175,7 @@ def _bind(L, path: str, debug: bool = False):
     pack = [vp, i64, vp, vp, i, i, cam_p, i, vp]              # depth, depth_len, offsets, headers, n, R, cam, layout, stream
     indexed = [vp, i64, vp, vp, i64, vp, i, i, cam_p, i, vp]  # ... headers, n_pack, index, n, R, cam, layout, stream
     outs = [vp, vp, vp, vp]                                   # tsdf, max_l, mid_p, status
-    for name, argtypes in {
+    entries = {
             "tsdf_voxelize_hip": pack + outs,
             "tsdf_voxelize_labels_hip": pack + outs + [lab_p],
             "tsdf_voxelize_grid_hip": pack + [vp, vp, vp],                       # grid, tsdf, status
@@ -159,11 +200,8 @@ def _bind(L, path: str, debug: bool = False):
             "tsdf_describe_launch": [i, i, i, i, ctypes.c_char_p, i],
             "tsdf_debug_pixmap_hip": pack + [vp, vp, vp, vp],                    # grid, tsdf, pixmap, status
             "tsdf_debug_set_queue_word": [vp, ctypes.c_uint64],
-    }.items():
-        if not name.startswith("tsdf_debug_") or debug:
-            fn = getattr(L, name)
-            fn.restype = i
-            fn.argtypes = argtypes
+    }
+    _declare(L, {k: v for k, v in entries.items() if debug or not k.startswith("tsdf_debug_")})
     return L
 
 
@@ -195,98 +233,42 @@ def load_debug():
     return L
 
 
-def load_augment():
-    """Load libtsdf_augment.so once and declare its two entry points; raise loudly if it is not there."""
-    global _augment_lib
-    if _augment_lib is not None:
-        return _augment_lib
-    if not os.path.exists(AUGMENT_LIB_PATH):
-        raise ImportError(f"{AUGMENT_LIB_PATH} not found: build it with `make -C handposeestimation-with-3d-cnns_amd/csrc "
-                          "augment` (__graft_entry__.build() does). There is no CPU fallback.")
-    L = ctypes.CDLL(AUGMENT_LIB_PATH)
-    L.tsdf_augment_version.restype = ctypes.c_int
-    L.tsdf_augment_version.argtypes = []
-    if L.tsdf_augment_version() != AUGMENT_VERSION:
-        raise ImportError(f"{AUGMENT_LIB_PATH} has version {L.tsdf_augment_version()}, this package needs "
-                          f"{AUGMENT_VERSION}: rebuild it")
-    vp = ctypes.c_void_p
-    L.tsdf_aug_draw_hip.restype = ctypes.c_int
-    # centres, n_src, index, n, key, counter0, stream, xforms, stretch, rot
-    L.tsdf_aug_draw_hip.argtypes = [vp, ctypes.c_int64, vp, ctypes.c_int, ctypes.c_uint64, ctypes.c_uint64, vp, vp, vp, vp]
-    _augment_lib = L
+def _load_ext(name: str):
+    """Load libtsdf_<name>.so once and declare its entry points; raise loudly if it is not there."""
+    L = _ext_libs.get(name)
+    if L is not None:
+        return L
+    ext = _EXTS[name]
+    if not os.path.exists(ext.path):
+        raise ImportError(f"{ext.path} not found: build it with `make -C handposeestimation-with-3d-cnns_amd/csrc "
+                          f"{name}` (__graft_entry__.build() does). There is no CPU fallback.")
+    L = ctypes.CDLL(ext.path)
+    _declare(L, {ext.version_symbol: [], **ext.entries})
+    have = getattr(L, ext.version_symbol)()
+    if have != ext.version:
+        raise ImportError(f"{ext.path} has version {have}, this package needs {ext.version}: rebuild it")
+    _ext_libs[name] = L
     return L
+
+
+def load_augment():
+    """libtsdf_augment.so, the library of include/tsdf_augment.h."""
+    return _load_ext("augment")
 
 
 def load_augstep():
-    """Load libtsdf_augstep.so once and declare its two entry points; raise loudly if it is not there."""
-    global _augstep_lib
-    if _augstep_lib is not None:
-        return _augstep_lib
-    if not os.path.exists(AUGSTEP_LIB_PATH):
-        raise ImportError(f"{AUGSTEP_LIB_PATH} not found: build it with `make -C handposeestimation-with-3d-cnns_amd/csrc "
-                          "augstep` (__graft_entry__.build() does). There is no CPU fallback.")
-    L = ctypes.CDLL(AUGSTEP_LIB_PATH)
-    L.tsdf_augstep_version.restype = ctypes.c_int
-    L.tsdf_augstep_version.argtypes = []
-    if L.tsdf_augstep_version() != AUGSTEP_VERSION:
-        raise ImportError(f"{AUGSTEP_LIB_PATH} has version {L.tsdf_augstep_version()}, this package needs "
-                          f"{AUGSTEP_VERSION}: rebuild it")
-    vp = ctypes.c_void_p
-    L.tsdf_aug_draw_at_hip.restype = ctypes.c_int
-    # centres, n_src, index, n, state, counters, stream, xforms, stretch, rot
-    L.tsdf_aug_draw_at_hip.argtypes = [vp, ctypes.c_int64, vp, ctypes.c_int, vp, vp, vp, vp, vp, vp]
-    _augstep_lib = L
-    return L
+    """libtsdf_augstep.so, the library of include/tsdf_augstep.h."""
+    return _load_ext("augstep")
 
 
 def load_auggrid():
-    """Load libtsdf_auggrid.so once and declare its three entry points; raise loudly if it is not there."""
-    global _auggrid_lib
-    if _auggrid_lib is not None:
-        return _auggrid_lib
-    if not os.path.exists(AUGGRID_LIB_PATH):
-        raise ImportError(f"{AUGGRID_LIB_PATH} not found: build it with `make -C handposeestimation-with-3d-cnns_amd/csrc "
-                          "auggrid` (__graft_entry__.build() does). There is no CPU fallback.")
-    L = ctypes.CDLL(AUGGRID_LIB_PATH)
-    L.tsdf_auggrid_version.restype = ctypes.c_int
-    L.tsdf_auggrid_version.argtypes = []
-    if L.tsdf_auggrid_version() != AUGGRID_VERSION:
-        raise ImportError(f"{AUGGRID_LIB_PATH} has version {L.tsdf_auggrid_version()}, this package needs "
-                          f"{AUGGRID_VERSION}: rebuild it")
-    vp, i = ctypes.c_void_p, ctypes.c_int
-    L.tsdf_voxelize_aug_grid_hip.restype = i
-    # depth, depth_len, offsets, headers, n, R, cam, layout, stream, xforms, grid, tsdf, status
-    L.tsdf_voxelize_aug_grid_hip.argtypes = [vp, ctypes.c_int64, vp, vp, i, i, ctypes.POINTER(TsdfCam), i, vp, vp, vp, vp, vp]
-    L.tsdf_transform_joints_hip.restype = i
-    # gt, xforms, n, n_joints, stream, gt_aug
-    L.tsdf_transform_joints_hip.argtypes = [vp, vp, i, i, vp, vp]
-    _auggrid_lib = L
-    return L
+    """libtsdf_auggrid.so, the library of include/tsdf_auggrid.h."""
+    return _load_ext("auggrid")
 
 
 def load_depth16():
-    """Load libtsdf_depth16.so once and declare its two entry points; raise loudly if it is not there."""
-    global _depth16_lib
-    if _depth16_lib is not None:
-        return _depth16_lib
-    if not os.path.exists(DEPTH16_LIB_PATH):
-        raise ImportError(f"{DEPTH16_LIB_PATH} not found: build it with `make -C handposeestimation-with-3d-cnns_amd/csrc "
-                          "depth16` (__graft_entry__.build() does). There is no CPU fallback.")
-    L = ctypes.CDLL(DEPTH16_LIB_PATH)
-    L.tsdf_depth16_version.restype = ctypes.c_int
-    L.tsdf_depth16_version.argtypes = []
-    if L.tsdf_depth16_version() != DEPTH16_VERSION:
-        raise ImportError(f"{DEPTH16_LIB_PATH} has version {L.tsdf_depth16_version()}, this package needs "
-                          f"{DEPTH16_VERSION}: rebuild it")
-    vp, i, i64 = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64
-    L.tsdf_depth16_widen_hip.restype = i
-    # src, n_px, shift, dst, stream
-    L.tsdf_depth16_widen_hip.argtypes = [vp, i64, i, vp, vp]
-    L.tsdf_depth16_host_gather.restype = i
-    # src, src_len, src_offsets, n_src, index, n, dst, dst_len, dst_offsets, n_threads
-    L.tsdf_depth16_host_gather.argtypes = [vp, i64, vp, i64, vp, i64, vp, i64, vp, i]
-    _depth16_lib = L
-    return L
+    """libtsdf_depth16.so, the library of include/tsdf_depth16.h."""
+    return _load_ext("depth16")
 
 
 @contextlib.contextmanager

@@ -251,8 +251,7 @@ int tsdf_debug_set_queue_word(void *hip_stream, uint64_t value) {
 int tsdf_describe_launch(int n, int R, int layout, int aug, char *buf, int buflen) {
   if (!buf || buflen < 1 || n < 1 || !tsdf_resolution_supported(R)) return TSDF_ERR_INVALID_ARG;
   if (layout != TSDF_LAYOUT_CZYX && layout != TSDF_LAYOUT_CXYZ) return TSDF_ERR_INVALID_ARG;
-  int dev = 0;
-  const int rc = check_device(&dev);
+  const int rc = check_device(nullptr);
   if (rc != TSDF_OK) return rc;
   const int rt = (R == 32 || R == 64) ? R : 0;   // launch_r's choice of instantiation
   int S = 0, per = R;

@@ -4,7 +4,8 @@
 // angle formulas, the float64 operation order of the maps, the analytic inverse, the twelve 16-byte stores — is this file.
 // Arithmetic contract: include/tsdf_augment.h; float64 throughout, compiled with -ffp-contract=off.
 //
-// Included inside an anonymous namespace, after <hip/hip_runtime.h>, <stdint.h>, <string.h>, <atomic> and include/tsdf.h.
+// Device code only (the host preamble is device.inc).  Included inside an anonymous namespace, after
+// <hip/hip_runtime.h>, <stdint.h> and include/tsdf.h.
 
 constexpr int kAugWG = 256;   // threads per workgroup (4 wave64)
 
@@ -84,26 +85,4 @@ __device__ __forceinline__ void aug_draw_row(const float *centres, int64_t n_src
     rot[2 * i + 0] = rxy;
     rot[2 * i + 1] = rz;
   }
-}
-
-// The current device must be a gfx950 (the code object holds nothing else).  The answer is cached per device.
-int aug_check_device() {
-  static std::atomic<int> arch_state[64];  // 0 unknown, 1 gfx950, -1 something else
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess) {
-    (void)hipGetLastError();
-    return TSDF_ERR_NO_DEVICE;
-  }
-  if (dev < 0 || dev >= 64) return TSDF_OK;  // beyond the cache: let the launch decide
-  int st = arch_state[dev].load(std::memory_order_relaxed);
-  if (st == 0) {
-    hipDeviceProp_t prop;
-    if (hipGetDeviceProperties(&prop, dev) != hipSuccess) {
-      (void)hipGetLastError();
-      return TSDF_ERR_NO_DEVICE;
-    }
-    st = strncmp(prop.gcnArchName, "gfx950", 6) == 0 ? 1 : -1;
-    arch_state[dev].store(st, std::memory_order_relaxed);
-  }
-  return st == 1 ? TSDF_OK : TSDF_ERR_NO_DEVICE;
 }

@@ -265,11 +265,10 @@ int run_point_clouds(const float *d_depth, int64_t depth_len, const int64_t *d_o
                      int points, const tsdf_cam *cam, uint64_t seed, int64_t frame_base, const double *d_xforms,
                      void *hip_stream, double *d_out_points, int32_t *d_out_count, int32_t *d_out_status) {
   if (n < 0 || points < 1 || !d_out_points) return TSDF_ERR_INVALID_ARG;
-  if (reinterpret_cast<uintptr_t>(d_xforms) & 7) return TSDF_ERR_INVALID_ARG;
+  if (misaligned(d_xforms, 7)) return TSDF_ERR_INVALID_ARG;
   if (n == 0) return TSDF_OK;
   if (!d_depth || !d_offsets || !d_headers || depth_len < 0) return TSDF_ERR_INVALID_ARG;
-  int dev = 0;
-  const int rc = check_device(&dev);
+  const int rc = check_device(nullptr);
   if (rc != TSDF_OK) return rc;
   // split a frame's slots over workgroups until the launch has about two workgroups per CU
   const int tiles = (points + kCloudWG - 1) / kCloudWG;
@@ -298,5 +297,5 @@ int run_point_clouds(const float *d_depth, int64_t depth_len, const int64_t *d_o
   a.status = d_out_status;
   hipLaunchKernelGGL(tsdf_point_cloud_kernel, dim3((unsigned)blocks), dim3(kCloudWG), 0,
                      static_cast<hipStream_t>(hip_stream), a);
-  return hipGetLastError() == hipSuccess ? TSDF_OK : TSDF_ERR_LAUNCH;
+  return launched();
 }

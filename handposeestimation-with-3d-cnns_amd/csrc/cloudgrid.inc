@@ -152,9 +152,8 @@ int run_cloud_grid(const double *d_points, int n, int points, int R, const tsdf_
   if (n < 0 || points < 1 || !tsdf_resolution_supported(R)) return TSDF_ERR_INVALID_ARG;
   if (n == 0) return TSDF_OK;
   if (!d_points || !d_out_grid || !d_out_max_l || !d_out_mid_p) return TSDF_ERR_INVALID_ARG;
-  if (reinterpret_cast<uintptr_t>(d_points) & 7) return TSDF_ERR_INVALID_ARG;
-  int dev = 0;
-  const int rc = check_device(&dev);
+  if (misaligned(d_points, 7)) return TSDF_ERR_INVALID_ARG;
+  const int rc = check_device(nullptr);
   if (rc != TSDF_OK) return rc;
   CloudGridArgs a;
   a.points = d_points;
@@ -167,5 +166,5 @@ int run_cloud_grid(const double *d_points, int n, int points, int R, const tsdf_
   a.aabb = d_out_aabb;
   a.status = d_out_status;
   hipLaunchKernelGGL(tsdf_cloud_grid_kernel, dim3((unsigned)n), dim3(kCgWG), 0, static_cast<hipStream_t>(hip_stream), a);
-  return hipGetLastError() == hipSuccess ? TSDF_OK : TSDF_ERR_LAUNCH;
+  return launched();
 }

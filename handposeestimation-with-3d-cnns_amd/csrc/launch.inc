@@ -1,6 +1,6 @@
 // launch.inc — part of the one translation unit tsdf_hip.hip (included there, inside its anonymous namespace).
-// Host side of a call: the one argument check (tsdf_host.inc), device check, split plan, choice of instantiation,
-// argument marshalling.
+// Host side of a call: the one argument check (tsdf_host.inc), device check (device.inc), split plan, choice of
+// instantiation, argument marshalling.
 
 const tsdf_cam kDefaultCam = {241.42, 160.0, 120.0, 1.0f, 3.0f};
 
@@ -15,30 +15,6 @@ int num_cus() {
     cached[dev].store(v, std::memory_order_relaxed);
   }
   return v;
-}
-
-// The code object holds gfx950 kernels only: any other device is "no usable device", not a launch error.
-// (Cached per device id; a racing first call computes the same value.)
-int check_device(int *dev_out) {
-  static std::atomic<int> arch_state[64];  // 0 unknown, 1 gfx950, -1 something else
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess) {
-    (void)hipGetLastError();
-    return TSDF_ERR_NO_DEVICE;
-  }
-  *dev_out = dev;
-  if (dev < 0 || dev >= 64) return TSDF_OK;  // beyond the cache: let the launch decide
-  int st = arch_state[dev].load(std::memory_order_relaxed);
-  if (st == 0) {
-    hipDeviceProp_t prop;
-    if (hipGetDeviceProperties(&prop, dev) != hipSuccess) {
-      (void)hipGetLastError();
-      return TSDF_ERR_NO_DEVICE;
-    }
-    st = strncmp(prop.gcnArchName, "gfx950", 6) == 0 ? 1 : -1;
-    arch_state[dev].store(st, std::memory_order_relaxed);
-  }
-  return st == 1 ? TSDF_OK : TSDF_ERR_NO_DEVICE;
 }
 
 // Workgroups per frame and slices per workgroup for the split kernel (0: use the fused kernel).
@@ -211,8 +187,7 @@ int run_normalize(const float *d_in, const float *d_max_l, const float *d_mid_p,
   if (n < 0 || n_joints < 1 || n_joints > 170) return TSDF_ERR_INVALID_ARG;
   if (n == 0) return TSDF_OK;
   if (!d_in || !d_max_l || !d_mid_p || !d_out) return TSDF_ERR_INVALID_ARG;
-  int dev = 0;
-  int rc = check_device(&dev);
+  const int rc = check_device(nullptr);
   if (rc != TSDF_OK) return rc;
   const int nc = 3 * n_joints;
   const int64_t total = (int64_t)n * nc;
@@ -220,7 +195,7 @@ int run_normalize(const float *d_in, const float *d_max_l, const float *d_mid_p,
   if (blocks > 0x7fffffff) return TSDF_ERR_INVALID_ARG;
   hipLaunchKernelGGL(tsdf_normalize_kernel, dim3((unsigned)blocks), dim3(256), 0, static_cast<hipStream_t>(hip_stream),
                      d_in, d_max_l, d_mid_p, total, nc, clamp, inverse, d_out);
-  return hipGetLastError() == hipSuccess ? TSDF_OK : TSDF_ERR_LAUNCH;
+  return launched();
 }
 
 
@@ -230,15 +205,14 @@ int run_project(const float *d_gt, const float *d_max_l, const float *d_mid_p, i
   if (n < 0 || tsdf_host::check_pca(pca, n, n_joints, true) != TSDF_OK) return TSDF_ERR_INVALID_ARG;
   if (n == 0) return TSDF_OK;
   if (!d_gt || !d_max_l || !d_mid_p) return TSDF_ERR_INVALID_ARG;
-  int dev = 0;
-  const int rc = check_device(&dev);
+  const int rc = check_device(nullptr);
   if (rc != TSDF_OK) return rc;
   const int K = pca->n_components, kchunks = (K + 63) / 64;
   const int64_t blocks = (int64_t)n * kchunks;
   if (blocks > 0x7fffffff) return TSDF_ERR_INVALID_ARG;
   hipLaunchKernelGGL(tsdf_project_kernel, dim3((unsigned)blocks), dim3(64), 0, static_cast<hipStream_t>(hip_stream), d_gt,
                      d_max_l, d_mid_p, 3 * n_joints, pca->d_mean, pca->d_coeff, K, kchunks, pca->d_out_gt_pca);
-  return hipGetLastError() == hipSuccess ? TSDF_OK : TSDF_ERR_LAUNCH;
+  return launched();
 }
 
 // tsdf_pose_error_hip: one wave per frame.
@@ -248,8 +222,7 @@ int run_pose_error(const float *d_pred, const tsdf_pca *pca, const float *d_max_
   if (pca && tsdf_host::check_pca(pca, n, n_joints, false) != TSDF_OK) return TSDF_ERR_INVALID_ARG;
   if (n == 0) return TSDF_OK;
   if (!d_pred || !d_max_l || !d_mid_p || !d_gt || !d_err || !d_fmean || !d_fmax) return TSDF_ERR_INVALID_ARG;
-  int dev = 0;
-  const int rc = check_device(&dev);
+  const int rc = check_device(nullptr);
   if (rc != TSDF_OK) return rc;
   PoseArgs a;
   a.pred = d_pred;
@@ -268,5 +241,5 @@ int run_pose_error(const float *d_pred, const tsdf_pca *pca, const float *d_max_
   const int blocks = (n + kPoseWaves - 1) / kPoseWaves;
   hipLaunchKernelGGL(tsdf_pose_error_kernel, dim3((unsigned)blocks), dim3(64 * kPoseWaves), 0,
                      static_cast<hipStream_t>(hip_stream), a);
-  return hipGetLastError() == hipSuccess ? TSDF_OK : TSDF_ERR_LAUNCH;
+  return launched();
 }

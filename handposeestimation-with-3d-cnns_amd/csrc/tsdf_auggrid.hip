@@ -2,9 +2,9 @@
 // their own (include/tsdf_auggrid.h).
 //
 // A translation unit and a library of its own, next to libtsdf_hip.so, libtsdf_augment.so and libtsdf_augstep.so (all
-// frozen).  It takes the status codes, tsdf_cam and the layout enum from include/tsdf.h; the two small arithmetic helpers
-// (trunc_i32, the device check) are restated here, nothing of the product's .inc files is included, and there is no device
-// global: every launch is self-contained.
+// frozen).  It takes the status codes, tsdf_cam and the layout enum from include/tsdf.h and the host preamble every library
+// here has from device.inc; the small arithmetic helper trunc_i32 is restated here, nothing else of the product's .inc files
+// is included, and there is no device global: every launch is self-contained.
 //
 // tsdf_aug_grid_kernel: n x ceil(R / slab) workgroups of 256 threads; a workgroup owns `slab` consecutive slices (indices
 // of the slowest output axis) of one frame, so a batch of 16 frames at 32^3 is 256 workgroups.  It
@@ -31,6 +31,8 @@
 #include "../../include/tsdf_auggrid.h"
 
 namespace {
+
+#include "device.inc"   // check_device, launched, misaligned: the host preamble of every library here
 
 constexpr int kGridWG = 256;       // threads per workgroup (4 wave64)
 constexpr int kGridMaxR = 128;     // largest resolution (include/tsdf.h: tsdf_resolution_supported)
@@ -216,28 +218,6 @@ __global__ __launch_bounds__(kGridWG) void tsdf_transform_joints_kernel(JointArg
     o[r] = (float)__builtin_fma(m[4 * r], x, __builtin_fma(m[4 * r + 1], y, __builtin_fma(m[4 * r + 2], z, m[4 * r + 3])));
 }
 
-// The current device must be a gfx950 (the code object holds nothing else).  The answer is cached per device (host side).
-int grid_check_device() {
-  static std::atomic<int> arch_state[64];  // 0 unknown, 1 gfx950, -1 something else
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess) {
-    (void)hipGetLastError();
-    return TSDF_ERR_NO_DEVICE;
-  }
-  if (dev < 0 || dev >= 64) return TSDF_OK;  // beyond the cache: let the launch decide
-  int st = arch_state[dev].load(std::memory_order_relaxed);
-  if (st == 0) {
-    hipDeviceProp_t prop;
-    if (hipGetDeviceProperties(&prop, dev) != hipSuccess) {
-      (void)hipGetLastError();
-      return TSDF_ERR_NO_DEVICE;
-    }
-    st = strncmp(prop.gcnArchName, "gfx950", 6) == 0 ? 1 : -1;
-    arch_state[dev].store(st, std::memory_order_relaxed);
-  }
-  return st == 1 ? TSDF_OK : TSDF_ERR_NO_DEVICE;
-}
-
 }  // namespace
 
 extern "C" {
@@ -253,14 +233,14 @@ int tsdf_voxelize_aug_grid_hip(const float *d_depth, int64_t depth_len, const in
   if (!d_depth || !d_offsets || !d_headers || !d_xforms || !d_grid || !d_out_tsdf || depth_len < 0) return TSDF_ERR_INVALID_ARG;
   if (R < 4 || R > kGridMaxR || (R & 3)) return TSDF_ERR_INVALID_ARG;
   if (layout != TSDF_LAYOUT_CZYX && layout != TSDF_LAYOUT_CXYZ) return TSDF_ERR_INVALID_ARG;
-  if ((reinterpret_cast<uintptr_t>(d_xforms) & 7) || (reinterpret_cast<uintptr_t>(d_out_tsdf) & 15)) return TSDF_ERR_INVALID_ARG;
+  if (misaligned(d_xforms, 7) || misaligned(d_out_tsdf, 15)) return TSDF_ERR_INVALID_ARG;
   const int per = R * (R >> 2);   // items per slice
   int slab = (kGridItems + per - 1) / per;
   if (slab > R) slab = R;
   const int nslab = (R + slab - 1) / slab;
   const int64_t blocks = (int64_t)n * nslab;
   if (blocks * kGridWG > 0xffffffffll) return TSDF_ERR_INVALID_ARG;   // a launch holds fewer than 2^32 work-items
-  const int rc = grid_check_device();
+  const int rc = check_device(nullptr);
   if (rc != TSDF_OK) return rc;
   if (!cam) cam = &kDefaultCam;
   AugGridArgs a;
@@ -285,7 +265,7 @@ int tsdf_voxelize_aug_grid_hip(const float *d_depth, int64_t depth_len, const in
     hipLaunchKernelGGL(tsdf_aug_grid_kernel<0>, dim3((unsigned)blocks), dim3(kGridWG), 0, s, a);
   else
     hipLaunchKernelGGL(tsdf_aug_grid_kernel<1>, dim3((unsigned)blocks), dim3(kGridWG), 0, s, a);
-  return hipGetLastError() == hipSuccess ? TSDF_OK : TSDF_ERR_LAUNCH;
+  return launched();
 }
 
 int tsdf_transform_joints_hip(const float *d_gt, const double *d_xforms, int n, int n_joints, void *hip_stream,
@@ -293,8 +273,8 @@ int tsdf_transform_joints_hip(const float *d_gt, const double *d_xforms, int n, 
   if (n < 0) return TSDF_ERR_INVALID_ARG;
   if (n == 0) return TSDF_OK;
   if (!d_gt || !d_xforms || !d_out_gt_aug || n_joints < 1 || n_joints > 170) return TSDF_ERR_INVALID_ARG;
-  if (reinterpret_cast<uintptr_t>(d_xforms) & 7) return TSDF_ERR_INVALID_ARG;
-  const int rc = grid_check_device();
+  if (misaligned(d_xforms, 7)) return TSDF_ERR_INVALID_ARG;
+  const int rc = check_device(nullptr);
   if (rc != TSDF_OK) return rc;
   JointArgs a;
   a.gt = d_gt;
@@ -306,7 +286,7 @@ int tsdf_transform_joints_hip(const float *d_gt, const double *d_xforms, int n, 
   if (blocks * kGridWG > 0xffffffffll) return TSDF_ERR_INVALID_ARG;
   hipLaunchKernelGGL(tsdf_transform_joints_kernel, dim3((unsigned)blocks), dim3(kGridWG), 0,
                      static_cast<hipStream_t>(hip_stream), a);
-  return hipGetLastError() == hipSuccess ? TSDF_OK : TSDF_ERR_LAUNCH;
+  return launched();
 }
 
 }  // extern "C"

@@ -1,7 +1,8 @@
 // tsdf_augment.hip — libtsdf_augment.so: the 3-D augmentation's draws and maps on the GPU (include/tsdf_augment.h).
 //
 // A translation unit and a library of its own, next to the product (tsdf_hip.hip -> libtsdf_hip.so, whose ABI is
-// frozen): it shares the status codes of include/tsdf.h and nothing else — none of the product's .inc files is included.
+// frozen): it shares the status codes of include/tsdf.h and the host preamble of device.inc — none of the product's other
+// .inc files is included.
 // The draw and map arithmetic is in augdraw.inc, which tsdf_augstep.hip (libtsdf_augstep.so) includes too.
 //
 // What it replaces: augment.random_affines per batch on the host (a numpy Generator, stacked rotation matrices,
@@ -28,7 +29,8 @@
 
 namespace {
 
-#include "augdraw.inc"   // aug_mix, aug_angle, aug_draw_row, aug_check_device: shared with tsdf_augstep.hip
+#include "device.inc"    // check_device, launched, misaligned: the host preamble of every library here
+#include "augdraw.inc"   // aug_mix, aug_angle, aug_draw_row: shared with tsdf_augstep.hip
 
 struct AugArgs {
   const float *centres;    // [n_src][3]
@@ -61,8 +63,8 @@ int tsdf_aug_draw_hip(const float *d_centres, int64_t n_src, const int64_t *d_in
   if (n < 0) return TSDF_ERR_INVALID_ARG;
   if (n == 0) return TSDF_OK;
   if (!d_centres || !d_out_xforms || n_src < 1) return TSDF_ERR_INVALID_ARG;
-  if (reinterpret_cast<uintptr_t>(d_out_xforms) & 7) return TSDF_ERR_INVALID_ARG;
-  const int rc = aug_check_device();
+  if (misaligned(d_out_xforms, 7)) return TSDF_ERR_INVALID_ARG;
+  const int rc = check_device(nullptr);
   if (rc != TSDF_OK) return rc;
   AugArgs a;
   a.centres = d_centres;
@@ -76,7 +78,7 @@ int tsdf_aug_draw_hip(const float *d_centres, int64_t n_src, const int64_t *d_in
   a.rot = d_out_rot;
   const unsigned blocks = ((unsigned)n + kAugWG - 1) / kAugWG;
   hipLaunchKernelGGL(tsdf_aug_draw_kernel, dim3(blocks), dim3(kAugWG), 0, static_cast<hipStream_t>(hip_stream), a);
-  return hipGetLastError() == hipSuccess ? TSDF_OK : TSDF_ERR_LAUNCH;
+  return launched();
 }
 
 }  // extern "C"

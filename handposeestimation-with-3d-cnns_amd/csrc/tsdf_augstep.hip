@@ -2,7 +2,8 @@
 // (include/tsdf_augstep.h).
 //
 // A translation unit and a library of its own, next to libtsdf_hip.so and libtsdf_augment.so (both frozen).  It shares the
-// status codes of include/tsdf.h and, with tsdf_augment.hip, augdraw.inc: the draw and map arithmetic exists once.
+// status codes of include/tsdf.h, the host preamble of device.inc and, with tsdf_augment.hip, augdraw.inc: the draw and map
+// arithmetic exists once.
 //
 // What it adds to tsdf_aug_draw_hip: that entry takes key and counter0 as kernel arguments and gives position i the counter
 // counter0 + i.  Two things cannot be done with it: a batch whose counters are not contiguous (a shuffled batch in which
@@ -24,7 +25,8 @@
 
 namespace {
 
-#include "augdraw.inc"   // aug_mix, aug_angle, aug_draw_row, aug_check_device: shared with tsdf_augment.hip
+#include "device.inc"    // check_device, launched, misaligned: the host preamble of every library here
+#include "augdraw.inc"   // aug_mix, aug_angle, aug_draw_row: shared with tsdf_augment.hip
 
 struct AugAtArgs {
   const float *centres;      // [n_src][3]
@@ -60,8 +62,8 @@ int tsdf_aug_draw_at_hip(const float *d_centres, int64_t n_src, const int64_t *d
   if (n < 0) return TSDF_ERR_INVALID_ARG;
   if (n == 0) return TSDF_OK;
   if (!d_centres || !d_state || !d_out_xforms || n_src < 1) return TSDF_ERR_INVALID_ARG;
-  if ((reinterpret_cast<uintptr_t>(d_out_xforms) | reinterpret_cast<uintptr_t>(d_state)) & 7) return TSDF_ERR_INVALID_ARG;
-  const int rc = aug_check_device();
+  if (misaligned(d_out_xforms, 7) || misaligned(d_state, 7)) return TSDF_ERR_INVALID_ARG;
+  const int rc = check_device(nullptr);
   if (rc != TSDF_OK) return rc;
   AugAtArgs a;
   a.centres = d_centres;
@@ -75,7 +77,7 @@ int tsdf_aug_draw_at_hip(const float *d_centres, int64_t n_src, const int64_t *d
   a.rot = d_out_rot;
   const unsigned blocks = ((unsigned)n + kAugWG - 1) / kAugWG;
   hipLaunchKernelGGL(tsdf_aug_draw_at_kernel, dim3(blocks), dim3(kAugWG), 0, static_cast<hipStream_t>(hip_stream), a);
-  return hipGetLastError() == hipSuccess ? TSDF_OK : TSDF_ERR_LAUNCH;
+  return launched();
 }
 
 }  // extern "C"

@@ -2,8 +2,8 @@
 // twin of the loaders' host gather (include/tsdf_depth16.h).
 //
 // A translation unit and a library of its own, next to libtsdf_hip.so and the three aug* extensions (all frozen).  It
-// shares the status codes of include/tsdf.h; the host gather is depth16_host.inc (plain C++, also built on its own under
-// the CPU sanitizers).
+// shares the status codes of include/tsdf.h and the host preamble of device.inc (device_cus sizes the grid); the host
+// gather is depth16_host.inc (plain C++, also built on its own under the CPU sanitizers).
 //
 // Kernel: a streaming conversion, 2 bytes in and 4 bytes out per pixel, nothing reused — it should run at memory rate.
 //   * A lane converts eight pixels per step: ONE 16-byte load, eight v_cvt + v_mul, TWO 16-byte stores.  A wave's load
@@ -29,6 +29,8 @@
 #include "depth16_host.inc"
 
 namespace {
+
+#include "device.inc"   // device_cus, launched, misaligned: the host preamble of every library here
 
 constexpr int kWG = 256;          // threads per workgroup (4 wave64)
 constexpr int kWGPerCU = 8;       // workgroups per CU the grid is sized for
@@ -66,29 +68,6 @@ __global__ __launch_bounds__(kWG) void tsdf_depth16_widen_kernel(const uint16_t 
   }
 }
 
-// The current device must be a gfx950 (the code object holds nothing else); its CU count sizes the grid.  Both are
-// cached per device.  Returns the CU count (> 0), or a negative tsdf_status.
-int device_cus() {
-  static std::atomic<int> state[64];  // 0 unknown, > 0 the CU count of a gfx950, -1 something else
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess) {
-    (void)hipGetLastError();
-    return TSDF_ERR_NO_DEVICE;
-  }
-  const bool cached = dev >= 0 && dev < 64;
-  int st = cached ? state[dev].load(std::memory_order_relaxed) : 0;
-  if (st == 0) {
-    hipDeviceProp_t prop;
-    if (hipGetDeviceProperties(&prop, dev) != hipSuccess) {
-      (void)hipGetLastError();
-      return TSDF_ERR_NO_DEVICE;
-    }
-    st = strncmp(prop.gcnArchName, "gfx950", 6) == 0 && prop.multiProcessorCount > 0 ? prop.multiProcessorCount : -1;
-    if (cached) state[dev].store(st, std::memory_order_relaxed);
-  }
-  return st > 0 ? st : TSDF_ERR_NO_DEVICE;
-}
-
 }  // namespace
 
 extern "C" {
@@ -100,11 +79,11 @@ int tsdf_depth16_widen_hip(const uint16_t *d_src, int64_t n_px, int shift, float
   if (n_px < 0 || shift < 0 || shift > TSDF_DEPTH16_MAX_SHIFT) return TSDF_ERR_INVALID_ARG;
   if (n_px == 0) return TSDF_OK;
   if (!d_src || !d_dst) return TSDF_ERR_INVALID_ARG;
-  const uintptr_t sa = reinterpret_cast<uintptr_t>(d_src), da = reinterpret_cast<uintptr_t>(d_dst);
-  if ((sa & 1) || (da & 3)) return TSDF_ERR_INVALID_ARG;
+  if (misaligned(d_src, 1) || misaligned(d_dst, 3)) return TSDF_ERR_INVALID_ARG;
   const int cus = device_cus();
   if (cus < 0) return cus;
 
+  const uintptr_t da = reinterpret_cast<uintptr_t>(d_dst);
   int64_t head = (int64_t)(((16 - (da & 15)) & 15) >> 2);   // pixels up to the destination's next 16-byte boundary
   if (head > n_px) head = n_px;
   const int64_t groups = (n_px - head) / 8;
@@ -115,7 +94,7 @@ int tsdf_depth16_widen_hip(const uint16_t *d_src, int64_t n_px, int shift, float
   const float scale = 1.0f / (float)(1 << shift);
   hipLaunchKernelGGL(tsdf_depth16_widen_kernel, dim3((unsigned)blocks), dim3(kWG), 0, static_cast<hipStream_t>(hip_stream),
                      d_src, n_px, head, groups, scale, d_dst);
-  return hipGetLastError() == hipSuccess ? TSDF_OK : TSDF_ERR_LAUNCH;
+  return launched();
 }
 
 }  // extern "C"

@@ -45,13 +45,14 @@
 // inter-workgroup communication in the fused kernel (XCD placement is irrelevant), no CPU fallback, gfx950 only.
 //
 // One translation unit; the pieces (all inside the anonymous namespace below, in this order):
+//   device.inc   host preamble shared with the extension libraries: check_device, device_cus, launched, misaligned
 //   common.inc   constants, types, VALU / DPP / float64 helpers
 //   phase1.inc   row stream -> extents (AABB) -> grid placement
 //   phase2.inc   the voxel pass, plain and augmented; gather sources, projection tables, volume stores
 //   frame.inc    kernel arguments, LDS layout, group barrier, per-frame helpers, LDS-DMA staging, table fill
 //   queue.inc    per-(device, stream) work-queue words and exchange mailboxes, device and host side
 //   kernels.inc  tsdf_fused_kernel, tsdf_split_kernel, tsdf_normalize_kernel, tsdf_project_kernel, tsdf_pose_error_kernel
-//   launch.inc   host side of a call: device check, split plan, instantiation choice, argument marshalling
+//   launch.inc   host side of a call: split plan, instantiation choice, argument marshalling
 //   cloud.inc    tsdf_point_cloud_kernel and its host side (back-projected, resampled point clouds)
 //   cloudgrid.inc  tsdf_cloud_grid_kernel and its host side (grid placement from a point cloud: tsdf_f's first half)
 //   abi.inc      extern "C" — include/tsdf.h (and, under -DTSDF_DEBUG_HOOKS, include/tsdf_debug.h)
@@ -80,6 +81,7 @@
 
 namespace {
 
+#include "device.inc"    // host preamble: device check, launch status, alignment test (every library here has it)
 #include "common.inc"    // constants, types, VALU / DPP / float64 helpers
 #include "phase1.inc"    // row stream -> extents -> grid placement
 #include "phase2.inc"    // the voxel pass, plain and augmented

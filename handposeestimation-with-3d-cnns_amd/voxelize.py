@@ -524,6 +524,42 @@ def voxelize_aug(depth: torch.Tensor, offsets: torch.Tensor, headers: torch.Tens
     return out if gt is None else (out, gt_nor, gt_aug)
 
 
+_NO_STATE = object()
+
+
+def _draw_args(centres, n, index, counters, out, params, state=_NO_STATE):
+    """The one validation of :func:`aug_xforms` and :func:`aug_xforms_at` (``state``, ``counters``: the latter's only):
+    returns ``(device, n_src, n, xforms, stretch, rot)`` — the outputs allocated, or ``out`` validated; ``stretch`` and
+    ``rot`` are None without ``params``."""
+    _dev_check("centres", centres, torch.float32)
+    dev = centres.device
+    if centres.dim() != 2 or centres.shape[1] != 3:
+        raise ValueError("centres must have shape [N, 3]")
+    n_src = centres.shape[0]
+    if state is not _NO_STATE:
+        _dev_check("state", state, torch.int64, dev)
+        if state.numel() != 2:
+            raise ValueError("state must hold 2 elements: {key, counter0}")
+    for name, t in (("index", index), ("counters", counters)):
+        if t is None:
+            continue
+        _dev_check(name, t, torch.int64, dev, host_ok=True)
+        if t.dim() != 1:
+            raise ValueError(f"{name} must have shape [n]")
+        if n is not None and int(n) != t.numel():
+            raise ValueError(f"n must be the length of {name}" if t is index else "counters must have n entries")
+        n = t.numel()
+    n = n_src if n is None else int(n)
+    if n < 0:
+        raise ValueError("n must be >= 0")
+    if n and n_src < 1:
+        raise ValueError("centres holds no frame")
+    xf = _out("out", out, (n, 24), torch.float64, dev)
+    stretch = _out("stretch", None, (n,), torch.float64, dev) if params else None
+    rot = _out("rot", None, (n, 2), torch.int32, dev) if params else None
+    return dev, n_src, n, xf, stretch, rot
+
+
 def aug_xforms(centres: torch.Tensor, n: Optional[int] = None, index: Optional[torch.Tensor] = None, key: int = 0,
                counter0: int = 0, out: Optional[torch.Tensor] = None, want_params: bool = False):
     """The maps of a batch of fused augmentations, drawn on the GPU (``tsdf_aug_draw_hip`` of libtsdf_augment.so, one small
@@ -539,26 +575,7 @@ def aug_xforms(centres: torch.Tensor, n: Optional[int] = None, index: Optional[t
     ``(xforms, stretch float64[n], rot int32[n,2])``, rot = (rot_xy, rot_z) in degrees.  A position whose index is outside
     [0, N) gets the identity map and a NaN stretch."""
     A = _lib.load_augment()
-    _dev_check("centres", centres, torch.float32)
-    dev = centres.device
-    if centres.dim() != 2 or centres.shape[1] != 3:
-        raise ValueError("centres must have shape [N, 3]")
-    n_src = centres.shape[0]
-    if index is not None:
-        _dev_check("index", index, torch.int64, dev, host_ok=True)
-        if index.dim() != 1:
-            raise ValueError("index must have shape [n]")
-        if n is not None and int(n) != index.numel():
-            raise ValueError("n must be the length of index")
-        n = index.numel()
-    n = n_src if n is None else int(n)
-    if n < 0:
-        raise ValueError("n must be >= 0")
-    if n and n_src < 1:
-        raise ValueError("centres holds no frame")
-    xf = _out("out", out, (n, 24), torch.float64, dev)
-    stretch = _out("stretch", None, (n,), torch.float64, dev) if want_params else None
-    rot = _out("rot", None, (n, 2), torch.int32, dev) if want_params else None
+    dev, n_src, n, xf, stretch, rot = _draw_args(centres, n, index, None, out, want_params)
     if n:
         m64 = (1 << 64) - 1
         _call(dev, A.tsdf_aug_draw_hip, [centres.data_ptr(), n_src, _ptr(index), n, int(key) & m64, int(counter0) & m64, None,
@@ -606,31 +623,7 @@ def aug_xforms_at(centres: torch.Tensor, state: torch.Tensor, n: Optional[int] =
     ``return_params`` ``(xforms, stretch float64[n], rot int32[n,2])``.  A position whose index is outside [0, N) gets the
     identity map and a NaN stretch."""
     A = _lib.load_augstep()
-    _dev_check("centres", centres, torch.float32)
-    dev = centres.device
-    if centres.dim() != 2 or centres.shape[1] != 3:
-        raise ValueError("centres must have shape [N, 3]")
-    n_src = centres.shape[0]
-    _dev_check("state", state, torch.int64, dev)
-    if state.numel() != 2:
-        raise ValueError("state must hold 2 elements: {key, counter0}")
-    for name, t in (("index", index), ("counters", counters)):
-        if t is None:
-            continue
-        _dev_check(name, t, torch.int64, dev, host_ok=True)
-        if t.dim() != 1:
-            raise ValueError(f"{name} must have shape [n]")
-        if n is not None and int(n) != t.numel():
-            raise ValueError(f"n must be the length of {name}" if t is index else "counters must have n entries")
-        n = t.numel()
-    n = n_src if n is None else int(n)
-    if n < 0:
-        raise ValueError("n must be >= 0")
-    if n and n_src < 1:
-        raise ValueError("centres holds no frame")
-    xf = _out("out", out, (n, 24), torch.float64, dev)
-    stretch = _out("stretch", None, (n,), torch.float64, dev) if return_params else None
-    rot = _out("rot", None, (n, 2), torch.int32, dev) if return_params else None
+    dev, n_src, n, xf, stretch, rot = _draw_args(centres, n, index, counters, out, return_params, state)
     if n:
         _call(dev, A.tsdf_aug_draw_at_hip, [centres.data_ptr(), n_src, _ptr(index), n, state.data_ptr(), _ptr(counters), None,
                                             xf.data_ptr(), _ptr(stretch), _ptr(rot)], 6)

@@ -4,10 +4,10 @@ libtsdf_augment.so is checked as far as it goes without a GPU — exports, versi
 import ctypes
 import itertools
 import os
-import subprocess
 
 import numpy as np
 import pytest
+from abi_util import declared_functions, exported
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 M = 1 << 64
@@ -88,20 +88,12 @@ def test_device_key_is_injective_over_small_arguments(pkg):
     assert aug.device_key(9, 1, 0) == aug._mix((aug._mix((aug._mix(9) + 1) % M) + 0) % M) == 902413603941569471
 
 
-def declared_functions():
-    import re
-    text = open(os.path.join(ROOT, "include", "tsdf_augment.h")).read()
-    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    return sorted(set(re.findall(r"\b(tsdf_\w+)\s*\(", text)))
-
-
 def test_augment_library_exports_exactly_its_header(pkg):
-    assert declared_functions() == ["tsdf_aug_draw_hip", "tsdf_augment_version"]
-    path = pkg._lib.AUGMENT_LIB_PATH
-    out = subprocess.run(["nm", "-D", "--defined-only", path], capture_output=True, text=True, check=True).stdout
-    rows = [ln.split() for ln in out.splitlines() if ln.strip()]
-    assert sorted(r[-1] for r in rows if r[-2] in "TtWw") == declared_functions()      # the functions it defines
-    assert sorted(r[-1] for r in rows if r[-1].startswith("tsdf_")) == declared_functions()
+    want = declared_functions("tsdf_augment.h")
+    assert want == ["tsdf_aug_draw_hip", "tsdf_augment_version"]
+    funcs, named = exported(pkg._lib.AUGMENT_LIB_PATH)
+    assert funcs == want                                                               # the functions it defines
+    assert named == want
     A = pkg._lib.load_augment()
     assert A.tsdf_augment_version() == 1 == pkg._lib.AUGMENT_VERSION
     assert pkg._lib.load_augment() is A
@@ -109,8 +101,9 @@ def test_augment_library_exports_exactly_its_header(pkg):
 
 
 def test_missing_augment_library_names_the_make_target(pkg, monkeypatch):
-    monkeypatch.setattr(pkg._lib, "_augment_lib", None)
-    monkeypatch.setattr(pkg._lib, "AUGMENT_LIB_PATH", os.path.join(ROOT, "build", "no_such_libtsdf_augment.so"))
+    monkeypatch.delitem(pkg._lib._ext_libs, "augment", raising=False)
+    monkeypatch.setitem(pkg._lib._EXTS, "augment", pkg._lib._EXTS["augment"]._replace(
+        path=os.path.join(ROOT, "build", "no_such_libtsdf_augment.so")))
     with pytest.raises(ImportError, match="csrc augment"):
         pkg._lib.load_augment()
 

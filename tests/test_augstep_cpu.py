@@ -3,26 +3,13 @@ without a GPU — exports, version, argument checks before device work —, the 
 ``aug`` / ``graph`` values of the consumers, and the numpy side of the per-frame contract."""
 import ctypes
 import os
-import re
-import subprocess
 
 import numpy as np
 import pytest
+from abi_util import declared_functions, exported
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 M = 1 << 64
-
-
-def declared_functions(header):
-    text = open(os.path.join(ROOT, "include", header)).read()
-    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    return sorted(set(re.findall(r"\b(tsdf_\w+)\s*\(", text)))
-
-
-def exported(path):
-    out = subprocess.run(["nm", "-D", "--defined-only", path], capture_output=True, text=True, check=True).stdout
-    rows = [ln.split() for ln in out.splitlines() if ln.strip()]
-    return sorted(r[-1] for r in rows if r[-2] in "TtWw"), sorted(r[-1] for r in rows if r[-1].startswith("tsdf_"))
 
 
 def test_augstep_library_exports_exactly_its_header(pkg):
@@ -42,8 +29,9 @@ def test_augstep_library_exports_exactly_its_header(pkg):
 
 
 def test_missing_augstep_library_names_the_make_target(pkg, monkeypatch):
-    monkeypatch.setattr(pkg._lib, "_augstep_lib", None)
-    monkeypatch.setattr(pkg._lib, "AUGSTEP_LIB_PATH", os.path.join(ROOT, "build", "no_such_libtsdf_augstep.so"))
+    monkeypatch.delitem(pkg._lib._ext_libs, "augstep", raising=False)
+    monkeypatch.setitem(pkg._lib._EXTS, "augstep", pkg._lib._EXTS["augstep"]._replace(
+        path=os.path.join(ROOT, "build", "no_such_libtsdf_augstep.so")))
     with pytest.raises(ImportError, match="csrc augstep"):
         pkg._lib.load_augstep()
 

@@ -5,12 +5,12 @@ under the CPU sanitizers as a stand-alone program, and the dataset's refusal of 
 ``q.astype(float32) * float32(2.0 ** -k)`` — and every comparison is exact.  Nothing here touches a GPU."""
 import ctypes
 import os
-import re
 import struct
 import subprocess
 
 import numpy as np
 import pytest
+from abi_util import declared_functions, exported
 
 torch = pytest.importorskip("torch")
 
@@ -21,18 +21,6 @@ f32 = np.float32
 
 def bits(a):
     return np.ascontiguousarray(a, np.float32).view(np.uint32)
-
-
-def declared_functions(header):
-    text = open(os.path.join(ROOT, "include", header)).read()
-    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    return sorted(set(re.findall(r"\b(tsdf_\w+)\s*\(", text)))
-
-
-def exported(path):
-    out = subprocess.run(["nm", "-D", "--defined-only", path], capture_output=True, text=True, check=True).stdout
-    rows = [ln.split() for ln in out.splitlines() if ln.strip()]
-    return sorted(r[-1] for r in rows if r[-2] in "TtWw"), sorted(r[-1] for r in rows if r[-1].startswith("tsdf_"))
 
 
 def frames_at(synth, n, k, seed0=700):
@@ -358,8 +346,9 @@ def test_library_exports_exactly_its_header(pkg):
 
 
 def test_missing_library_names_the_make_target(pkg, monkeypatch):
-    monkeypatch.setattr(pkg._lib, "_depth16_lib", None)
-    monkeypatch.setattr(pkg._lib, "DEPTH16_LIB_PATH", os.path.join(ROOT, "build", "no_such_libtsdf_depth16.so"))
+    monkeypatch.delitem(pkg._lib._ext_libs, "depth16", raising=False)
+    monkeypatch.setitem(pkg._lib._EXTS, "depth16", pkg._lib._EXTS["depth16"]._replace(
+        path=os.path.join(ROOT, "build", "no_such_libtsdf_depth16.so")))
     with pytest.raises(ImportError, match="csrc depth16"):
         pkg._lib.load_depth16()
     with pytest.raises(ImportError, match="csrc depth16"):
