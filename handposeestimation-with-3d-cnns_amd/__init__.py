@@ -22,15 +22,18 @@ The reference's process(), batched:      cloud_grids (grid placed on a cloud's e
 Packs with 16-bit depth:                 packing.depth16_shift, PackedFrames.to_depth16 / to_float32 (TSDFPK02, lossless or
                                          refused), widen_depth16 (libtsdf_depth16.so, include/tsdf_depth16.h); the loaders
                                          upload uint16 and widen on the GPU
+Volumes in the cloud's principal axes:   obb_xforms (per-frame OBB maps from the depth alone: libtsdf_obb.so,
+                                         include/tsdf_obb.h), voxelize_obb, invert_xforms, ResidentLoader(frame="obb")
 """
 from . import _lib  # noqa: F401
 from ._lib import TsdfCam, TsdfError, default_cam  # noqa: F401
-from .voxelize import (AabbBatch, AugmentedStep, CloudGridBatch, PointCloudBatch, PoseError, ProcessAugBatch, ProcessBatch, TsdfBatch,  # noqa: F401
+from .voxelize import (AabbBatch, AugmentedStep, CloudGridBatch, ObbBatch, PointCloudBatch, PoseError, ProcessAugBatch, ProcessBatch, TsdfBatch,  # noqa: F401
                        aabb,
                        aug_state, aug_xforms, aug_xforms_at, cloud_grids, denormalize_joints, empty_batch,
                        frames_within, joints_within, normalize_joints, point_clouds, pose_error, process_batch, process_batch_aug,
                        project_joints, release_stream, transform_joints, voxel_pixels, voxelize_aug_grid,
-                       voxelize, voxelize_aug, voxelize_grid, voxelize_indexed, voxelize_labels, widen_depth16)
+                       voxelize, voxelize_aug, voxelize_grid, voxelize_indexed, voxelize_labels, widen_depth16,
+                       invert_xforms, obb_xforms, voxelize_obb)
 from .pca import JointPCA, fit_joint_pca  # noqa: F401
 from . import augment, dataset, export, packing, pca, shard, synth  # noqa: F401
 from .dataset import MSRA_Dataset, MSRADepthDataset, ResidentLoader, VoxelBatch, VoxelLoader  # noqa: F401
@@ -44,4 +47,4 @@ __all__ = ["voxelize", "voxelize_labels", "voxelize_indexed", "ResidentLoader", 
            "pca", "JointPCA", "fit_joint_pca", "project_joints", "pose_error", "PoseError", "joints_within", "frames_within",
            "point_clouds", "PointCloudBatch", "cloud_grids", "CloudGridBatch", "process_batch", "ProcessBatch", "aug_xforms",
            "aug_xforms_at", "aug_state", "AugmentedStep", "voxelize_aug_grid", "transform_joints", "process_batch_aug",
-           "ProcessAugBatch", "widen_depth16"]
+           "ProcessAugBatch", "widen_depth16", "obb_xforms", "voxelize_obb", "invert_xforms", "ObbBatch"]

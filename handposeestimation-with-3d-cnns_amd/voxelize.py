@@ -932,3 +932,58 @@ def widen_depth16(src_u16: torch.Tensor, shift: int, out: Optional[torch.Tensor]
     if src_u16.numel():
         _call(dev, D.tsdf_depth16_widen_hip, [src_u16.data_ptr(), src_u16.numel(), shift, out.data_ptr(), None], 4)
     return out
+
+
+class ObbBatch(NamedTuple):
+    xforms: torch.Tensor        # float64[n,24]  forward rows then inverse rows: what voxelize_aug / voxelize_indexed take
+    status: torch.Tensor        # int32[n]       (_lib.TSDF_FRAME_*)
+    count: torch.Tensor         # float64[n]     valid pixels N (an exact integer; a view of the moments row)
+    mean: torch.Tensor          # float64[n,3]   the centroid mu
+    cov: torch.Tensor           # float64[n,6]   xx xy xz yy yz zz, divisor N
+    eigenvalues: torch.Tensor   # float64[n,3]   descending
+
+
+def obb_xforms(depth: torch.Tensor, offsets: torch.Tensor, headers: torch.Tensor, cam: Optional[_lib.TsdfCam] = None,
+               out: Optional[torch.Tensor] = None) -> ObbBatch:
+    """The principal-axis (oriented-bounding-box) map of every frame, computed on the GPU (``tsdf_obb_xforms_hip`` of
+    libtsdf_obb.so; include/tsdf_obb.h has the contract): the rotation about the cloud's centroid that turns its principal
+    axes into x (largest extent), y and z (smallest), signs by HandPointNet's convention.  Feed ``xforms`` to
+    :func:`voxelize_aug` and the volume, ``max_l`` / ``mid_p`` and the labels no longer depend on how the hand is turned
+    in the image plane.  The map is rigid: distances between joints, and pose error, are what they are in the camera frame.
+
+    depth / offsets / headers as for :func:`voxelize`; ``out``: optional float64[n,24] to write the maps into (it is
+    ``ObbBatch.xforms`` then).  A frame with a bad header (status 2) or fewer than 3 valid pixels, non-finite or all-equal
+    points (status 1) gets the identity map and zero moments.  ``count`` / ``mean`` / ``cov`` / ``eigenvalues`` are views
+    of one float64[n,16] tensor.  One launch on the current stream, no synchronisation."""
+    O = _lib.load_obb()
+    dev, n, _ = _pack(_lib.load(), depth, offsets, headers)
+    xf = _out("out", out, (n, 24), torch.float64, dev)
+    mo = _out("moments", None, (n, 16), torch.float64, dev)
+    st = _out("status", None, (n,), torch.int32, dev)
+    if n:
+        _call(dev, O.tsdf_obb_xforms_hip, [depth.data_ptr(), depth.numel(), offsets.data_ptr(), headers.data_ptr(), n,
+                                           _cam(cam), None, xf.data_ptr(), mo.data_ptr(), st.data_ptr()], 6)
+    return ObbBatch(xf, st, mo[:, 0], mo[:, 1:4], mo[:, 4:10], mo[:, 10:13])
+
+
+def voxelize_obb(depth: torch.Tensor, offsets: torch.Tensor, headers: torch.Tensor, res: int = 32, layout: str = "czyx",
+                 cam: Optional[_lib.TsdfCam] = None, gt: Optional[torch.Tensor] = None, clamp: bool = True):
+    """Volumes cut in every cloud's own principal axes: :func:`obb_xforms` followed by :func:`voxelize_aug` on the same
+    stream, nothing on the host in between.  Returns ``(TsdfBatch, xforms)``, or with ``gt`` (float32[n,3J] on the GPU)
+    ``(TsdfBatch, gt_nor, gt_obb, xforms)``: ``gt_obb`` are the joints in the mapped frame, ``gt_nor`` their labels;
+    ``max_l`` / ``mid_p`` are in the mapped frame, as for :func:`voxelize_aug`.  Predictions go back to the camera frame
+    with ``transform_joints(pred, invert_xforms(xforms))``."""
+    xf = obb_xforms(depth, offsets, headers, cam=cam).xforms
+    r = voxelize_aug(depth, offsets, headers, xf, res=res, layout=layout, cam=cam, gt=gt, clamp=clamp)
+    return (r, xf) if gt is None else (r[0], r[1], r[2], xf)
+
+
+def invert_xforms(xforms: torch.Tensor) -> torch.Tensor:
+    """The same maps with the forward and inverse halves swapped (float64[n,24] -> float64[n,24]; a pure tensor
+    operation, on whatever device ``xforms`` lives): ``transform_joints(x, invert_xforms(xf))`` carries joints of the mapped
+    frame back to the camera's."""
+    if not isinstance(xforms, torch.Tensor):
+        raise TypeError("xforms must be a torch.Tensor")
+    if xforms.dim() != 2 or xforms.shape[1] != 24:
+        raise ValueError("xforms must have shape [n, 24] (forward rows then inverse rows)")
+    return torch.cat([xforms[:, 12:], xforms[:, :12]], dim=1)
