@@ -25,19 +25,23 @@ reader's flip restores the camera-frame sign.
 """
 from __future__ import annotations
 
+import ctypes
 import os
 import sys
 import queue
 import threading
+import warnings
 from typing import Iterator, List, NamedTuple, Optional, Sequence, Tuple, Union
 
 import numpy as np
 import torch
 import torch.utils.data as data
 
-from . import packing, shard
-from .voxelize import (TsdfBatch, aug_xforms, denormalize_joints, empty_batch, normalize_joints, voxelize,  # noqa: F401
-                       voxelize_indexed, voxelize_labels, widen_depth16)
+from . import _lib, augment, packing, shard
+from .pca import JointPCA, fit_joint_pca
+from .voxelize import (AugmentedStep, TsdfBatch, _get_raw_stream, aabb, aug_state, aug_xforms, aug_xforms_at,  # noqa: F401
+                       denormalize_joints, empty_batch, normalize_joints, obb_xforms, project_joints, voxelize,
+                       voxelize_aug, voxelize_indexed, voxelize_labels, widen_depth16)
 
 
 def _common_depth_shift(packs: Sequence[packing.PackedFrames]) -> Optional[int]:
@@ -331,7 +335,28 @@ class _Staging:
         self.src = None                   # pinned tensor to upload from (the staging buffer, or a slice of a pinned pack)
 
 
-class VoxelLoader:
+class _BatchLoader:
+    """What :class:`VoxelLoader` and :class:`ResidentLoader` share: the arguments of :func:`plan_batches` and of the
+    voxelizer's launch, and the epoch's batches."""
+
+    def __init__(self, dataset: MSRADepthDataset, batch_size: int, device, res, shuffle, seed, drop_last, rank, world,
+                 labels, clamp, layout, balance):
+        self.balance = balance
+        self.ds, self.bs, self.device, self.res = dataset, int(batch_size), torch.device(device), res
+        self.shuffle, self.seed, self.drop_last = shuffle, seed, drop_last
+        self.rank, self.world = rank, world
+        self.labels, self.clamp, self.layout = labels, clamp, layout
+        self.epoch = 0
+
+    def _batches(self) -> List[np.ndarray]:
+        return plan_batches(len(self.ds), self.bs, self.rank, self.world, self.shuffle, self.seed, self.epoch,
+                            self.drop_last, self.ds.pixels() if self.balance == "pixels" else None, self.balance)
+
+    def __len__(self) -> int:
+        return len(self._batches())
+
+
+class VoxelLoader(_BatchLoader):
     """Batches of voxel grids produced on the fly.
 
     A worker thread packs the next batch straight into one of TWO reusable pinned staging sets (no allocation
@@ -349,23 +374,12 @@ class VoxelLoader:
         """``balance``: how ranks split the frames (:func:`plan_batches`): ``"frames"`` (default) gives every rank the same
         number of batches — required when the consumer synchronises per batch (DDP); ``"pixels"`` equalises the
         voxelization work instead (export jobs)."""
-        self.balance = balance
-        self.ds, self.bs, self.device, self.res = dataset, int(batch_size), torch.device(device), res
-        self.shuffle, self.seed, self.drop_last = shuffle, seed, drop_last
-        self.rank, self.world = rank, world
-        self.labels, self.clamp, self.layout = labels, clamp, layout
+        super().__init__(dataset, batch_size, device, res, shuffle, seed, drop_last, rank, world, labels, clamp, layout,
+                         balance)
         self.max_px = int(max_pixels) if max_pixels else self.bs * 320 * 240
-        self.epoch = 0
         self.pin_packs = pin_packs
         self._sets: Optional[List[_Staging]] = None
         self._copy_stream = None
-
-    def _batches(self) -> List[np.ndarray]:
-        return plan_batches(len(self.ds), self.bs, self.rank, self.world, self.shuffle, self.seed, self.epoch,
-                            self.drop_last, self.ds.pixels() if self.balance == "pixels" else None, self.balance)
-
-    def __len__(self) -> int:
-        return len(self._batches())
 
     def __iter__(self) -> Iterator[VoxelBatch]:
         batches = self._batches()
@@ -468,7 +482,6 @@ class ResidentPacks:
         pbase = np.concatenate([[0], np.cumsum(px)])
         fbase = np.concatenate([[0], np.cumsum(nf)])
         self.depth = torch.empty(int(pbase[-1]), dtype=torch.float32, device=device)
-        import warnings
         with warnings.catch_warnings():      # (a memory-mapped pack is read-only: torch warns, and we only read)
             warnings.simplefilter("ignore", UserWarning)
             for k, pk in enumerate(packs):   # (a memory-mapped pack is read here, once)
@@ -493,7 +506,7 @@ class ResidentPacks:
         return 4 * self.depth.numel()
 
 
-class ResidentLoader:
+class ResidentLoader(_BatchLoader):
     """Batches of voxel grids from a dataset that LIVES ON THE GPU.
 
     All of MSRA is 76.5 k crops = 4.8 GB; an MI355X has 288 GB.  So instead of feeding crops over the link batch after
@@ -564,13 +577,10 @@ class ResidentLoader:
         self.obb = None          # frame="obb": the maps of all resident frames, float64[N,24] on the device
         self.obb_status = None   # ... and their status, int32[N]
         self._step = None  # graph=True: the AugmentedStep of full batches
-        self.balance = balance
+        self._mapped = self.augment or frame == "obb"   # every launch takes one map per frame (_maps)
         self.prefetch, self.ring = int(prefetch), int(ring)
-        self.ds, self.bs, self.device, self.res = dataset, int(batch_size), torch.device(device), res
-        self.shuffle, self.seed, self.drop_last = shuffle, seed, drop_last
-        self.rank, self.world = rank, world
-        self.labels, self.clamp, self.layout = labels, clamp, layout
-        self.epoch = 0
+        super().__init__(dataset, batch_size, device, res, shuffle, seed, drop_last, rank, world, labels, clamp, layout,
+                         balance)
         self._dev = None   # (depth, offsets, headers, gt) of all packs, on the device
         self._g = None     # dataset frame -> frame of the concatenated packs
         self._idx = None   # two pinned index buffers + the events of the launches that read them
@@ -583,22 +593,18 @@ class ResidentLoader:
         rp = ResidentPacks(self.ds, self.device)
         self._dev = (rp.depth, rp.offsets, rp.headers, rp.gt)
         self._g = rp.frame
-        from . import _lib
         # (batches of up to 32 frames hand their index over by value — tsdf_voxelize_indexed_host_hip —, which an ordinary
         # CPU tensor selects in voxelize_indexed; larger ones, and augmented ones, are read from page-locked memory)
-        pin = self.bs > _lib.INLINE_INDEX_MAX or self.augment or self.frame == "obb"
+        pin = self.bs > _lib.INLINE_INDEX_MAX or self._mapped
         self._idx = [(torch.empty(self.bs, dtype=torch.int64).pin_memory() if pin else torch.empty(self.bs, dtype=torch.int64),
                       torch.cuda.Event()) for _ in range(2)]
         self._used = [False, False]
         self._mid = None
         if self.frame == "obb":   # every resident frame's map, once: one launch over the pack
-            from .voxelize import obb_xforms
             ob = obb_xforms(rp.depth, rp.offsets, rp.headers)
             self.obb, self.obb_status = ob.xforms, ob.status
         if self.augment:   # the centres the maps turn about: every frame's own grid centre, one AABB launch over the pack
-            from .voxelize import aabb
-            d, o, h, _ = self._dev
-            mid = aabb(d, o, h, res=self.res).grid[:, :3]
+            mid = aabb(rp.depth, rp.offsets, rp.headers, res=self.res).grid[:, :3]
             if self.device_draws:   # the centres stay where the launch left them; one map buffer per launch in flight
                 self._mid = mid.contiguous()
                 self._xf = torch.empty((self.ring if self.prefetch > 1 else 2, self.bs * self.prefetch, 24),
@@ -606,13 +612,6 @@ class ResidentLoader:
             else:
                 self._mid = mid.cpu().numpy().astype(np.float64)
                 self._xf = [torch.empty((self.bs, 24), dtype=torch.float64).pin_memory() for _ in range(2)]
-
-    def _batches(self) -> List[np.ndarray]:
-        return plan_batches(len(self.ds), self.bs, self.rank, self.world, self.shuffle, self.seed, self.epoch,
-                            self.drop_last, self.ds.pixels() if self.balance == "pixels" else None, self.balance)
-
-    def __len__(self) -> int:
-        return len(self._batches())
 
     def __iter__(self) -> Iterator[VoxelBatch]:
         batches = self._batches()
@@ -623,12 +622,35 @@ class ResidentLoader:
             return self._iter_blocks(batches, self.epoch)
         return self._iter_single(batches, self.epoch)
 
+    def _epoch_key(self, epoch: int) -> int:
+        """augment="device": the key the epoch's frames draw under (their counters are their places in the epoch)."""
+        return augment.device_key(self.seed, epoch, self.rank) if self.device_draws else 0
+
+    def _host_draw(self, gidx: np.ndarray, batches, epoch: int, k0: int = 0) -> np.ndarray:
+        """augment=True: the maps of batches ``k0, k0 + 1, ...`` of the epoch (``gidx``: their pack frames back to back),
+        one generator per batch, so that a batch's maps do not depend on ``prefetch``."""
+        xf = np.empty((gidx.size, 24), np.float64)
+        pos = 0
+        for k, b in enumerate(batches, k0):
+            xf[pos:pos + b.size] = augment.random_affines(self._mid[gidx[pos:pos + b.size]],
+                                                          rng=(self.seed, epoch, self.rank, k))[0]
+            pos += b.size
+        return xf
+
+    def _maps(self, index: torch.Tensor, slot: int, key: int, pos: int, drawn: Optional[torch.Tensor]):
+        """The maps of one launch over pack frames ``index``: its rows of the resident OBB table (``index`` on the device),
+        a device draw into map buffer ``slot`` (on the launch stream; the buffer's last reader is the voxelizer launch
+        before the slot came round again) with the counters of epoch positions ``pos, pos + 1, ...``, or what the host
+        drew (``drawn``, on the device: the maps are read per voxel)."""
+        if self.frame == "obb":
+            return self.obb.index_select(0, index)
+        if self.device_draws:
+            return aug_xforms(self._mid, index=index, key=key, counter0=pos, out=self._xf[slot, :index.numel()])
+        return drawn
+
     def _iter_single(self, batches, epoch) -> Iterator[VoxelBatch]:
         depth, off, hdr, gt = self._dev
-        key, pos = 0, 0
-        if self.device_draws:
-            from . import augment as _aug
-            key = _aug.device_key(self.seed, epoch, self.rank)
+        key, pos = self._epoch_key(epoch), 0
         for k, b in enumerate(batches):
             cur = torch.cuda.current_stream(self.device)   # (per batch: the consumer may have switched streams)
             h_idx, done = self._idx[k & 1]
@@ -638,30 +660,26 @@ class ResidentLoader:
             gidx = self._g[b]
             if self.graph and n == self.bs:   # the captured step: index and {key, counter} in, its static outputs out
                 if self._step is None:
-                    from .voxelize import AugmentedStep
                     self._step = AugmentedStep(depth, off, hdr, n, gt=gt, centres=self._mid, res=self.res,
                                                layout=self.layout, clamp=self.clamp)
                 out, gt_nor, g = self._step.step(gidx, key, pos)
-                pos += n
-                yield VoxelBatch(out.tsdf, g, out.max_l, out.mid_p, out.status, gt_nor if self.labels else None)
-                continue
-            h_idx.numpy()[:n] = gidx
-            xf, idx = None, h_idx[:n]
-            if self.frame == "obb":   # the batch's rows of the resident table, gathered by its index on the device
-                idx = idx.to(self.device, non_blocking=True)
-                xf = self.obb.index_select(0, idx)
-            elif self.device_draws:   # (the buffer's last reader is the voxelizer launch `done` was recorded after)
-                xf = aug_xforms(self._mid, index=h_idx[:n], key=key, counter0=pos, out=self._xf[k & 1, :n])
-                pos += n
-            elif self.augment:
-                from . import augment as _aug
-                h_xf = self._xf[k & 1]
-                h_xf.numpy()[:n] = _aug.random_affines(self._mid[gidx], rng=(self.seed, epoch, self.rank, k))[0]
-                xf = h_xf[:n].to(self.device, non_blocking=True)   # (read per voxel: device memory, not the link)
-            out, gt_nor, g = voxelize_indexed(depth, off, hdr, idx, gt, res=self.res, layout=self.layout,
-                                              clamp=self.clamp, gt_copy=True, xforms=xf)
-            done.record(cur)
-            self._used[k & 1] = True
+            else:
+                h_idx.numpy()[:n] = gidx
+                xf, idx = None, h_idx[:n]
+                if self._mapped:
+                    drawn = None
+                    if self.frame == "obb":   # the table's rows are gathered by the batch's index on the device
+                        idx = idx.to(self.device, non_blocking=True)
+                    elif not self.device_draws:
+                        h_xf = self._xf[k & 1]
+                        h_xf.numpy()[:n] = self._host_draw(gidx, (b,), epoch, k)
+                        drawn = h_xf[:n].to(self.device, non_blocking=True)
+                    xf = self._maps(idx, k & 1, key, pos, drawn)
+                out, gt_nor, g = voxelize_indexed(depth, off, hdr, idx, gt, res=self.res, layout=self.layout,
+                                                  clamp=self.clamp, gt_copy=True, xforms=xf)
+                done.record(cur)
+                self._used[k & 1] = True
+            pos += n
             yield VoxelBatch(out.tsdf, g, out.max_l, out.mid_p, out.status, gt_nor if self.labels else None)
 
     # ---- prefetch > 1: one launch per block of `prefetch` batches ----
@@ -693,20 +711,10 @@ class ResidentLoader:
         flat = np.concatenate(batches)
         gidx = self._g[flat]
         d_idx = torch.from_numpy(np.ascontiguousarray(gidx)).to(self.device)
+        key = self._epoch_key(epoch)
         d_xf = None
-        key = 0
-        if self.device_draws:
-            from . import augment as _aug
-            key = _aug.device_key(self.seed, epoch, self.rank)
-        elif self.augment:   # the same draws as without prefetch: one generator per batch
-            from . import augment as _aug
-            xf = np.empty((flat.size, 24), np.float64)
-            pos = 0
-            for k, b in enumerate(batches):
-                xf[pos:pos + b.size] = _aug.random_affines(self._mid[gidx[pos:pos + b.size]],
-                                                           rng=(self.seed, epoch, self.rank, k))[0]
-                pos += b.size
-            d_xf = torch.from_numpy(xf).to(self.device)
+        if self.augment and not self.device_draws:
+            d_xf = torch.from_numpy(self._host_draw(gidx, batches, epoch)).to(self.device)
         pos = 0
         for blk, k0 in enumerate(range(0, len(batches), P)):
             mine = batches[k0:k0 + P]
@@ -718,13 +726,10 @@ class ResidentLoader:
             else:      # the epoch's last block: the leading part of the ring entry
                 o = TsdfBatch(out.tsdf[:nfr], out.max_l[:nfr], out.mid_p[:nfr], out.status[:nfr])
                 gn, gg = gt_nor[:nfr], g[:nfr]
-            xf = None if d_xf is None else d_xf[pos:pos + nfr]
-            if self.frame == "obb":
-                xf = self.obb.index_select(0, d_idx[pos:pos + nfr])
-            elif self.device_draws:   # one launch for the block's maps, into the ring entry's buffer, on the launch stream
-                xf = aug_xforms(self._mid, index=d_idx[pos:pos + nfr], key=key, counter0=pos,
-                                out=self._xf[blk % self.ring, :nfr])
-            voxelize_indexed(depth, off, hdr, d_idx[pos:pos + nfr], gt, res=self.res, layout=self.layout, clamp=self.clamp,
+            idx, xf = d_idx[pos:pos + nfr], None
+            if self._mapped:
+                xf = self._maps(idx, blk % self.ring, key, pos, None if d_xf is None else d_xf[pos:pos + nfr])
+            voxelize_indexed(depth, off, hdr, idx, gt, res=self.res, layout=self.layout, clamp=self.clamp,
                              out=o, out_gt_nor=gn, out_gt=gg, xforms=xf)
             pos += nfr
             if full:
@@ -908,16 +913,13 @@ class MSRA_Dataset(data.Dataset):
         self._aug_state = None   # ... {key, 0} on the device, and the grid centres of the resident packs' frames
         self._aug_mid = None
         if self.aug_device:
-            from . import augment as _aug
-            self._aug_key = _aug.device_key(aug_seed, 0, 0)
+            self._aug_key = augment.device_key(aug_seed, 0, 0)
         elif self.AUG:
-            from . import augment as _aug
-            self._aug_params = _aug.draw_params(self._n, aug_seed)
+            self._aug_params = augment.draw_params(self._n, aug_seed)
         # full mode (3D_CNN/dataset.py:165-180): the joint-PCA basis, and gt_pca as the item's fifth element
         self.pca = None
         self._cache_pca: Optional[torch.Tensor] = None
         if pca is not None and pca is not False:
-            from .pca import JointPCA, fit_joint_pca
             if pca is True:
                 if not train:
                     raise ValueError("pca=True fits on a TRAINING dataset; pass the training set's basis (its .pca, a "
@@ -945,8 +947,6 @@ class MSRA_Dataset(data.Dataset):
         if self._rp is None:
             self._rp = ResidentPacks(self.raw, self.device)
             if self.AUG:   # every frame's own grid centre (one AABB launch over the pack), then all maps at once
-                from . import augment as _aug
-                from .voxelize import aabb
                 rp = self._rp
                 mid = aabb(rp.depth, rp.offsets, rp.headers).grid[:, :3]
                 self._frame2 = np.ascontiguousarray(np.concatenate([rp.frame, rp.frame]))
@@ -957,52 +957,67 @@ class MSRA_Dataset(data.Dataset):
                 else:
                     mid = mid.cpu().numpy().astype(np.float64)[rp.frame]
                     self._xf_table = np.ascontiguousarray(np.concatenate(
-                        [_aug.identity_affines(self._n), _aug.affines_from_params(mid, *self._aug_params)]))
+                        [augment.identity_affines(self._n), augment.affines_from_params(mid, *self._aug_params)]))
         return self._rp
 
     def _device_state(self) -> torch.Tensor:
         if self._aug_state is None:
-            from .voxelize import aug_state
             self._aug_state = aug_state(self._aug_key, 0, self.device)
         return self._aug_state
 
     def _device_maps(self, idx: np.ndarray) -> torch.Tensor:
         """aug="device", resident: the maps of items ``idx`` (identity for the plain ones), one launch."""
-        from .voxelize import aug_xforms_at
         return aug_xforms_at(self._aug_mid, self._device_state(),
                              index=torch.from_numpy(self._draw_frame[idx]).to(self.device),
                              counters=torch.from_numpy(self._draw_counter[idx]).to(self.device))
 
-    def _aug_batch_host_fed(self, idx: np.ndarray):
-        """aug=True on a dataset that is not resident: upload the frames, one AABB launch for their centres, then the
-        augmented entry (identity maps for the plain items)."""
-        from . import augment as _aug
-        from .voxelize import aabb, aug_xforms_at, voxelize_aug
+    def _voxelize_items(self, idx: np.ndarray, clamp: bool = True):
+        """Items ``idx`` as device tensors, by one voxelizer launch: ``(TsdfBatch, gt, gt_nor, gt_pca)``.  ``gt_nor`` are the
+        launch's labels (clamped unless ``clamp=False``; None from the plain entry, which writes none), ``gt_pca`` is None
+        without a basis.  With ``aug`` the launch is the augmented entry — plain items under the identity map — and
+        ``gt`` are the mapped joints."""
+        dev = self.device
+        kw = {} if self.pca is None else {"pca": self.pca, "k": self.PCA_SZ}
+        if self.resident:   # the batch is drawn by index from the packs on the device
+            rp = self._resident_packs()
+            xf = None
+            if self.aug_device:
+                xf = self._device_maps(idx)
+            elif self.AUG:
+                xf = torch.from_numpy(self._xf_table[idx]).to(dev)
+            frame = self._frame2 if self.AUG else rp.frame
+            r = voxelize_indexed(rp.depth, rp.offsets, rp.headers, torch.from_numpy(frame[idx]).to(dev), rp.gt,
+                                 clamp=clamp, gt_copy=True, xforms=xf, **kw)
+            return r[0], r[2], r[1], (r[3] if kw else None)
         src = idx % self._n
         pk = self.raw.take(src)
-        depth, offsets, headers = pk.to_torch(self.device, pin=False, non_blocking=False)
-        if self.aug_device:   # AABB -> draw -> augmented entry: the centres and the maps never leave the device
-            mid = aabb(depth, offsets, headers).grid[:, :3].contiguous()
+        depth, offsets, headers = pk.to_torch(dev, pin=False, non_blocking=False)
+        gt = torch.from_numpy(np.ascontiguousarray(pk.gt)).to(dev)
+        if not self.AUG:
+            if not kw:
+                return voxelize(depth, offsets, headers, res=32), gt, None, None
+            out, gt_nor, gt_pca = voxelize_labels(depth, offsets, headers, gt, res=32, clamp=clamp, **kw)
+            return out, gt, gt_nor, gt_pca
+        # one AABB launch for the frames' centres, the maps about them, then the augmented entry
+        mid = aabb(depth, offsets, headers).grid[:, :3]
+        if self.aug_device:   # the centres and the maps never leave the device
             pos = np.where(idx < self._n, -1, np.arange(idx.size)).astype(np.int64)   # plain items: the identity map
-            xf = aug_xforms_at(mid, self._device_state(), index=torch.from_numpy(pos).to(self.device),
-                               counters=torch.from_numpy(np.ascontiguousarray(src, np.int64)).to(self.device))
-            gt = torch.from_numpy(np.ascontiguousarray(pk.gt)).to(self.device)
-            out, _, gt_aug = voxelize_aug(depth, offsets, headers, xf, res=32, gt=gt)
-            return out, gt_aug
-        mid = aabb(depth, offsets, headers).grid[:, :3].cpu().numpy().astype(np.float64)
-        st, rxy, rz = (p[src] for p in self._aug_params)
-        xf = _aug.affines_from_params(mid, st, rxy, rz)
-        plain = idx < self._n
-        xf[plain] = _aug.identity_affines(int(plain.sum()))
-        gt = torch.from_numpy(np.ascontiguousarray(pk.gt)).to(self.device)
-        out, _, gt_aug = voxelize_aug(depth, offsets, headers, torch.from_numpy(xf).to(self.device), res=32, gt=gt)
-        return out, gt_aug
+            xf = aug_xforms_at(mid.contiguous(), self._device_state(), index=torch.from_numpy(pos).to(dev),
+                               counters=torch.from_numpy(np.ascontiguousarray(src, np.int64)).to(dev))
+        else:
+            xf = augment.affines_from_params(mid.cpu().numpy().astype(np.float64), *(p[src] for p in self._aug_params))
+            plain = idx < self._n
+            xf[plain] = augment.identity_affines(int(plain.sum()))
+            xf = torch.from_numpy(xf).to(dev)
+        out, gt_nor, gt_aug = voxelize_aug(depth, offsets, headers, xf, res=32, gt=gt, clamp=clamp)
+        # (the augmented entry has no fused projection: project_joints gives the same bits from the launch's outputs)
+        gt_pca = project_joints(gt_aug, out.max_l, out.mid_p, self.pca, self.PCA_SZ) if kw else None
+        return out, gt_aug, gt_nor, gt_pca
 
     def _fit_labels(self) -> np.ndarray:
         """The normalised labels (no clamp) of every item whose frame status is OK, float32[N, C] on the host, in item
         order — what :func:`pca.fit_joint_pca` fits.  Plain items: the grid placement of the AABB launch (bit-identical
         to the voxelizer's); augmented items: the augmented entry's own labels."""
-        from .voxelize import aabb, normalize_joints
         n, dev, us = self._n, self.device, []
         if self.resident:
             rp = self._resident_packs()
@@ -1019,25 +1034,10 @@ class MSRA_Dataset(data.Dataset):
                 gt = torch.from_numpy(np.ascontiguousarray(pk.gt)).to(dev)
                 u = normalize_joints(gt, ab.grid[:, 3].contiguous(), ab.grid[:, :3].contiguous(), clamp=False)
                 us.append(u[ab.status == 0].cpu().numpy())
-        if self.AUG:
-            for a in range(n, 2 * n, self.block):
-                idx = np.arange(a, min(2 * n, a + self.block))
-                if self.resident:
-                    rp = self._rp
-                    out, u = voxelize_indexed(rp.depth, rp.offsets, rp.headers,
-                                              torch.from_numpy(self._frame2[idx]).to(dev), rp.gt, clamp=False,
-                                              xforms=self._device_maps(idx) if self.aug_device else
-                                              torch.from_numpy(self._xf_table[idx]).to(dev))
-                else:
-                    out, gt_aug = self._aug_batch_host_fed(idx)
-                    u = normalize_joints(gt_aug, out.max_l, out.mid_p, clamp=False)
-                us.append(u[out.status == 0].cpu().numpy())
+        for a in range(n, len(self), self.block):   # (the augmented items, where there are any)
+            out, _, u, _ = self._voxelize_items(np.arange(a, min(len(self), a + self.block)), clamp=False)
+            us.append(u[out.status == 0].cpu().numpy())
         return np.concatenate(us) if us else np.zeros((0, 63), np.float32)
-
-    def _with_pca(self, gt, max_l, mid_p):
-        """gt_pca of labels already on the device (``project_joints``: the paths that are not fused)."""
-        from .voxelize import project_joints
-        return project_joints(gt.contiguous(), max_l, mid_p, self.pca, self.PCA_SZ)
 
     def _tuples(self, out, gt, gt_pca, m: int):
         if gt_pca is None:
@@ -1046,19 +1046,7 @@ class MSRA_Dataset(data.Dataset):
 
     def _load_block(self, blk: int):
         a, b = blk * self.block, min(len(self.raw), (blk + 1) * self.block)
-        if self.resident:
-            rp = self._resident_packs()
-            r = voxelize_indexed(rp.depth, rp.offsets, rp.headers, torch.from_numpy(rp.frame[a:b]).to(self.device), rp.gt,
-                                 gt_copy=True, pca=self.pca, k=self.PCA_SZ if self.pca is not None else None)
-            self._cache, self._cache_gt = r[0], r[2]
-            self._cache_pca = r[3] if self.pca is not None else None
-        else:
-            pk = self.raw.take(np.arange(a, b))
-            depth, offsets, headers = pk.to_torch(self.device, pin=False, non_blocking=False)
-            self._cache = voxelize(depth, offsets, headers, res=32)
-            self._cache_gt = torch.from_numpy(np.ascontiguousarray(pk.gt)).to(self.device)
-            self._cache_pca = None if self.pca is None else \
-                self._with_pca(self._cache_gt, self._cache.max_l, self._cache.mid_p)
+        self._cache, self._cache_gt, _, self._cache_pca = self._voxelize_items(np.arange(a, b))
         self._cache_block = blk
 
     # ---- the pre-batched path: one C call per batch, nothing allocated, nothing sliced ----
@@ -1084,8 +1072,6 @@ class MSRA_Dataset(data.Dataset):
 
         def __init__(self, rp: "ResidentPacks", bs: int, ring: int, device, frame=None, xf_table=None, pca=None, k=0,
                      draw=None):
-            import ctypes
-            from . import _lib
             self._ctypes, self._lib = ctypes, _lib
             self.always_fresh = not _slot_guard_works()
             ring = max(2, int(ring))
@@ -1114,7 +1100,6 @@ class MSRA_Dataset(data.Dataset):
                 self._fresh(k)
             self.read = [torch.cuda.Event() for _ in range(self.iring // self.kGroup)]
             self.read_used = [False] * (self.iring // self.kGroup)
-            from .voxelize import _get_raw_stream
             self.raw_stream = _get_raw_stream if _get_raw_stream is not None else \
                 (lambda i: torch.cuda.current_stream(i).cuda_stream)
             self.cur_dev = getattr(torch._C, "_cuda_getDevice", torch.cuda.current_device)
@@ -1129,11 +1114,12 @@ class MSRA_Dataset(data.Dataset):
             self.by_value = xf_table is None and draw is None and bs <= _lib.INLINE_INDEX_MAX
             self.fn_host = self.L.tsdf_voxelize_indexed_host_hip if pca is None else \
                 self.L.tsdf_voxelize_indexed_host_pca_hip
+            # ... and of both aug forms: one map per batch position, read by the kernel next to the index
+            self.fn_aug = self.L.tsdf_voxelize_indexed_aug_hip if pca is None else self.L.tsdf_voxelize_indexed_pca_hip
             self.idx_buf = np.empty(bs, np.int64)
             self.idx_ptr = self.idx_buf.ctypes.data
             self.xf_take = None
-            if xf_table is not None:   # aug=True: one map per batch position, in page-locked memory the kernel reads
-                self.fn_aug = self.L.tsdf_voxelize_indexed_aug_hip if pca is None else self.L.tsdf_voxelize_indexed_pca_hip
+            if xf_table is not None:   # aug=True: the maps in page-locked memory
                 self.h_xf = torch.empty((self.iring, bs, 24), dtype=torch.float64).pin_memory()
                 self.h_xf_np = self.h_xf.numpy()
                 self.xf_rows = [self.h_xf_np[k] for k in range(self.iring)]
@@ -1144,7 +1130,6 @@ class MSRA_Dataset(data.Dataset):
             self.draw = None
             if draw is not None:
                 centres, state, frames, counters = draw
-                self.fn_aug = self.L.tsdf_voxelize_indexed_aug_hip if pca is None else self.L.tsdf_voxelize_indexed_pca_hip
                 self.fn_draw = _lib.load_augstep().tsdf_aug_draw_at_hip
                 self.draw = (centres, state)      # (kept alive: the launches read them by raw pointer)
                 self.draw_head = (centres.data_ptr(), int(centres.shape[0]))
@@ -1225,60 +1210,57 @@ class MSRA_Dataset(data.Dataset):
         k = f.next_slot()
         a = f.args[k]
         if f.by_value:                        # (the epoch's short last batch, or another current device)
+            fn = f.fn_host
             f.idx_buf[:n] = f.take(indices)
             with torch.cuda.device(f.device):
-                rc = f.fn_host(*f.head, f.idx_ptr, n, 32, None, 0, f.raw_stream(f.dev_index), *a)
-            if rc != 0:
-                from . import _lib
-                _lib.check(rc, "tsdf_voxelize_indexed_host_hip")
-            f.count += 1
-            if n == f.bs:
-                return f.results[k]
-            return [PreBatched(tuple(t[:n] for t in f.results[k][0].batch))]
-        ki = f.count % f.iring                # the index words' slot (page-locked ring of whole event groups)
-        within = ki & (f.kGroup - 1)
-        if within == 0 and f.read_used[ki >> 4]:
-            f.read[ki >> 4].synchronize()     # the launches that read this group's index words a ring ago are done
-        # dataset item -> pack frame, written where the kernel will read it; numpy checks the range (IndexError) and,
-        # like a Python list, counts negative indices from the end
-        if n == f.bs:
-            f.take(indices, out=f.rows[ki])
+                rc = fn(*f.head, f.idx_ptr, n, 32, None, 0, f.raw_stream(f.dev_index), *a)
         else:
-            f.h_idx_np[ki, :n] = f.take(indices)
-        if f.draw is not None:        # aug="device": one launch draws the batch's maps, the next one reads them
-            fr, cn = f.draw_rows[ki]
+            ki = f.count % f.iring            # the index words' slot (page-locked ring of whole event groups)
+            within = ki & (f.kGroup - 1)
+            if within == 0 and f.read_used[ki >> 4]:
+                f.read[ki >> 4].synchronize()     # the launches that read this group's index words a ring ago are done
+            # dataset item -> pack frame, written where the kernel will read it; numpy checks the range (IndexError) and,
+            # like a Python list, counts negative indices from the end
             if n == f.bs:
-                f.frame_take(indices, out=fr)
-                f.counter_take(indices, out=cn)
+                f.take(indices, out=f.rows[ki])
             else:
-                fr[:n] = f.frame_take(indices)
-                cn[:n] = f.counter_take(indices)
-            with torch.cuda.device(f.device):
-                stream = f.raw_stream(f.dev_index)
-                rc = f.fn_draw(*f.draw_head, f.draw_ptrs[ki][0], n, f.state_ptr, f.draw_ptrs[ki][1], stream, f.xf_ptr[ki],
-                               None, None)
-                if rc != 0:
-                    from . import _lib
-                    _lib.check(rc, "tsdf_aug_draw_at_hip")
-                rc = f.fn_aug(*f.head, f.idx_ptrs[ki], n, 32, None, 0, stream, f.xf_ptr[ki], *a)
-        elif f.xf_take is not None:   # aug=True: the batch's maps next to its indices
-            if n == f.bs:
-                f.xf_take(indices, axis=0, out=f.xf_rows[ki])
+                f.h_idx_np[ki, :n] = f.take(indices)
+            if f.draw is not None:        # aug="device": one launch draws the batch's maps, the next one reads them
+                fr, cn = f.draw_rows[ki]
+                if n == f.bs:
+                    f.frame_take(indices, out=fr)
+                    f.counter_take(indices, out=cn)
+                else:
+                    fr[:n] = f.frame_take(indices)
+                    cn[:n] = f.counter_take(indices)
+                with torch.cuda.device(f.device):
+                    stream = f.raw_stream(f.dev_index)
+                    fn = f.fn_draw
+                    rc = fn(*f.draw_head, f.draw_ptrs[ki][0], n, f.state_ptr, f.draw_ptrs[ki][1], stream, f.xf_ptr[ki],
+                            None, None)
+                    if rc == 0:
+                        fn = f.fn_aug
+                        rc = fn(*f.head, f.idx_ptrs[ki], n, 32, None, 0, stream, f.xf_ptr[ki], *a)
+            elif f.xf_take is not None:   # aug=True: the batch's maps next to its indices
+                fn = f.fn_aug
+                if n == f.bs:
+                    f.xf_take(indices, axis=0, out=f.xf_rows[ki])
+                else:
+                    f.h_xf_np[ki, :n] = f.xf_take(indices, axis=0)
+                with torch.cuda.device(f.device):
+                    rc = fn(*f.head, f.idx_ptrs[ki], n, 32, None, 0, f.raw_stream(f.dev_index), f.xf_ptr[ki], *a)
             else:
-                f.h_xf_np[ki, :n] = f.xf_take(indices, axis=0)
-            with torch.cuda.device(f.device):
-                rc = f.fn_aug(*f.head, f.idx_ptrs[ki], n, 32, None, 0, f.raw_stream(f.dev_index), f.xf_ptr[ki], *a)
-        elif f.cur_dev() == f.dev_index:
-            rc = f.fn(*f.head, f.idx_ptrs[ki], n, 32, None, 0, f.raw_stream(f.dev_index), *f.plain_xf, *a)
-        else:
-            with torch.cuda.device(f.device):
-                rc = f.fn(*f.head, f.idx_ptrs[ki], n, 32, None, 0, f.raw_stream(f.dev_index), *f.plain_xf, *a)
-        if within == f.kGroup - 1:
-            f.read[ki >> 4].record(torch.cuda.current_stream(f.device))
-            f.read_used[ki >> 4] = True
+                fn = f.fn
+                if f.cur_dev() == f.dev_index:
+                    rc = fn(*f.head, f.idx_ptrs[ki], n, 32, None, 0, f.raw_stream(f.dev_index), *f.plain_xf, *a)
+                else:
+                    with torch.cuda.device(f.device):
+                        rc = fn(*f.head, f.idx_ptrs[ki], n, 32, None, 0, f.raw_stream(f.dev_index), *f.plain_xf, *a)
+            if within == f.kGroup - 1:
+                f.read[ki >> 4].record(torch.cuda.current_stream(f.device))
+                f.read_used[ki >> 4] = True
         if rc != 0:
-            from . import _lib
-            _lib.check(rc, "tsdf_voxelize_indexed_hip")
+            _lib.check(rc, fn.__name__)
         f.count += 1
         if n == f.bs:
             return f.results[k]
@@ -1301,49 +1283,21 @@ class MSRA_Dataset(data.Dataset):
             a = f.args[k]
             rc = f.fn_host(*f.head, f.idx_ptr, f.bs, 32, None, 0, f.raw_stream(f.dev_index), *a)
             if rc != 0:
-                from . import _lib
                 _lib.check(rc, "tsdf_voxelize_indexed_host_hip")
             f.count += 1
             self._last = indices[-1]
             return f.results[k]
-        if self.resident:
-            self._resident_packs()
         if self.prebatched:
             if not indices:
                 raise IndexError("empty batch")
+            self._resident_packs()
             self._last = indices[-1]
             return self._fast_batch(indices)
         idx = np.asarray([int(i) for i in indices], np.int64)
         if idx.size and (idx.min() < 0 or idx.max() >= len(self)):
             raise IndexError(int(idx.max() if idx.max() >= len(self) else idx.min()))
         self._last = int(idx[-1]) if idx.size else self._last
-        kw = {} if self.pca is None else {"pca": self.pca, "k": self.PCA_SZ}
-        gt_pca = None
-        if self.AUG:
-            if self.resident:
-                rp = self._rp
-                xf = self._device_maps(idx) if self.aug_device else torch.from_numpy(self._xf_table[idx]).to(self.device)
-                r = voxelize_indexed(rp.depth, rp.offsets, rp.headers, torch.from_numpy(self._frame2[idx]).to(self.device),
-                                     rp.gt, gt_copy=True, xforms=xf, **kw)
-                out, gt = r[0], r[2]
-                gt_pca = r[3] if kw else None
-            else:
-                out, gt = self._aug_batch_host_fed(idx)
-                gt_pca = self._with_pca(gt, out.max_l, out.mid_p) if kw else None
-            return self._tuples(out, gt, gt_pca, idx.size)
-        if self.resident:
-            rp = self._rp
-            r = voxelize_indexed(rp.depth, rp.offsets, rp.headers, torch.from_numpy(rp.frame[idx]).to(self.device), rp.gt,
-                                 gt_copy=True, **kw)
-            out, gt = r[0], r[2]
-            return self._tuples(out, gt, r[3] if kw else None, idx.size)
-        pk = self.raw.take(idx)
-        depth, offsets, headers = pk.to_torch(self.device, pin=False, non_blocking=False)
-        gt = torch.from_numpy(np.ascontiguousarray(pk.gt)).to(self.device)
-        if kw:   # (the labels path of the same launch, for gt_pca)
-            out, _, gt_pca = voxelize_labels(depth, offsets, headers, gt, res=32, clamp=False, **kw)
-        else:
-            out = voxelize(depth, offsets, headers, res=32)
+        out, gt, _, gt_pca = self._voxelize_items(idx)
         return self._tuples(out, gt, gt_pca, idx.size)
 
     def _items_of(self, indices):
