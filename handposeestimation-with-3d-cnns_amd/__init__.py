@@ -24,6 +24,9 @@ Packs with 16-bit depth:                 packing.depth16_shift, PackedFrames.to_
                                          upload uint16 and widen on the GPU
 Volumes in the cloud's principal axes:   obb_xforms (per-frame OBB maps from the depth alone: libtsdf_obb.so,
                                          include/tsdf_obb.h), voxelize_obb, invert_xforms, ResidentLoader(frame="obb")
+Volumes in float16 / bfloat16:           voxelize_grid_lowp (the plain voxel pass narrowed in registers: libtsdf_lowp.so,
+                                         include/tsdf_lowp.h), voxelize_lowp, narrow_volumes, process_batch(dtype=...),
+                                         ResidentLoader(volume_dtype=...)
 """
 from . import _lib  # noqa: F401
 from ._lib import TsdfCam, TsdfError, default_cam  # noqa: F401
@@ -33,7 +36,7 @@ from .voxelize import (AabbBatch, AugmentedStep, CloudGridBatch, ObbBatch, Point
                        frames_within, joints_within, normalize_joints, point_clouds, pose_error, process_batch, process_batch_aug,
                        project_joints, release_stream, transform_joints, voxel_pixels, voxelize_aug_grid,
                        voxelize, voxelize_aug, voxelize_grid, voxelize_indexed, voxelize_labels, widen_depth16,
-                       invert_xforms, obb_xforms, voxelize_obb)
+                       invert_xforms, obb_xforms, voxelize_obb, narrow_volumes, voxelize_grid_lowp, voxelize_lowp)
 from .pca import JointPCA, fit_joint_pca  # noqa: F401
 from . import augment, dataset, export, packing, pca, shard, synth  # noqa: F401
 from .dataset import MSRA_Dataset, MSRADepthDataset, ResidentLoader, VoxelBatch, VoxelLoader  # noqa: F401
@@ -47,4 +50,5 @@ __all__ = ["voxelize", "voxelize_labels", "voxelize_indexed", "ResidentLoader", 
            "pca", "JointPCA", "fit_joint_pca", "project_joints", "pose_error", "PoseError", "joints_within", "frames_within",
            "point_clouds", "PointCloudBatch", "cloud_grids", "CloudGridBatch", "process_batch", "ProcessBatch", "aug_xforms",
            "aug_xforms_at", "aug_state", "AugmentedStep", "voxelize_aug_grid", "transform_joints", "process_batch_aug",
-           "ProcessAugBatch", "widen_depth16", "obb_xforms", "voxelize_obb", "invert_xforms", "ObbBatch"]
+           "ProcessAugBatch", "widen_depth16", "obb_xforms", "voxelize_obb", "invert_xforms", "ObbBatch",
+           "voxelize_grid_lowp", "voxelize_lowp", "narrow_volumes"]

@@ -112,6 +112,13 @@ DEPTH16_MAX_SHIFT = 7   # TSDF_DEPTH16_MAX_SHIFT of include/tsdf_depth16.h
 OBB_LIB_PATH = os.path.join(_HERE, "libtsdf_obb.so")
 OBB_VERSION = 1
 
+# The extension library of include/tsdf_lowp.h (make -C csrc lowp): the plain voxel pass on a caller-supplied grid written
+# as float16 / bfloat16 voxels, and the same narrowing for float32 values.  A binary of its own: all above is frozen.
+LOWP_LIB_PATH = os.path.join(_HERE, "libtsdf_lowp.so")
+LOWP_VERSION = 1
+TSDF_LOWP_F16 = 1    # enum tsdf_lowp_dtype of include/tsdf_lowp.h
+TSDF_LOWP_BF16 = 2
+
 
 class _Ext(NamedTuple):
     """A row of the extension table: libtsdf_<name>.so, built by ``make -C csrc <name>`` from include/tsdf_<name>.h."""
@@ -154,6 +161,13 @@ _EXTS_LATER = {
     "obb": _Ext(OBB_LIB_PATH, "tsdf_obb_version", OBB_VERSION, {
         # depth, depth_len, offsets, headers, n, cam, stream, xforms, moments, status
         "tsdf_obb_xforms_hip": [_vp, _i64, _vp, _vp, _i, ctypes.POINTER(TsdfCam), _vp, _vp, _vp, _vp],
+    }),
+    "lowp": _Ext(LOWP_LIB_PATH, "tsdf_lowp_version", LOWP_VERSION, {
+        # depth, depth_len, offsets, headers, n_src, index, n, R, cam, layout, dtype, stream, grid, tsdf, status
+        "tsdf_voxelize_grid_lowp_hip": [_vp, _i64, _vp, _vp, _i64, _vp, _i, _i, ctypes.POINTER(TsdfCam), _i, _i, _vp, _vp,
+                                        _vp, _vp],
+        # in, count, dtype, stream, out
+        "tsdf_lowp_narrow_hip": [_vp, _i64, _i, _vp, _vp],
     }),
 }
 
@@ -289,6 +303,11 @@ def load_depth16():
 def load_obb():
     """libtsdf_obb.so, the library of include/tsdf_obb.h."""
     return _load_ext("obb")
+
+
+def load_lowp():
+    """libtsdf_lowp.so, the library of include/tsdf_lowp.h."""
+    return _load_ext("lowp")
 
 
 @contextlib.contextmanager

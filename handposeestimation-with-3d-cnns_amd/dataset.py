@@ -41,7 +41,7 @@ from . import _lib, augment, packing, shard
 from .pca import JointPCA, fit_joint_pca
 from .voxelize import (AugmentedStep, TsdfBatch, _get_raw_stream, aabb, aug_state, aug_xforms, aug_xforms_at,  # noqa: F401
                        denormalize_joints, empty_batch, normalize_joints, obb_xforms, project_joints, voxelize,
-                       voxelize_aug, voxelize_indexed, voxelize_labels, widen_depth16)
+                       voxelize_aug, voxelize_grid_lowp, voxelize_indexed, voxelize_labels, widen_depth16, _lowp_dtype)
 
 
 def _common_depth_shift(packs: Sequence[packing.PackedFrames]) -> Optional[int]:
@@ -545,12 +545,23 @@ class ResidentLoader(_BatchLoader):
     ``augment``; the map is rigid, so pose error is what it is in the camera frame, and
     ``transform_joints(pred, invert_xforms(loader.obb[index]))`` carries predictions back.  The default ``"camera"`` is the
     loader without it, bit for bit.  ``frame="obb"`` does not combine with ``augment`` or ``graph=True``.
+
+    ``volume_dtype=torch.float16`` / ``torch.bfloat16`` yields the volumes in that type, written once at half the bytes
+    (:func:`voxelize.voxelize_grid_lowp`; include/tsdf_lowp.h) — what a network under autocast reads, and half the ring of a
+    prefetching loader.  One :func:`voxelize.aabb` launch after the upload places every resident frame's grid into resident
+    tables (grid rows, ``max_l``, ``mid_p``, ``status``); the epoch's permutation goes up once, every batch (``prefetch=k``:
+    every block of k batches, into a ring of low-precision blocks) is one voxel launch with its slice of it, ``max_l`` /
+    ``mid_p`` / ``status`` / ``gt`` are gathered by ``index_select`` and the labels come from :func:`normalize_joints`
+    (0.5 for a frame that is not OK, as the fused entry writes).  Everything but ``tsdf`` equals the float32 loader's batch
+    bit for bit; ``tsdf`` is the float32 volume narrowed by round-to-nearest-even, up to the contract's 1e-5.  It does not
+    combine with ``augment``, ``frame="obb"`` or ``graph=True``.  The default ``None`` is the loader without it.
     """
 
     def __init__(self, dataset: MSRADepthDataset, batch_size: int, device, res: int = 32, shuffle: bool = False,
                  seed: int = 0, drop_last: bool = False, rank: int = 0, world: int = 1, labels: bool = True,
                  clamp: bool = True, layout: str = "czyx", augment: Union[bool, str] = False, balance: str = "frames",
-                 prefetch: int = 1, ring: int = 2, graph: bool = False, frame: str = "camera"):
+                 prefetch: int = 1, ring: int = 2, graph: bool = False, frame: str = "camera",
+                 volume_dtype: Optional[torch.dtype] = None):
         """``augment=True``: every frame of every batch gets a fresh 3-D augmentation with the reference's distributions
         (``augment.random_affines``, pre/process.py:209-216) about its own un-augmented grid centre, fused into the
         voxelizer (BASELINE configs[4]); the yielded ``gt`` are then the mapped joints, ``gt_nor`` their labels.
@@ -560,6 +571,11 @@ class ResidentLoader(_BatchLoader):
             raise ValueError(f"frame must be 'camera' or 'obb', got {frame!r}")
         if frame == "obb" and (augment or graph):
             raise ValueError("frame='obb' does not combine with augment or graph=True (the two maps are not composed)")
+        if volume_dtype is not None:
+            _lowp_dtype(volume_dtype)
+            if augment or graph or frame == "obb":
+                raise ValueError("volume_dtype does not combine with augment, frame='obb' or graph=True (the low-precision "
+                                 "voxel pass is the plain one)")
         if not dataset.packed:
             raise ValueError("ResidentLoader needs a pack-backed dataset (packing.pack_tree + packed_dir=, or from_packs)")
         if prefetch < 1 or ring < 2:
@@ -577,6 +593,9 @@ class ResidentLoader(_BatchLoader):
         self.obb = None          # frame="obb": the maps of all resident frames, float64[N,24] on the device
         self.obb_status = None   # ... and their status, int32[N]
         self._step = None  # graph=True: the AugmentedStep of full batches
+        self.volume_dtype = volume_dtype
+        self._lowp = None        # volume_dtype: (grid rows, max_l, mid_p, status) of all resident frames
+        self._lowp_ring = None   # ... and with prefetch > 1 the ring of low-precision volume blocks
         self._mapped = self.augment or frame == "obb"   # every launch takes one map per frame (_maps)
         self.prefetch, self.ring = int(prefetch), int(ring)
         super().__init__(dataset, batch_size, device, res, shuffle, seed, drop_last, rank, world, labels, clamp, layout,
@@ -603,6 +622,10 @@ class ResidentLoader(_BatchLoader):
         if self.frame == "obb":   # every resident frame's map, once: one launch over the pack
             ob = obb_xforms(rp.depth, rp.offsets, rp.headers)
             self.obb, self.obb_status = ob.xforms, ob.status
+        if self.volume_dtype is not None:   # every resident frame's grid placement, once: one AABB launch over the pack
+            ab = aabb(rp.depth, rp.offsets, rp.headers, res=self.res)
+            rows = torch.cat([ab.ori, ab.grid[:, 4:6], torch.zeros_like(ab.ori)], dim=1)
+            self._lowp = (rows, ab.grid[:, 3].contiguous(), ab.grid[:, :3].contiguous(), ab.status)
         if self.augment:   # the centres the maps turn about: every frame's own grid centre, one AABB launch over the pack
             mid = aabb(rp.depth, rp.offsets, rp.headers, res=self.res).grid[:, :3]
             if self.device_draws:   # the centres stay where the launch left them; one map buffer per launch in flight
@@ -618,9 +641,46 @@ class ResidentLoader(_BatchLoader):
         self.epoch += 1
         if self._dev is None:
             self._upload()
+        if self.volume_dtype is not None:
+            return self._iter_lowp(batches)
         if self.prefetch > 1:
             return self._iter_blocks(batches, self.epoch)
         return self._iter_single(batches, self.epoch)
+
+    def _iter_lowp(self, batches) -> Iterator[VoxelBatch]:
+        """volume_dtype: one low-precision voxel launch per block of ``prefetch`` batches over the resident grid rows; the
+        per-frame fields are gathered from the resident tables.  ``prefetch=1`` allocates every batch's volume, ``k > 1``
+        writes into a ring of blocks whose batches are views (lifetime as in the class docstring)."""
+        depth, off, hdr, gt = self._dev
+        rows, max_l, mid_p, status = self._lowp
+        if not batches:
+            return
+        bs, P, R = self.bs, self.prefetch, self.res
+        if P > 1 and self._lowp_ring is None:
+            self._lowp_ring = [torch.empty((bs * P, 3, R, R, R), dtype=self.volume_dtype, device=self.device)
+                               for _ in range(self.ring)]
+        d_idx = torch.from_numpy(np.ascontiguousarray(self._g[np.concatenate(batches)])).to(self.device)
+        pos = 0
+        for blk, k0 in enumerate(range(0, len(batches), P)):
+            mine = batches[k0:k0 + P]
+            nfr = int(sum(b.size for b in mine))
+            idx = d_idx[pos:pos + nfr]
+            pos += nfr
+            out = self._lowp_ring[blk % self.ring][:nfr] if P > 1 else None
+            tsdf, _ = voxelize_grid_lowp(depth, off, hdr, rows, res=R, layout=self.layout, dtype=self.volume_dtype,
+                                         index=idx, out=out)
+            ml, mp, st = max_l.index_select(0, idx), mid_p.index_select(0, idx), status.index_select(0, idx)
+            g = gt.index_select(0, idx)
+            gt_nor = None
+            if self.labels:
+                gt_nor = normalize_joints(g, ml, mp, clamp=self.clamp)
+                bad = (st != _lib.TSDF_FRAME_OK).reshape((-1,) + (1,) * (g.dim() - 1))
+                gt_nor = torch.where(bad, torch.full_like(gt_nor, 0.5), gt_nor)
+            a = 0
+            for b in mine:
+                e = a + int(b.size)
+                yield VoxelBatch(tsdf[a:e], g[a:e], ml[a:e], mp[a:e], st[a:e], gt_nor[a:e] if self.labels else None)
+                a = e
 
     def _epoch_key(self, epoch: int) -> int:
         """augment="device": the key the epoch's frames draw under (their counters are their places in the epoch)."""

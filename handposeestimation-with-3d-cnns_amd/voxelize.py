@@ -805,7 +805,7 @@ def cloud_grids(points: torch.Tensor, res: int = 32, cam: Optional[_lib.TsdfCam]
 
 class ProcessBatch(NamedTuple):
     points: torch.Tensor  # float64[n, P, 3]  the resampled clouds
-    tsdf: torch.Tensor    # float32[n, 3, R, R, R]
+    tsdf: torch.Tensor    # float32[n, 3, R, R, R] (float16 / bfloat16 with process_batch(dtype=...))
     max_l: torch.Tensor   # float32[n]
     mid_p: torch.Tensor   # float32[n, 3]
     status: torch.Tensor  # int32[n]  the first non-zero status of the three stages
@@ -814,7 +814,7 @@ class ProcessBatch(NamedTuple):
 
 def process_batch(depth: torch.Tensor, offsets: torch.Tensor, headers: torch.Tensor, points: int = 6000, seed: int = 0,
                   frame_base: int = 0, res: int = 32, layout: str = "czyx",
-                  cam: Optional[_lib.TsdfCam] = None) -> ProcessBatch:
+                  cam: Optional[_lib.TsdfCam] = None, dtype: Optional[torch.dtype] = None) -> ProcessBatch:
     """``DataProcess.process()`` (pre/process.py:13-28) for n packed frames: back-project and resample the cloud
     (:func:`point_clouds`), place the grid on the AABB of THAT cloud (:func:`cloud_grids` — the reference's rule; every
     other batched path places it on all valid pixels) and voxelize with that placement (:func:`voxelize_grid`).  Three
@@ -822,10 +822,18 @@ def process_batch(depth: torch.Tensor, offsets: torch.Tensor, headers: torch.Ten
 
     ``seed`` / ``frame_base`` as for :func:`point_clouds`: a batch split over several calls gives the same result.
     A frame that is not OK in any stage has a zero volume and ``max_l`` 0; ``status`` is the first non-zero status among
-    the stages (cloud, grid, volume)."""
+    the stages (cloud, grid, volume).
+
+    ``dtype`` (torch.float16 / torch.bfloat16): the last stage is :func:`voxelize_grid_lowp` on the same rows and ``tsdf``
+    has that type; every other field is unchanged."""
+    if dtype is not None:
+        _lowp_dtype(dtype)
     pc = point_clouds(depth, offsets, headers, points=points, seed=seed, frame_base=frame_base, cam=cam)
     cg = cloud_grids(pc.points, res=res, cam=cam)
-    tsdf, st = voxelize_grid(depth, offsets, headers, cg.grid, res=res, layout=layout, cam=cam)
+    if dtype is None:
+        tsdf, st = voxelize_grid(depth, offsets, headers, cg.grid, res=res, layout=layout, cam=cam)
+    else:
+        tsdf, st = voxelize_grid_lowp(depth, offsets, headers, cg.grid, res=res, layout=layout, dtype=dtype, cam=cam)
     status = torch.where(pc.status != 0, pc.status, torch.where(cg.status != 0, cg.status, st))
     return ProcessBatch(pc.points, tsdf, cg.max_l, cg.mid_p, status, pc.count)
 
@@ -987,3 +995,81 @@ def invert_xforms(xforms: torch.Tensor) -> torch.Tensor:
     if xforms.dim() != 2 or xforms.shape[1] != 24:
         raise ValueError("xforms must have shape [n, 24] (forward rows then inverse rows)")
     return torch.cat([xforms[:, 12:], xforms[:, :12]], dim=1)
+
+
+_LOWP_DTYPES = {torch.float16: _lib.TSDF_LOWP_F16, torch.bfloat16: _lib.TSDF_LOWP_BF16}
+
+
+def _lowp_dtype(dtype) -> int:
+    """enum tsdf_lowp_dtype of a torch dtype; anything but float16 / bfloat16 is a ValueError."""
+    code = _LOWP_DTYPES.get(dtype) if isinstance(dtype, torch.dtype) else None
+    if code is None:
+        raise ValueError(f"dtype must be torch.float16 or torch.bfloat16, got {dtype!r}")
+    return code
+
+
+def voxelize_grid_lowp(depth: torch.Tensor, offsets: torch.Tensor, headers: torch.Tensor, grid: torch.Tensor,
+                       res: int = 32, layout: str = "czyx", dtype: torch.dtype = torch.bfloat16,
+                       cam: Optional[_lib.TsdfCam] = None, index: Optional[torch.Tensor] = None,
+                       out: Optional[torch.Tensor] = None):
+    """:func:`voxelize_grid` written as float16 / bfloat16 voxels (``tsdf_voxelize_grid_lowp_hip`` of libtsdf_lowp.so;
+    include/tsdf_lowp.h has the contract): every voxel is the float32 value of the plain pass narrowed by
+    round-to-nearest-even in registers, so the volume is written once, at half the bytes.
+
+    depth / offsets / headers   the n_src source frames, as for :func:`voxelize`
+    grid    float32[n_src,8] on the GPU: vox_ori[3], voxel_len, trunc_dis, 3 pad words per SOURCE frame
+    dtype   torch.float16 or torch.bfloat16
+    index   optional int64[n] on the GPU: batch position i voxelizes source frame index[i] (repeats allowed; an entry
+            outside [0, n_src) gives that position status 2 and a zero volume).  Without it the batch is the n_src frames
+    out     optional preallocated ``dtype[n,3,R,R,R]`` (a contiguous view of a larger buffer will do) to write into
+    Returns ``(tsdf dtype[n,3,R,R,R], status int32[n])``.  A bad header (2) or an unusable grid row (1: ``trunc_dis`` not
+    positive, or anything non-finite) gives a zero volume; the crop is not scanned, so a frame without a valid pixel gets
+    a zero volume with status 0.  One launch on the current stream, no synchronisation."""
+    code = _lowp_dtype(dtype)
+    P = _lib.load_lowp()
+    dev, n_src, R = _pack(_lib.load(), depth, offsets, headers, res, layout)
+    _shaped("grid", grid, (n_src, 8), torch.float32, dev)
+    n = n_src
+    if index is not None:
+        _dev_check("index", index, torch.int64, dev)
+        if index.dim() != 1:
+            raise ValueError("index must have shape [n]")
+        n = int(index.shape[0])
+        if n and not n_src:
+            raise ValueError("index needs at least one source frame")
+    tsdf = _out("out", out, (n, 3, R, R, R), dtype, dev)
+    st = _out("status", None, (n,), torch.int32, dev)
+    if n:
+        _call(dev, P.tsdf_voxelize_grid_lowp_hip,
+              [depth.data_ptr(), depth.numel(), offsets.data_ptr(), headers.data_ptr(), n_src, _ptr(index), n, R, _cam(cam),
+               _lib.LAYOUTS[layout], code, None, grid.data_ptr(), tsdf.data_ptr(), st.data_ptr()], 11)
+    return tsdf, st
+
+
+def voxelize_lowp(depth: torch.Tensor, offsets: torch.Tensor, headers: torch.Tensor, res: int = 32, layout: str = "czyx",
+                  dtype: torch.dtype = torch.bfloat16, cam: Optional[_lib.TsdfCam] = None) -> TsdfBatch:
+    """:func:`voxelize` with a float16 / bfloat16 volume: :func:`aabb` places the grid, the rows are put together on the
+    device and :func:`voxelize_grid_lowp` writes the volume.  Nothing runs on the host in between, but it is TWO launches
+    and the crop is read twice (the fused float32 entry reads it once).  ``max_l`` / ``mid_p`` / ``status`` are
+    :func:`aabb`'s, bit for bit those of :func:`voxelize`; ``tsdf`` is ``dtype[n,3,R,R,R]``."""
+    _lowp_dtype(dtype)
+    ab = aabb(depth, offsets, headers, res=res, cam=cam)
+    rows = torch.cat([ab.ori, ab.grid[:, 4:6], torch.zeros_like(ab.ori)], dim=1)
+    tsdf, _ = voxelize_grid_lowp(depth, offsets, headers, rows, res=res, layout=layout, dtype=dtype, cam=cam)
+    return TsdfBatch(tsdf, ab.grid[:, 3].contiguous(), ab.grid[:, :3].contiguous(), ab.status)
+
+
+def narrow_volumes(tsdf32: torch.Tensor, dtype: torch.dtype = torch.bfloat16,
+                   out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """float32 values narrowed to float16 / bfloat16 by round-to-nearest-even (``tsdf_lowp_narrow_hip`` of libtsdf_lowp.so):
+    the cast :func:`voxelize_grid_lowp` applies in registers, for volumes that are already float32.  ``tsdf32``: float32 on
+    the GPU, contiguous, any shape, 16-byte aligned; ``out``: ``dtype`` of the same shape (allocated when None).  One launch
+    on the current stream, no synchronisation."""
+    code = _lowp_dtype(dtype)
+    P = _lib.load_lowp()
+    _dev_check("tsdf32", tsdf32, torch.float32)
+    dev = tsdf32.device
+    out = _out("out", out, tuple(tsdf32.shape), dtype, dev)
+    if tsdf32.numel():
+        _call(dev, P.tsdf_lowp_narrow_hip, [tsdf32.data_ptr(), tsdf32.numel(), code, None, out.data_ptr()], 3)
+    return out
