@@ -130,7 +130,8 @@ class _Ext(NamedTuple):
 
 _vp, _i, _i64, _u64 = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_uint64
 
-# Adding an extension library is a row here, a name in csrc/Makefile's EXTS and a one-line load_<name> below.
+# Every extension library, in the order of csrc/Makefile's EXTS.  Adding one is a row here, a name in EXTS (with what its
+# tsdf_<name>.hip includes besides device.inc / prim.inc in <name>_DEPS) and a one-line load_<name> below.
 _EXTS = {
     "augment": _Ext(AUGMENT_LIB_PATH, "tsdf_augment_version", AUGMENT_VERSION, {
         # centres, n_src, index, n, key, counter0, stream, xforms, stretch, rot
@@ -152,12 +153,6 @@ _EXTS = {
         # src, src_len, src_offsets, n_src, index, n, dst, dst_len, dst_offsets, n_threads
         "tsdf_depth16_host_gather": [_vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i],
     }),
-}
-
-# Extensions merged after the table above was pinned: tests/test_ext_table_cpu.py asserts that _EXTS holds exactly its four
-# rows, and that file is a yardstick no later change may edit.  So a newer library gets its row here, in a table of the
-# same _Ext type that _load_ext consults as well; everything else about adding one is as described above.
-_EXTS_LATER = {
     "obb": _Ext(OBB_LIB_PATH, "tsdf_obb_version", OBB_VERSION, {
         # depth, depth_len, offsets, headers, n, cam, stream, xforms, moments, status
         "tsdf_obb_xforms_hip": [_vp, _i64, _vp, _vp, _i, ctypes.POINTER(TsdfCam), _vp, _vp, _vp, _vp],
@@ -267,7 +262,7 @@ def _load_ext(name: str):
     L = _ext_libs.get(name)
     if L is not None:
         return L
-    ext = _EXTS[name] if name in _EXTS else _EXTS_LATER[name]
+    ext = _EXTS[name]
     if not os.path.exists(ext.path):
         raise ImportError(f"{ext.path} not found: build it with `make -C handposeestimation-with-3d-cnns_amd/csrc "
                           f"{name}` (__graft_entry__.build() does). There is no CPU fallback.")

@@ -126,14 +126,6 @@ __device__ __forceinline__ float row0_max(float v) {
 }
 
 // ---- exact float64 helpers (never contracted) ----------------------------------------------
-// int() of a float64, toward zero; v_cvt_i32_f64 saturates out-of-range values and maps NaN to 0
-// (same rule as oracle/tsdf_oracle.c::trunc_i32).
-__device__ __forceinline__ int trunc_i32(double v) {
-  int r;
-  asm("v_cvt_i32_f64 %0, %1" : "=v"(r) : "v"(v));
-  return r;
-}
-
 // (a * b) + c with two roundings: pre/tsdf_numba.py:31-32 as numba types it (App. A.3).
 __device__ __forceinline__ double mul_then_add(double a, double b, double c) {
 #pragma clang fp contract(off)

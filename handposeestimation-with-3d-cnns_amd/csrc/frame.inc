@@ -184,8 +184,6 @@ __device__ __forceinline__ bool frame_from_header(const FrameHdr &fh, const floa
          fh.off1 <= depth_len;
 }
 
-__device__ __forceinline__ bool finite32(float v) { return __builtin_fabsf(v) < TSDF_INF; }
-
 // AABB -> grid placement and frame status (degenerate-frame rule of include/tsdf.h).
 __device__ __forceinline__ void place_grid(Aabb &ab, int R, const CamK &cam, const float *grid_in, int frame,
                                            Grid &g, int &status) {

@@ -2,8 +2,6 @@
 // Host side of a call: the one argument check (tsdf_host.inc), device check (device.inc), split plan, choice of
 // instantiation, argument marshalling.
 
-const tsdf_cam kDefaultCam = {241.42, 160.0, 120.0, 1.0f, 3.0f};
-
 // CU count of the current device (cached per device id; a racing first call computes the same value)
 int num_cus() {
   static std::atomic<int> cached[64];

@@ -45,13 +45,6 @@ __device__ __forceinline__ int project_rel(double v, double q, double c, int p0,
   return (unsigned)rel <= (unsigned)dmax ? rel : -1;
 }
 
-// smallest float32 >= t  (so that for a float32 p:  p < t  <=>  p < result)
-__device__ __forceinline__ float f32_round_up(double t) {
-  float f = (float)t;
-  if ((double)f < t) f = nextafterf(f, TSDF_INF);
-  return f;
-}
-
 // The gather source is either the LDS pool of captured row spans or the frame in global memory.  It is
 // passed with its address space in the type: a generic pointer would make every gather a FLAT load,
 // which is counted in vmcnt together with the volume stores, so each loop iteration would wait for the

@@ -3,8 +3,9 @@
 //
 // A translation unit and a library of its own, next to libtsdf_hip.so, libtsdf_augment.so and libtsdf_augstep.so (all
 // frozen).  It takes the status codes, tsdf_cam and the layout enum from include/tsdf.h and the host preamble every library
-// here has from device.inc; the small arithmetic helper trunc_i32 is restated here, nothing else of the product's .inc files
-// is included, and there is no device global: every launch is self-contained.
+// here has from device.inc, the device primitives from prim.inc and the slab scaffold it shares with tsdf_lowp.hip from
+// slab.inc; nothing else of the product's .inc files is included, and there is no device global: every launch is
+// self-contained.
 //
 // tsdf_aug_grid_kernel: n x ceil(R / slab) workgroups of 256 threads; a workgroup owns `slab` consecutive slices (indices
 // of the slowest output axis) of one frame, so a batch of 16 frames at 32^3 is 256 workgroups.  It
@@ -33,12 +34,8 @@
 namespace {
 
 #include "device.inc"   // check_device, launched, misaligned: the host preamble of every library here
-
-constexpr int kGridWG = 256;       // threads per workgroup (4 wave64)
-constexpr int kGridMaxR = 128;     // largest resolution (include/tsdf.h: tsdf_resolution_supported)
-constexpr int kGridItems = 512;    // items (4 voxels each) a workgroup aims for: two per lane
-
-const tsdf_cam kDefaultCam = {241.42, 160.0, 120.0, 1.0f, 3.0f};   // pre/tsdf_numba.py:8-10, as in include/tsdf.h
+#include "prim.inc"     // kDefaultCam, trunc_i32, finite32, header_ok
+#include "slab.inc"     // workgroup <-> slab, the frame's header and grid row, zero-fill, host sizing
 
 typedef float grid_f4 __attribute__((ext_vector_type(4)));
 typedef double grid_d4 __attribute__((ext_vector_type(4)));
@@ -59,56 +56,34 @@ struct AugGridArgs {
   int32_t *status;        // [n] or null
 };
 
-// int() of a float64, toward zero; v_cvt_i32_f64 saturates out-of-range values and maps NaN to 0
-// (the rule of oracle/tsdf_oracle.c::trunc_i32).
-__device__ __forceinline__ int trunc_i32(double v) {
-  int r;
-  asm("v_cvt_i32_f64 %0, %1" : "=v"(r) : "v"(v));
-  return r;
-}
-
-__device__ __forceinline__ bool finite32(float v) { return __builtin_fabsf(v) < __builtin_inff(); }   // false for NaN
-
 template <int LAYOUT>
-__global__ __launch_bounds__(kGridWG) void tsdf_aug_grid_kernel(AugGridArgs a) {
+__global__ __launch_bounds__(kSlabWG) void tsdf_aug_grid_kernel(AugGridArgs a) {
 #pragma clang fp contract(off)
   // [axis][index] = {A'_0a v'_a, A'_1a v'_a, A'_2a v'_a, v'_a - b_a}; the z axis carries + b'_i in its first three
-  __shared__ grid_d4 s_tab[3][kGridMaxR];
+  __shared__ grid_d4 s_tab[3][kSlabMaxR];
 
   const int tid = threadIdx.x;
   const int R = a.R, R4 = R >> 2;
-  const int64_t i = blockIdx.x / (unsigned)a.nslab;
-  const int sidx = (int)(blockIdx.x - i * a.nslab);
-  const int sb = sidx * a.slab;
-  const int se = sb + a.slab < R ? sb + a.slab : R;
+  const Slab blk = slab_of_block(a.nslab, a.slab, R);
+  const int64_t i = blk.i;
+  const int sb = blk.sb, se = blk.se;
   const int64_t R3 = (int64_t)R * R * R;
   float *__restrict__ out = a.out + i * 3 * R3;
 
-  // the voxelizer's header rule; a bad frame's depth is not read
-  const int32_t *hd = a.headers + 6 * i;
-  const int left = hd[2], top = hd[3], right = hd[4], bottom = hd[5];
-  const int64_t off0 = a.offsets[i], off1 = a.offsets[i + 1];
-  const int64_t bw = (int64_t)right - left, bh = (int64_t)bottom - top;
-  const bool hdr_ok = bw > 0 && bh > 0 && bw <= 0x7fffffff && bh <= 0x7fffffff && bw * bh == off1 - off0 && off0 >= 0 &&
-                      off1 <= a.depth_len;
-  const float *gr = a.grid + 8 * i;
-  const float ox = gr[0], oy = gr[1], oz = gr[2], vl = gr[3], td = gr[4];
-  const bool grid_ok = td > 0.0f && finite32(td) && finite32(vl) && finite32(ox) && finite32(oy) && finite32(oz);
-  const int status = !hdr_ok ? TSDF_FRAME_BAD_HEADER : !grid_ok ? TSDF_FRAME_DEGENERATE : TSDF_FRAME_OK;
-  if (sidx == 0 && tid == 0 && a.status) a.status[i] = status;
+  const int64_t depth_len = a.depth_len;
+  const SlabFrame fr = slab_frame(depth_len, a.offsets, a.headers, a.grid, i, true);
+  const int left = fr.left, top = fr.top, right = fr.right, bottom = fr.bottom;
+  const int64_t bw = fr.bw;
+  const float ox = fr.ox, oy = fr.oy, oz = fr.oz, vl = fr.vl, td = fr.td;
+  if (blk.first() && tid == 0 && a.status) a.status[i] = fr.status;
 
-  if (status != TSDF_FRAME_OK) {   // (uniform) zeros for this slab: slices [sb, se) of every channel are contiguous
-    const int64_t per = (int64_t)(se - sb) * R * R4;   // 16-byte pieces per channel
-    const grid_f4 z4 = {0.f, 0.f, 0.f, 0.f};
-    for (int c = 0; c < 3; ++c) {
-      grid_f4 *p = reinterpret_cast<grid_f4 *>(out + c * R3 + (int64_t)sb * R * R);
-      for (int64_t q = tid; q < per; q += kGridWG) p[q] = z4;
-    }
+  if (fr.status != TSDF_FRAME_OK) {   // (uniform)
+    slab_zero_fill<grid_f4>(out, R, sb, (int64_t)(se - sb) * R * R4, tid);
     return;
   }
 
   const double *__restrict__ xf = a.xforms + 24 * i;
-  for (int e = tid; e < 3 * R; e += kGridWG) {
+  for (int e = tid; e < 3 * R; e += kSlabWG) {
     const int ax = e / R, idx = e - ax * R;
     const float o = ax == 0 ? ox : ax == 1 ? oy : oz;
     const double prod = (double)idx * (double)vl;
@@ -134,11 +109,11 @@ __global__ __launch_bounds__(kGridWG) void tsdf_aug_grid_kernel(AugGridArgs a) {
   const double g01 = xf[1] * iF, g11 = xf[5] * iF, g21 = xf[9] * iF;         // g_i1 = A_i1 * iF
   const double a02 = xf[2], a12 = xf[6], a22 = xf[10];
   const float eps = a.eps;
-  const float *__restrict__ d = a.depth + off0;
+  const float *__restrict__ d = a.depth + fr.off0;
   __syncthreads();
 
   const int nit = (se - sb) * R * R4;
-  for (int item = tid; item < nit; item += kGridWG) {
+  for (int item = tid; item < nit; item += kSlabWG) {
     const int f4 = (item % R4) * 4;
     const int t1 = item / R4;
     const int y = t1 % R, sl = sb + t1 / R;
@@ -205,8 +180,8 @@ struct JointArgs {
 };
 
 // one lane per coordinate triple: T(joint) with the frame's forward rows, a fused chain in float64 (affine3_fwd)
-__global__ __launch_bounds__(kGridWG) void tsdf_transform_joints_kernel(JointArgs a) {
-  const int64_t t = (int64_t)blockIdx.x * kGridWG + threadIdx.x;
+__global__ __launch_bounds__(kSlabWG) void tsdf_transform_joints_kernel(JointArgs a) {
+  const int64_t t = (int64_t)blockIdx.x * kSlabWG + threadIdx.x;
   if (t >= a.total) return;
   const int64_t i = t / a.J;
   const double *__restrict__ m = a.xforms + 24 * i;
@@ -231,15 +206,10 @@ int tsdf_voxelize_aug_grid_hip(const float *d_depth, int64_t depth_len, const in
   if (n < 0) return TSDF_ERR_INVALID_ARG;
   if (n == 0) return TSDF_OK;
   if (!d_depth || !d_offsets || !d_headers || !d_xforms || !d_grid || !d_out_tsdf || depth_len < 0) return TSDF_ERR_INVALID_ARG;
-  if (R < 4 || R > kGridMaxR || (R & 3)) return TSDF_ERR_INVALID_ARG;
-  if (layout != TSDF_LAYOUT_CZYX && layout != TSDF_LAYOUT_CXYZ) return TSDF_ERR_INVALID_ARG;
+  if (slab_bad_shape(R, layout)) return TSDF_ERR_INVALID_ARG;
   if (misaligned(d_xforms, 7) || misaligned(d_out_tsdf, 15)) return TSDF_ERR_INVALID_ARG;
-  const int per = R * (R >> 2);   // items per slice
-  int slab = (kGridItems + per - 1) / per;
-  if (slab > R) slab = R;
-  const int nslab = (R + slab - 1) / slab;
-  const int64_t blocks = (int64_t)n * nslab;
-  if (blocks * kGridWG > 0xffffffffll) return TSDF_ERR_INVALID_ARG;   // a launch holds fewer than 2^32 work-items
+  SlabPlan plan;
+  if (!slab_plan(n, R, 4, plan)) return TSDF_ERR_INVALID_ARG;   // a launch holds fewer than 2^32 work-items
   const int rc = check_device(nullptr);
   if (rc != TSDF_OK) return rc;
   if (!cam) cam = &kDefaultCam;
@@ -250,8 +220,8 @@ int tsdf_voxelize_aug_grid_hip(const float *d_depth, int64_t depth_len, const in
   a.headers = d_headers;
   a.n = n;
   a.R = R;
-  a.slab = slab;
-  a.nslab = nslab;
+  a.slab = plan.slab;
+  a.nslab = plan.nslab;
   a.focal = cam->focal;
   a.cx = cam->cx;
   a.cy = cam->cy;
@@ -262,9 +232,9 @@ int tsdf_voxelize_aug_grid_hip(const float *d_depth, int64_t depth_len, const in
   a.status = d_out_status;
   hipStream_t s = static_cast<hipStream_t>(hip_stream);
   if (layout == TSDF_LAYOUT_CZYX)
-    hipLaunchKernelGGL(tsdf_aug_grid_kernel<0>, dim3((unsigned)blocks), dim3(kGridWG), 0, s, a);
+    hipLaunchKernelGGL(tsdf_aug_grid_kernel<0>, dim3((unsigned)plan.blocks), dim3(kSlabWG), 0, s, a);
   else
-    hipLaunchKernelGGL(tsdf_aug_grid_kernel<1>, dim3((unsigned)blocks), dim3(kGridWG), 0, s, a);
+    hipLaunchKernelGGL(tsdf_aug_grid_kernel<1>, dim3((unsigned)plan.blocks), dim3(kSlabWG), 0, s, a);
   return launched();
 }
 
@@ -282,9 +252,9 @@ int tsdf_transform_joints_hip(const float *d_gt, const double *d_xforms, int n, 
   a.total = (int64_t)n * n_joints;
   a.J = n_joints;
   a.out = d_out_gt_aug;
-  const int64_t blocks = (a.total + kGridWG - 1) / kGridWG;
-  if (blocks * kGridWG > 0xffffffffll) return TSDF_ERR_INVALID_ARG;
-  hipLaunchKernelGGL(tsdf_transform_joints_kernel, dim3((unsigned)blocks), dim3(kGridWG), 0,
+  const int64_t blocks = (a.total + kSlabWG - 1) / kSlabWG;
+  if (blocks * kSlabWG > 0xffffffffll) return TSDF_ERR_INVALID_ARG;
+  hipLaunchKernelGGL(tsdf_transform_joints_kernel, dim3((unsigned)blocks), dim3(kSlabWG), 0,
                      static_cast<hipStream_t>(hip_stream), a);
   return launched();
 }

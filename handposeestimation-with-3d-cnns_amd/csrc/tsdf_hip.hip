@@ -46,6 +46,7 @@
 //
 // One translation unit; the pieces (all inside the anonymous namespace below, in this order):
 //   device.inc   host preamble shared with the extension libraries: check_device, device_cus, launched, misaligned
+//   prim.inc     device primitives shared with the extension libraries: default camera, truncation, the header rule
 //   common.inc   constants, types, VALU / DPP / float64 helpers
 //   phase1.inc   row stream -> extents (AABB) -> grid placement
 //   phase2.inc   the voxel pass, plain and augmented; gather sources, projection tables, volume stores
@@ -82,6 +83,7 @@
 namespace {
 
 #include "device.inc"    // host preamble: device check, launch status, alignment test (every library here has it)
+#include "prim.inc"      // kDefaultCam, trunc_i32, finite32, f32_round_up, header_ok (shared with the extension libraries)
 #include "common.inc"    // constants, types, VALU / DPP / float64 helpers
 #include "phase1.inc"    // row stream -> extents -> grid placement
 #include "phase2.inc"    // the voxel pass, plain and augmented

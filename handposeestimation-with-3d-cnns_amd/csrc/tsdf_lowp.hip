@@ -2,8 +2,9 @@
 // the same narrowing for float32 values (include/tsdf_lowp.h).
 //
 // A translation unit and a library of its own, next to libtsdf_hip.so and the other extension libraries (all frozen).  It
-// takes the status codes, tsdf_cam and the layout enum from include/tsdf.h and the host preamble every library here has
-// from device.inc; the product's plain voxel arithmetic (phase2.inc::voxel_values4 and the tables of frame.inc that feed
+// takes the status codes, tsdf_cam and the layout enum from include/tsdf.h, the host preamble every library here has
+// from device.inc, the device primitives from prim.inc and the slab scaffold it shares with tsdf_auggrid.hip from
+// slab.inc; the product's plain voxel arithmetic (phase2.inc::voxel_values4 and the tables of frame.inc that feed
 // it) is RESTATED here operation for operation, nothing else of the product's .inc files is included, and there is no
 // device global: every launch is self-contained.
 //
@@ -40,13 +41,10 @@
 namespace {
 
 #include "device.inc"   // check_device, launched, misaligned: the host preamble of every library here
+#include "prim.inc"     // kDefaultCam, trunc_i32, finite32, f32_round_up, header_ok
+#include "slab.inc"     // workgroup <-> slab, the frame's header and grid row, zero-fill, host sizing
 
-constexpr int kLowpWG = 256;       // threads per workgroup (4 wave64)
-constexpr int kLowpMaxR = 128;     // largest resolution (include/tsdf.h: tsdf_resolution_supported)
-constexpr int kLowpItems = 512;    // items (V voxels each) a workgroup aims for: two per lane
 constexpr int kNarrowMaxBlocks = 1 << 16;   // the narrowing kernel strides over anything larger
-
-const tsdf_cam kDefaultCam = {241.42, 160.0, 120.0, 1.0f, 3.0f};   // pre/tsdf_numba.py:8-10, as in include/tsdf.h
 
 typedef float lowp_f4 __attribute__((ext_vector_type(4)));
 typedef float lowp_f2 __attribute__((ext_vector_type(2)));
@@ -72,23 +70,6 @@ struct LowpArgs {
   uint16_t *out;            // [n][3][R][R][R]
   int32_t *status;          // [n] or null
 };
-
-// int() of a float64, toward zero; v_cvt_i32_f64 saturates out-of-range values and maps NaN to 0
-// (the rule of oracle/tsdf_oracle.c::trunc_i32).
-__device__ __forceinline__ int trunc_i32(double v) {
-  int r;
-  asm("v_cvt_i32_f64 %0, %1" : "=v"(r) : "v"(v));
-  return r;
-}
-
-__device__ __forceinline__ bool finite32(float v) { return __builtin_fabsf(v) < __builtin_inff(); }   // false for NaN
-
-// smallest float32 >= t  (so that for a float32 p:  p < t  <=>  p < result)
-__device__ __forceinline__ float f32_round_up(double t) {
-  float f = (float)t;
-  if ((double)f < t) f = nextafterf(f, __builtin_inff());
-  return f;
-}
 
 // Two float32 narrowed by round-to-nearest-even into one 32-bit word, the first in the low half.  float16: v_cvt_f16_f32
 // (the kernels run with float16 subnormals on); bfloat16: v_cvt_pk_bf16_f32, gfx950's own conversion.
@@ -128,47 +109,34 @@ struct Piece<4> {
 
 // V = voxels per lane and item (8: 16-byte stores, 4: 8-byte stores)
 template <int LAYOUT, bool BF16, int V>
-__global__ __launch_bounds__(kLowpWG) void tsdf_grid_lowp_kernel(LowpArgs a) {
+__global__ __launch_bounds__(kSlabWG) void tsdf_grid_lowp_kernel(LowpArgs a) {
 #pragma clang fp contract(off)
   typedef typename Piece<V>::type piece;
-  __shared__ double s_vx[kLowpMaxR], s_vxs[kLowpMaxR];     // v_x, v_x * it
-  __shared__ double s_nvy[kLowpMaxR], s_vys[kLowpMaxR];    // -v_y, v_y * it
-  __shared__ double s_q[kLowpMaxR], s_vzs[kLowpMaxR];      // -F / v_z, v_z * it
-  __shared__ float s_neg[kLowpMaxR];                       // f32_round_up(-v_z)
+  __shared__ double s_vx[kSlabMaxR], s_vxs[kSlabMaxR];     // v_x, v_x * it
+  __shared__ double s_nvy[kSlabMaxR], s_vys[kSlabMaxR];    // -v_y, v_y * it
+  __shared__ double s_q[kSlabMaxR], s_vzs[kSlabMaxR];      // -F / v_z, v_z * it
+  __shared__ float s_neg[kSlabMaxR];                       // f32_round_up(-v_z)
 
   const int tid = threadIdx.x;
   const int R = a.R, RV = R / V;
-  const int64_t i = blockIdx.x / (unsigned)a.nslab;
-  const int sidx = (int)(blockIdx.x - i * a.nslab);
-  const int sb = sidx * a.slab;
-  const int se = sb + a.slab < R ? sb + a.slab : R;
+  const Slab blk = slab_of_block(a.nslab, a.slab, R);
+  const int64_t i = blk.i;
+  const int sb = blk.sb, se = blk.se;
   const int64_t R3 = (int64_t)R * R * R;
   uint16_t *__restrict__ out = a.out + i * 3 * R3;
 
   // the source frame; outside the tables it is a bad header and nothing of it is read
   const int64_t g = a.index ? a.index[i] : i;
   const bool src_ok = g >= 0 && g < a.n_src;
-  const int64_t gs = src_ok ? g : 0;
-  // the voxelizer's header rule; a bad frame's depth is not read
-  const int32_t *hd = a.headers + 6 * gs;
-  const int left = hd[2], top = hd[3], right = hd[4], bottom = hd[5];
-  const int64_t off0 = a.offsets[gs], off1 = a.offsets[gs + 1];
-  const int64_t bw = (int64_t)right - left, bh = (int64_t)bottom - top;
-  const bool hdr_ok = src_ok && bw > 0 && bh > 0 && bw <= 0x7fffffff && bh <= 0x7fffffff && bw * bh == off1 - off0 &&
-                      off0 >= 0 && off1 <= a.depth_len;
-  const float *gr = a.grid + 8 * gs;
-  const float ox = gr[0], oy = gr[1], oz = gr[2], vl = gr[3], td = gr[4];
-  const bool grid_ok = td > 0.0f && finite32(td) && finite32(vl) && finite32(ox) && finite32(oy) && finite32(oz);
-  const int status = !hdr_ok ? TSDF_FRAME_BAD_HEADER : !grid_ok ? TSDF_FRAME_DEGENERATE : TSDF_FRAME_OK;
-  if (sidx == 0 && tid == 0 && a.status) a.status[i] = status;
+  const int64_t gs = src_ok ? g : 0, depth_len = a.depth_len;
+  const SlabFrame fr = slab_frame(depth_len, a.offsets, a.headers, a.grid, gs, src_ok);
+  const int left = fr.left, top = fr.top, right = fr.right, bottom = fr.bottom;
+  const int64_t bw = fr.bw;
+  const float ox = fr.ox, oy = fr.oy, oz = fr.oz, vl = fr.vl, td = fr.td;
+  if (blk.first() && tid == 0 && a.status) a.status[i] = fr.status;
 
-  if (status != TSDF_FRAME_OK) {   // (uniform) zeros for this slab: slices [sb, se) of every channel are contiguous
-    const int64_t per = (int64_t)(se - sb) * R * R / 8;   // 16-byte pieces per channel (R * R is a multiple of 16)
-    const lowp_u4 z4 = {0u, 0u, 0u, 0u};
-    for (int c = 0; c < 3; ++c) {
-      lowp_u4 *p = reinterpret_cast<lowp_u4 *>(out + c * R3 + (int64_t)sb * R * R);
-      for (int64_t q = tid; q < per; q += kLowpWG) p[q] = z4;
-    }
+  if (fr.status != TSDF_FRAME_OK) {   // (uniform)
+    slab_zero_fill<lowp_u4>(out, R, sb, (int64_t)(se - sb) * R * R / 8, tid);   // R * R is a multiple of 16
     return;
   }
 
@@ -176,7 +144,7 @@ __global__ __launch_bounds__(kLowpWG) void tsdf_grid_lowp_kernel(LowpArgs a) {
   const double F = a.focal, cx = a.cx, cy = a.cy;
   const double it = 1.0 / (double)td;
   const double kq = a.inv_focal * it;
-  for (int e = tid; e < 3 * R; e += kLowpWG) {
+  for (int e = tid; e < 3 * R; e += kSlabWG) {
     const int ax = e / R, idx = e - ax * R;
     const float o = ax == 0 ? ox : ax == 1 ? oy : oz;
     const double prod = (double)idx * (double)vl;
@@ -195,11 +163,11 @@ __global__ __launch_bounds__(kLowpWG) void tsdf_grid_lowp_kernel(LowpArgs a) {
     }
   }
   const float eps = a.eps;
-  const float *__restrict__ d = a.depth + off0;
+  const float *__restrict__ d = a.depth + fr.off0;
   __syncthreads();
 
   const int nit = (se - sb) * R * RV;
-  for (int item = tid; item < nit; item += kLowpWG) {
+  for (int item = tid; item < nit; item += kSlabWG) {
     const int fv = (item % RV) * V;
     const int t1 = item / RV;
     const int y = t1 % R, sl = sb + t1 / R;
@@ -280,12 +248,12 @@ struct NarrowArgs {
 
 // 8 elements per lane and step: two 16-byte loads, one 16-byte store; the last count % 8 elements one by one
 template <bool BF16>
-__global__ __launch_bounds__(kLowpWG) void tsdf_lowp_narrow_kernel(NarrowArgs a) {
+__global__ __launch_bounds__(kSlabWG) void tsdf_lowp_narrow_kernel(NarrowArgs a) {
   const int64_t n8 = a.count >> 3;
-  const int64_t step = (int64_t)gridDim.x * kLowpWG;
+  const int64_t step = (int64_t)gridDim.x * kSlabWG;
   const lowp_f4 *__restrict__ in4 = reinterpret_cast<const lowp_f4 *>(a.in);
   lowp_u4 *__restrict__ out4 = reinterpret_cast<lowp_u4 *>(a.out);
-  for (int64_t k = (int64_t)blockIdx.x * kLowpWG + threadIdx.x; k < n8; k += step) {
+  for (int64_t k = (int64_t)blockIdx.x * kSlabWG + threadIdx.x; k < n8; k += step) {
     const lowp_f4 lo = in4[2 * k], hi = in4[2 * k + 1];
     lowp_u4 o;
     o.x = narrow2<BF16>(lo.x, lo.y);
@@ -303,9 +271,9 @@ bool bad_dtype(int dtype) { return dtype != TSDF_LOWP_F16 && dtype != TSDF_LOWP_
 template <int LAYOUT, bool BF16>
 void launch_grid(const LowpArgs &a, int64_t blocks, hipStream_t s) {
   if (a.R % 8 == 0)
-    hipLaunchKernelGGL((tsdf_grid_lowp_kernel<LAYOUT, BF16, 8>), dim3((unsigned)blocks), dim3(kLowpWG), 0, s, a);
+    hipLaunchKernelGGL((tsdf_grid_lowp_kernel<LAYOUT, BF16, 8>), dim3((unsigned)blocks), dim3(kSlabWG), 0, s, a);
   else
-    hipLaunchKernelGGL((tsdf_grid_lowp_kernel<LAYOUT, BF16, 4>), dim3((unsigned)blocks), dim3(kLowpWG), 0, s, a);
+    hipLaunchKernelGGL((tsdf_grid_lowp_kernel<LAYOUT, BF16, 4>), dim3((unsigned)blocks), dim3(kSlabWG), 0, s, a);
 }
 
 }  // namespace
@@ -319,20 +287,14 @@ int tsdf_voxelize_grid_lowp_hip(const float *d_depth, int64_t depth_len, const i
                                 int dtype, void *hip_stream, const float *d_grid, void *d_out_tsdf, int32_t *d_out_status) {
   // arguments first, then the device, then the launch
   if (n < 0) return TSDF_ERR_INVALID_ARG;
-  if (R < 4 || R > kLowpMaxR || (R & 3)) return TSDF_ERR_INVALID_ARG;
-  if (layout != TSDF_LAYOUT_CZYX && layout != TSDF_LAYOUT_CXYZ) return TSDF_ERR_INVALID_ARG;
+  if (slab_bad_shape(R, layout)) return TSDF_ERR_INVALID_ARG;
   if (bad_dtype(dtype)) return TSDF_ERR_INVALID_ARG;
   if (n == 0) return TSDF_OK;
   if (!d_depth || !d_offsets || !d_headers || !d_grid || !d_out_tsdf || depth_len < 0) return TSDF_ERR_INVALID_ARG;
   if (n_src < 1 || (!d_index && n_src != n)) return TSDF_ERR_INVALID_ARG;
   if (misaligned(d_out_tsdf, 15)) return TSDF_ERR_INVALID_ARG;
-  const int V = R % 8 == 0 ? 8 : 4;
-  const int per = R * (R / V);   // items per slice
-  int slab = (kLowpItems + per - 1) / per;
-  if (slab > R) slab = R;
-  const int nslab = (R + slab - 1) / slab;
-  const int64_t blocks = (int64_t)n * nslab;
-  if (blocks * kLowpWG > 0xffffffffll) return TSDF_ERR_INVALID_ARG;   // a launch holds fewer than 2^32 work-items
+  SlabPlan plan;
+  if (!slab_plan(n, R, R % 8 == 0 ? 8 : 4, plan)) return TSDF_ERR_INVALID_ARG;   // a launch holds fewer than 2^32 work-items
   const int rc = check_device(nullptr);
   if (rc != TSDF_OK) return rc;
   if (!cam) cam = &kDefaultCam;
@@ -345,8 +307,8 @@ int tsdf_voxelize_grid_lowp_hip(const float *d_depth, int64_t depth_len, const i
   a.index = d_index;
   a.n = n;
   a.R = R;
-  a.slab = slab;
-  a.nslab = nslab;
+  a.slab = plan.slab;
+  a.nslab = plan.nslab;
   a.focal = cam->focal;
   a.cx = cam->cx;
   a.cy = cam->cy;
@@ -358,11 +320,11 @@ int tsdf_voxelize_grid_lowp_hip(const float *d_depth, int64_t depth_len, const i
   hipStream_t s = static_cast<hipStream_t>(hip_stream);
   const bool bf = dtype == TSDF_LOWP_BF16;
   if (layout == TSDF_LAYOUT_CZYX) {
-    if (bf) launch_grid<0, true>(a, blocks, s);
-    else launch_grid<0, false>(a, blocks, s);
+    if (bf) launch_grid<0, true>(a, plan.blocks, s);
+    else launch_grid<0, false>(a, plan.blocks, s);
   } else {
-    if (bf) launch_grid<1, true>(a, blocks, s);
-    else launch_grid<1, false>(a, blocks, s);
+    if (bf) launch_grid<1, true>(a, plan.blocks, s);
+    else launch_grid<1, false>(a, plan.blocks, s);
   }
   return launched();
 }
@@ -377,14 +339,14 @@ int tsdf_lowp_narrow_hip(const float *d_in, int64_t count, int dtype, void *hip_
   a.in = d_in;
   a.count = count;
   a.out = static_cast<uint16_t *>(d_out);
-  int64_t blocks = ((count >> 3) + kLowpWG - 1) / kLowpWG;
+  int64_t blocks = ((count >> 3) + kSlabWG - 1) / kSlabWG;
   if (blocks < 1) blocks = 1;
   if (blocks > kNarrowMaxBlocks) blocks = kNarrowMaxBlocks;
   hipStream_t s = static_cast<hipStream_t>(hip_stream);
   if (dtype == TSDF_LOWP_BF16)
-    hipLaunchKernelGGL(tsdf_lowp_narrow_kernel<true>, dim3((unsigned)blocks), dim3(kLowpWG), 0, s, a);
+    hipLaunchKernelGGL(tsdf_lowp_narrow_kernel<true>, dim3((unsigned)blocks), dim3(kSlabWG), 0, s, a);
   else
-    hipLaunchKernelGGL(tsdf_lowp_narrow_kernel<false>, dim3((unsigned)blocks), dim3(kLowpWG), 0, s, a);
+    hipLaunchKernelGGL(tsdf_lowp_narrow_kernel<false>, dim3((unsigned)blocks), dim3(kSlabWG), 0, s, a);
   return launched();
 }
 

@@ -2,8 +2,8 @@
 // (include/tsdf_obb.h).
 //
 // A translation unit and a library of its own, next to libtsdf_hip.so and the four extensions (all frozen).  It takes the
-// status codes and tsdf_cam from include/tsdf.h and the host preamble every library here has from device.inc; nothing
-// else of the product's .inc files is included, and there is no device global: the launch is self-contained.
+// status codes and tsdf_cam from include/tsdf.h, the host preamble every library here has from device.inc and the header
+// rule and default camera from prim.inc; nothing else of the product's .inc files is included, and there is no device global: the launch is self-contained.
 //
 // tsdf_obb_kernel: one workgroup of 1024 threads (16 wave64) per frame, a grid-stride loop over frames when n exceeds the
 // grid.  Per frame:
@@ -35,13 +35,12 @@
 namespace {
 
 #include "device.inc"   // check_device, launched, misaligned: the host preamble of every library here
+#include "prim.inc"     // kDefaultCam, header_ok
 
 constexpr int kObbWG = 1024;              // threads per workgroup
 constexpr int kObbWaves = kObbWG / 64;    // 16 wave64
 constexpr int kObbMaxBlocks = 1 << 16;    // frames beyond the grid are reached by the grid-stride loop
 constexpr int kObbSweeps = 12;
-
-const tsdf_cam kDefaultCam = {241.42, 160.0, 120.0, 1.0f, 3.0f};   // pre/tsdf_numba.py:8-10, as in include/tsdf.h
 
 typedef float obb_f4 __attribute__((ext_vector_type(4), aligned(4)));   // 16 bytes on a 4-byte boundary
 
@@ -190,17 +189,15 @@ __global__ __launch_bounds__(kObbWG) void tsdf_obb_kernel(ObbArgs a) {
     const int32_t *hd = a.headers + 6 * i;
     const int left = hd[2], top = hd[3], right = hd[4], bottom = hd[5];
     const int64_t off0 = a.offsets[i], off1 = a.offsets[i + 1];
-    const int64_t bw64 = (int64_t)right - left, bh64 = (int64_t)bottom - top;
-    const bool hdr_ok = bw64 > 0 && bh64 > 0 && bw64 <= 0x7fffffff && bh64 <= 0x7fffffff && bw64 * bh64 == off1 - off0 &&
-                        off0 >= 0 && off1 <= a.depth_len;
-    if (!hdr_ok) {   // (uniform)
+    const int64_t depth_len = a.depth_len;
+    if (!header_ok(left, top, right, bottom, off0, off1, depth_len)) {   // (uniform)
       if (tid == 0) {
         obb_identity(xf, mo, 0.0);
         if (a.status) a.status[i] = TSDF_FRAME_BAD_HEADER;
       }
       continue;
     }
-    const int bw = (int)bw64, bh = (int)bh64;
+    const int bw = right - left, bh = bottom - top;   // header_ok: both are positive ints
     const float *__restrict__ d = a.depth + off0;
 
     // pass 1: the count and the sum of the points

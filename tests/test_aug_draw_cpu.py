@@ -3,13 +3,11 @@
 libtsdf_augment.so is checked as far as it goes without a GPU — exports, version, argument checks before device work."""
 import ctypes
 import itertools
-import os
 
 import numpy as np
 import pytest
 from abi_util import declared_functions, exported
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 M = 1 << 64
 
 
@@ -98,14 +96,6 @@ def test_augment_library_exports_exactly_its_header(pkg):
     assert A.tsdf_augment_version() == 1 == pkg._lib.AUGMENT_VERSION
     assert pkg._lib.load_augment() is A
     assert pkg._lib.load() is not A and pkg._lib.load().tsdf_version() == 7          # the product is untouched
-
-
-def test_missing_augment_library_names_the_make_target(pkg, monkeypatch):
-    monkeypatch.delitem(pkg._lib._ext_libs, "augment", raising=False)
-    monkeypatch.setitem(pkg._lib._EXTS, "augment", pkg._lib._EXTS["augment"]._replace(
-        path=os.path.join(ROOT, "build", "no_such_libtsdf_augment.so")))
-    with pytest.raises(ImportError, match="csrc augment"):
-        pkg._lib.load_augment()
 
 
 def test_argument_validation_happens_before_device_work(pkg):

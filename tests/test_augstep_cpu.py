@@ -2,13 +2,11 @@
 without a GPU — exports, version, argument checks before device work —, the two frozen libraries beside it, the new
 ``aug`` / ``graph`` values of the consumers, and the numpy side of the per-frame contract."""
 import ctypes
-import os
 
 import numpy as np
 import pytest
 from abi_util import declared_functions, exported
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 M = 1 << 64
 
 
@@ -26,14 +24,6 @@ def test_augstep_library_exports_exactly_its_header(pkg):
     assert A is not S and A.tsdf_augment_version() == 1
     funcs, named = exported(pkg._lib.AUGMENT_LIB_PATH)
     assert funcs == named == ["tsdf_aug_draw_hip", "tsdf_augment_version"] == declared_functions("tsdf_augment.h")
-
-
-def test_missing_augstep_library_names_the_make_target(pkg, monkeypatch):
-    monkeypatch.delitem(pkg._lib._ext_libs, "augstep", raising=False)
-    monkeypatch.setitem(pkg._lib._EXTS, "augstep", pkg._lib._EXTS["augstep"]._replace(
-        path=os.path.join(ROOT, "build", "no_such_libtsdf_augstep.so")))
-    with pytest.raises(ImportError, match="csrc augstep"):
-        pkg._lib.load_augstep()
 
 
 def test_argument_validation_happens_before_device_work(pkg):

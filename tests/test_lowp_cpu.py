@@ -32,7 +32,7 @@ def test_make_rules_cross_compile_for_gfx950():
 
 # ---- binding ----
 def test_row_binds_exactly_its_header_with_types(pkg):
-    ext = pkg._lib._EXTS_LATER["lowp"]
+    ext = pkg._lib._EXTS["lowp"]
     want = ["tsdf_lowp_narrow_hip", "tsdf_lowp_version", "tsdf_voxelize_grid_lowp_hip"]
     assert declared_functions("tsdf_lowp.h") == want == sorted([ext.version_symbol, *ext.entries])
     funcs, named = exported(pkg._lib.LOWP_LIB_PATH)
@@ -51,21 +51,9 @@ def test_row_binds_exactly_its_header_with_types(pkg):
         assert list(getattr(L, name).argtypes) == args
     assert (pkg._lib.TSDF_LOWP_F16, pkg._lib.TSDF_LOWP_BF16) == (1, 2)
     assert pkg._lib.load_lowp() is L and L is not pkg._lib.load()
-    # the pinned table is what it was, and the product beside it too
-    assert sorted(pkg._lib._EXTS) == ["auggrid", "augment", "augstep", "depth16"]
-    assert sorted(pkg._lib._EXTS_LATER) == ["lowp", "obb"]
+    # the table holds the six extensions, and the product beside it is what it was
+    assert sorted(pkg._lib._EXTS) == ["auggrid", "augment", "augstep", "depth16", "lowp", "obb"]
     assert pkg._lib.load().tsdf_version() == 7
-
-
-def test_wrong_version_and_missing_library_raise_import_error(pkg, monkeypatch):
-    row = pkg._lib._EXTS_LATER["lowp"]
-    monkeypatch.delitem(pkg._lib._ext_libs, "lowp", raising=False)
-    monkeypatch.setitem(pkg._lib._EXTS_LATER, "lowp", row._replace(version=2))
-    with pytest.raises(ImportError, match="version 1"):
-        pkg._lib.load_lowp()
-    monkeypatch.setitem(pkg._lib._EXTS_LATER, "lowp", row._replace(path=os.path.join(ROOT, "build", "no_such_libtsdf_lowp.so")))
-    with pytest.raises(ImportError, match="csrc lowp"):
-        pkg._lib.load_lowp()
 
 
 def test_argument_validation_happens_before_device_work(pkg):

@@ -14,12 +14,11 @@ from abi_util import declared_functions, exported  # noqa: E402
 
 torch = pytest.importorskip("torch")
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 # ---- binding ----
 def test_row_binds_exactly_its_header_with_types(pkg):
-    ext = pkg._lib._EXTS_LATER["obb"]
+    ext = pkg._lib._EXTS["obb"]
     want = ["tsdf_obb_version", "tsdf_obb_xforms_hip"]
     assert declared_functions("tsdf_obb.h") == want == sorted([ext.version_symbol, *ext.entries])
     funcs, named = exported(pkg._lib.OBB_LIB_PATH)
@@ -34,20 +33,9 @@ def test_row_binds_exactly_its_header_with_types(pkg):
     assert list(L.tsdf_obb_xforms_hip.argtypes) == [vp, i64, vp, vp, i, ctypes.POINTER(pkg._lib.TsdfCam), vp, vp, vp, vp]
     assert list(L.tsdf_obb_xforms_hip.argtypes) == ext.entries["tsdf_obb_xforms_hip"]
     assert pkg._lib.load_obb() is L and L is not pkg._lib.load()
-    # the pinned table is what it was, and the product beside it too
-    assert sorted(pkg._lib._EXTS) == ["auggrid", "augment", "augstep", "depth16"]
+    # the table holds the six extensions, and the product beside it is what it was
+    assert sorted(pkg._lib._EXTS) == ["auggrid", "augment", "augstep", "depth16", "lowp", "obb"]
     assert pkg._lib.load().tsdf_version() == 7
-
-
-def test_wrong_version_and_missing_library_raise_import_error(pkg, monkeypatch):
-    row = pkg._lib._EXTS_LATER["obb"]
-    monkeypatch.delitem(pkg._lib._ext_libs, "obb", raising=False)
-    monkeypatch.setitem(pkg._lib._EXTS_LATER, "obb", row._replace(version=2))
-    with pytest.raises(ImportError, match="version 1"):
-        pkg._lib.load_obb()
-    monkeypatch.setitem(pkg._lib._EXTS_LATER, "obb", row._replace(path=os.path.join(ROOT, "build", "no_such_libtsdf_obb.so")))
-    with pytest.raises(ImportError, match="csrc obb"):
-        pkg._lib.load_obb()
 
 
 def test_argument_validation_happens_before_device_work(pkg):

@@ -32,30 +32,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 pkg = importlib.import_module("handposeestimation-with-3d-cnns_amd")
 synth = importlib.import_module("handposeestimation-with-3d-cnns_amd.synth")
-
-
-def timed_us(fn, iters: int) -> float:
-    """Microseconds per launch: device events around ``iters`` back-to-back launches."""
-    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    a.record()
-    for _ in range(iters):
-        fn()
-    b.record()
-    b.synchronize()
-    return 1e3 * a.elapsed_time(b) / iters
-
-
-def take_turns(legs: dict, iters: int, warmup: int, rounds: int) -> dict:
-    for fn in legs.values():
-        for _ in range(warmup):
-            fn()
-    torch.cuda.synchronize()
-    times = {k: [] for k in legs}
-    for _ in range(rounds):
-        for k, fn in legs.items():
-            times[k].append(timed_us(fn, iters))
-    return {k: dict(us=round(float(np.median(v)), 2), us_min=round(min(v), 2), us_max=round(max(v), 2))
-            for k, v in times.items()}
+from _timing import take_turns  # noqa: E402  (tools/_timing.py, beside this file)
 
 
 def main():

@@ -14,7 +14,9 @@ least 50); the legs of a shape take turns for --rounds rounds and the median rou
 drift of the machine meets all alike.  The wrappers allocate their outputs (torch's caching allocator: no device
 allocation in the steady state).  Bytes read per launch of a one-read pass: 4 * pixels.
 
-    python tools/bench_obb.py [--iters 100] [--warmup 20] [--rounds 5] [--out x.json]
+``--lib PATH`` times another build of libtsdf_obb.so (an A/B of two builds) in the obb_xforms and voxelize_obb legs.
+
+    python tools/bench_obb.py [--iters 100] [--warmup 20] [--rounds 5] [--lib x.so] [--out x.json]
 """
 from __future__ import annotations
 
@@ -31,30 +33,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 pkg = importlib.import_module("handposeestimation-with-3d-cnns_amd")
 synth = importlib.import_module("handposeestimation-with-3d-cnns_amd.synth")
-
-
-def timed_us(fn, iters: int) -> float:
-    """Microseconds per launch: device events around ``iters`` back-to-back launches."""
-    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    a.record()
-    for _ in range(iters):
-        fn()
-    b.record()
-    b.synchronize()
-    return 1e3 * a.elapsed_time(b) / iters
-
-
-def take_turns(legs: dict, iters: int, warmup: int, rounds: int) -> dict:
-    for fn in legs.values():
-        for _ in range(warmup):
-            fn()
-    torch.cuda.synchronize()
-    times = {k: [] for k in legs}
-    for _ in range(rounds):
-        for k, fn in legs.items():
-            times[k].append(timed_us(fn, iters))
-    return {k: dict(us=round(float(np.median(v)), 2), us_min=round(min(v), 2), us_max=round(max(v), 2))
-            for k, v in times.items()}
+from _timing import take_turns  # noqa: E402  (tools/_timing.py, beside this file)
 
 
 def main():
@@ -62,10 +41,14 @@ def main():
     ap.add_argument("--iters", type=int, default=100)
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--rounds", type=int, default=5)
+    ap.add_argument("--lib")
     ap.add_argument("--out")
     a = ap.parse_args()
     assert a.iters >= 50, "time at least 50 launches"
     assert torch.cuda.is_available(), "bench_obb.py needs a HIP device"
+    if a.lib:
+        row = pkg._lib._EXTS["obb"]
+        pkg._lib._EXTS["obb"] = row._replace(path=os.path.abspath(a.lib))
     dev = torch.device("cuda:0")
     R = 32
     rows = []
