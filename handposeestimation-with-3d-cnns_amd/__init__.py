@@ -27,16 +27,21 @@ Volumes in the cloud's principal axes:   obb_xforms (per-frame OBB maps from the
 Volumes in float16 / bfloat16:           voxelize_grid_lowp (the plain voxel pass narrowed in registers: libtsdf_lowp.so,
                                          include/tsdf_lowp.h), voxelize_lowp, narrow_volumes, process_batch(dtype=...),
                                          ResidentLoader(volume_dtype=...)
+... under a per-frame map:               map_grids (the map's grid placement on its own), voxelize_map_grid_lowp (the
+                                         augmented voxel pass narrowed in registers: libtsdf_maplowp.so,
+                                         include/tsdf_maplowp.h), voxelize_aug_lowp, voxelize_obb(dtype=...),
+                                         process_batch_aug(dtype=...), AugmentedStep(dtype=...)
 """
 from . import _lib  # noqa: F401
 from ._lib import TsdfCam, TsdfError, default_cam  # noqa: F401
-from .voxelize import (AabbBatch, AugmentedStep, CloudGridBatch, ObbBatch, PointCloudBatch, PoseError, ProcessAugBatch, ProcessBatch, TsdfBatch,  # noqa: F401
+from .voxelize import (AabbBatch, AugmentedStep, CloudGridBatch, MapGridBatch, ObbBatch, PointCloudBatch, PoseError, ProcessAugBatch, ProcessBatch, TsdfBatch,  # noqa: F401
                        aabb,
                        aug_state, aug_xforms, aug_xforms_at, cloud_grids, denormalize_joints, empty_batch,
                        frames_within, joints_within, normalize_joints, point_clouds, pose_error, process_batch, process_batch_aug,
                        project_joints, release_stream, transform_joints, voxel_pixels, voxelize_aug_grid,
                        voxelize, voxelize_aug, voxelize_grid, voxelize_indexed, voxelize_labels, widen_depth16,
-                       invert_xforms, obb_xforms, voxelize_obb, narrow_volumes, voxelize_grid_lowp, voxelize_lowp)
+                       invert_xforms, obb_xforms, voxelize_obb, narrow_volumes, voxelize_grid_lowp, voxelize_lowp,
+                       map_grids, voxelize_aug_lowp, voxelize_map_grid_lowp)
 from .pca import JointPCA, fit_joint_pca  # noqa: F401
 from . import augment, dataset, export, packing, pca, shard, synth  # noqa: F401
 from .dataset import MSRA_Dataset, MSRADepthDataset, ResidentLoader, VoxelBatch, VoxelLoader  # noqa: F401
@@ -51,4 +56,5 @@ __all__ = ["voxelize", "voxelize_labels", "voxelize_indexed", "ResidentLoader", 
            "point_clouds", "PointCloudBatch", "cloud_grids", "CloudGridBatch", "process_batch", "ProcessBatch", "aug_xforms",
            "aug_xforms_at", "aug_state", "AugmentedStep", "voxelize_aug_grid", "transform_joints", "process_batch_aug",
            "ProcessAugBatch", "widen_depth16", "obb_xforms", "voxelize_obb", "invert_xforms", "ObbBatch",
-           "voxelize_grid_lowp", "voxelize_lowp", "narrow_volumes"]
+           "voxelize_grid_lowp", "voxelize_lowp", "narrow_volumes", "map_grids", "MapGridBatch", "voxelize_map_grid_lowp",
+           "voxelize_aug_lowp"]

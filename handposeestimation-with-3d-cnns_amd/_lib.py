@@ -119,6 +119,11 @@ LOWP_VERSION = 1
 TSDF_LOWP_F16 = 1    # enum tsdf_lowp_dtype of include/tsdf_lowp.h
 TSDF_LOWP_BF16 = 2
 
+# The extension library of include/tsdf_maplowp.h (make -C csrc maplowp): the grid placement under a per-frame map on its
+# own, and the augmented voxel pass on a caller-supplied grid written as float16 / bfloat16 voxels.  A binary of its own.
+MAPLOWP_LIB_PATH = os.path.join(_HERE, "libtsdf_maplowp.so")
+MAPLOWP_VERSION = 1
+
 
 class _Ext(NamedTuple):
     """A row of the extension table: libtsdf_<name>.so, built by ``make -C csrc <name>`` from include/tsdf_<name>.h."""
@@ -163,6 +168,18 @@ _EXTS = {
                                         _vp, _vp],
         # in, count, dtype, stream, out
         "tsdf_lowp_narrow_hip": [_vp, _i64, _i, _vp, _vp],
+    }),
+}
+
+# The rows added since the table above was pinned at six by the tests of the libraries it holds; _load_ext looks here
+# after _EXTS.  One table again is a clean-up of its own ("Adding an extension library").
+_EXTS_MORE = {
+    "maplowp": _Ext(MAPLOWP_LIB_PATH, "tsdf_maplowp_version", MAPLOWP_VERSION, {
+        # depth, depth_len, offsets, headers, n_src, index, n, R, cam, stream, xforms, grid, max_l, mid_p, status
+        "tsdf_map_place_hip": [_vp, _i64, _vp, _vp, _i64, _vp, _i, _i, ctypes.POINTER(TsdfCam), _vp, _vp, _vp, _vp, _vp, _vp],
+        # depth, depth_len, offsets, headers, n_src, index, n, R, cam, layout, dtype, stream, xforms, grid, tsdf, status
+        "tsdf_voxelize_map_grid_lowp_hip": [_vp, _i64, _vp, _vp, _i64, _vp, _i, _i, ctypes.POINTER(TsdfCam), _i, _i, _vp, _vp,
+                                            _vp, _vp, _vp],
     }),
 }
 
@@ -262,7 +279,7 @@ def _load_ext(name: str):
     L = _ext_libs.get(name)
     if L is not None:
         return L
-    ext = _EXTS[name]
+    ext = _EXTS[name] if name in _EXTS else _EXTS_MORE[name]
     if not os.path.exists(ext.path):
         raise ImportError(f"{ext.path} not found: build it with `make -C handposeestimation-with-3d-cnns_amd/csrc "
                           f"{name}` (__graft_entry__.build() does). There is no CPU fallback.")
@@ -303,6 +320,11 @@ def load_obb():
 def load_lowp():
     """libtsdf_lowp.so, the library of include/tsdf_lowp.h."""
     return _load_ext("lowp")
+
+
+def load_maplowp():
+    """libtsdf_maplowp.so, the library of include/tsdf_maplowp.h."""
+    return _load_ext("maplowp")
 
 
 @contextlib.contextmanager

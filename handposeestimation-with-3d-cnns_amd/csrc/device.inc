@@ -1,5 +1,5 @@
 // device.inc — the host preamble of every library here: tsdf_hip.hip and the extensions (tsdf_augment.hip,
-// tsdf_augstep.hip, tsdf_auggrid.hip, tsdf_depth16.hip, tsdf_obb.hip, tsdf_lowp.hip) include it, so "is this a device the
+// tsdf_augstep.hip, tsdf_auggrid.hip, tsdf_depth16.hip, tsdf_obb.hip, tsdf_lowp.hip, tsdf_maplowp.hip) include it, so "is this a device the
 // code object runs on" and the two return idioms of an entry point exist once.  Host code only; it exports nothing.
 // (The device primitives that exist once are in prim.inc.)
 //   check_device   the current device is a gfx950

@@ -1,5 +1,5 @@
 // prim.inc — the device primitives every voxelizing library here shares: tsdf_hip.hip (before common.inc),
-// tsdf_auggrid.hip, tsdf_obb.hip and tsdf_lowp.hip include it, so each rule below exists once.
+// tsdf_auggrid.hip, tsdf_obb.hip, tsdf_lowp.hip and tsdf_maplowp.hip include it, so each rule below exists once.
 //   kDefaultCam    the camera an entry uses when the caller passes none
 //   trunc_i32      int() of a float64, the pixel index's truncation
 //   finite32       a float32 that is neither infinite nor NaN

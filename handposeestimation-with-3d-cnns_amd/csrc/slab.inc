@@ -1,9 +1,9 @@
-// slab.inc — the scaffold of a kernel that voxelizes on a grid row the caller supplies: tsdf_auggrid.hip and
-// tsdf_lowp.hip include it (after prim.inc, inside their anonymous namespace); the product does not.  Such a kernel is
+// slab.inc — the scaffold of a kernel that voxelizes on a grid row the caller supplies: tsdf_auggrid.hip, tsdf_lowp.hip
+// and tsdf_maplowp.hip include it (after prim.inc, inside their anonymous namespace); the product does not.  Such a kernel is
 // launched as n x ceil(R / slab) workgroups of kSlabWG threads, and a workgroup owns `slab` consecutive slices (indices
 // of the slowest output axis) of one batch position.  What is the same for all of them is here:
 //   slab_of_block    workgroup -> (batch position, slab index, slices [sb, se))
-//   slab_frame       a source frame's crop, depth, grid row and status
+//   slab_frame       a source frame's crop, depth, grid row and status (slab_frame_row: on a row the kernel picks)
 //   slab_zero_fill   the zeros of a slab whose frame is not OK
 //   slab_plan        host: slices per workgroup, workgroups per position, workgroups in all
 //   slab_bad_shape   host: the R / layout test of an entry
@@ -37,25 +37,32 @@ struct SlabFrame {
   int status;                     // TSDF_FRAME_*: a bad header before an unusable grid row
 };
 
-// Source frame g of the tables (all uniform).  src_ok: g lies inside the tables — the caller has clamped a g that does
-// not, and the frame is then a bad header.  A bad frame's depth is not read.  (depth_len and src_ok by reference, from the
-// caller's locals: see header_ok.)
-__device__ __forceinline__ SlabFrame slab_frame(const int64_t &depth_len, const int64_t *offsets,
-                                                const int32_t *headers, const float *grid, int64_t g,
-                                                const bool &src_ok) {
+// A source frame g of the tables with the grid row gr to voxelize it on (all uniform).  src_ok: g lies inside the
+// tables — the caller has clamped a g that does not, and the frame is then a bad header.  A bad frame's depth is not read.
+// (depth_len and src_ok by reference, from the caller's locals: see header_ok.)
+__device__ __forceinline__ SlabFrame slab_frame_row(const int64_t &depth_len, const int64_t *offsets,
+                                                    const int32_t *headers, const float *gr, int64_t g,
+                                                    const bool &src_ok) {
   SlabFrame f;
   const int32_t *hd = headers + 6 * g;
   f.left = hd[2], f.top = hd[3], f.right = hd[4], f.bottom = hd[5];
   const int64_t off0 = offsets[g], off1 = offsets[g + 1];
   f.bw = (int64_t)f.right - f.left;
   const bool hdr_ok = src_ok && header_ok(f.left, f.top, f.right, f.bottom, off0, off1, depth_len);
-  const float *gr = grid + 8 * g;
   f.ox = gr[0], f.oy = gr[1], f.oz = gr[2], f.vl = gr[3], f.td = gr[4];
   const bool grid_ok =
       f.td > 0.0f && finite32(f.td) && finite32(f.vl) && finite32(f.ox) && finite32(f.oy) && finite32(f.oz);
   f.status = !hdr_ok ? TSDF_FRAME_BAD_HEADER : !grid_ok ? TSDF_FRAME_DEGENERATE : TSDF_FRAME_OK;
   f.off0 = off0;
   return f;
+}
+
+// The grid rows belong to SOURCE frames (tsdf_auggrid.hip, tsdf_lowp.hip): row g of `grid`.  Where they belong to batch
+// positions (tsdf_maplowp.hip) the kernel calls slab_frame_row with the position's row.
+__device__ __forceinline__ SlabFrame slab_frame(const int64_t &depth_len, const int64_t *offsets,
+                                                const int32_t *headers, const float *grid, int64_t g,
+                                                const bool &src_ok) {
+  return slab_frame_row(depth_len, offsets, headers, grid + 8 * g, g, src_ok);
 }
 
 // (uniform) zeros for a slab: slices [sb, se) of every channel are contiguous, `per` 16-byte pieces VEC of them.

@@ -3,8 +3,8 @@
 //
 // A translation unit and a library of its own, next to libtsdf_hip.so and the other extension libraries (all frozen).  It
 // takes the status codes, tsdf_cam and the layout enum from include/tsdf.h, the host preamble every library here has
-// from device.inc, the device primitives from prim.inc and the slab scaffold it shares with tsdf_auggrid.hip from
-// slab.inc; the product's plain voxel arithmetic (phase2.inc::voxel_values4 and the tables of frame.inc that feed
+// from device.inc, the device primitives from prim.inc, the slab scaffold it shares with tsdf_auggrid.hip from
+// slab.inc and the narrowing and the stores it shares with tsdf_maplowp.hip from narrow.inc; the product's plain voxel arithmetic (phase2.inc::voxel_values4 and the tables of frame.inc that feed
 // it) is RESTATED here operation for operation, nothing else of the product's .inc files is included, and there is no
 // device global: every launch is self-contained.
 //
@@ -43,16 +43,11 @@ namespace {
 #include "device.inc"   // check_device, launched, misaligned: the host preamble of every library here
 #include "prim.inc"     // kDefaultCam, trunc_i32, finite32, f32_round_up, header_ok
 #include "slab.inc"     // workgroup <-> slab, the frame's header and grid row, zero-fill, host sizing
+#include "narrow.inc"   // narrow2, store_vol, Piece: the 2-byte store side, shared with tsdf_maplowp.hip
 
 constexpr int kNarrowMaxBlocks = 1 << 16;   // the narrowing kernel strides over anything larger
 
 typedef float lowp_f4 __attribute__((ext_vector_type(4)));
-typedef float lowp_f2 __attribute__((ext_vector_type(2)));
-typedef unsigned lowp_u4 __attribute__((ext_vector_type(4)));
-typedef unsigned lowp_u2 __attribute__((ext_vector_type(2)));
-typedef _Float16 lowp_h2 __attribute__((ext_vector_type(2)));
-typedef __bf16 lowp_b2 __attribute__((ext_vector_type(2)));
-typedef __attribute__((address_space(1))) void *GlobalOut;
 
 struct LowpArgs {
   const float *depth;
@@ -69,42 +64,6 @@ struct LowpArgs {
   const float *grid;        // [n_src][8]
   uint16_t *out;            // [n][3][R][R][R]
   int32_t *status;          // [n] or null
-};
-
-// Two float32 narrowed by round-to-nearest-even into one 32-bit word, the first in the low half.  float16: v_cvt_f16_f32
-// (the kernels run with float16 subnormals on); bfloat16: v_cvt_pk_bf16_f32, gfx950's own conversion.
-template <bool BF16>
-__device__ __forceinline__ unsigned narrow2(float lo, float hi) {
-  const lowp_f2 v = {lo, hi};
-  if constexpr (BF16) {
-    return __builtin_bit_cast(unsigned, __builtin_convertvector(v, lowp_b2));
-  } else {
-    return __builtin_bit_cast(unsigned, __builtin_convertvector(v, lowp_h2));
-  }
-}
-
-#ifndef TSDF_LOWP_STORE_ASM
-#define TSDF_LOWP_STORE_ASM "nt"
-#endif
-// One store of the output volume: 16 bytes (8 voxels) or 8 bytes (4 voxels).  There is no builtin for the scope bits of
-// a plain store, hence the inline assembly; the s_nop covers the "VALU overwrites the data registers of a wide store"
-// hazard the compiler can no longer see (as in the product's store_vol4).
-__device__ __forceinline__ void store_vol(GlobalOut p, lowp_u4 v) {
-  asm volatile("global_store_dwordx4 %0, %1, off " TSDF_LOWP_STORE_ASM "\n\ts_nop 1" ::"v"(p), "v"(v) : "memory");
-}
-__device__ __forceinline__ void store_vol(GlobalOut p, lowp_u2 v) {
-  asm volatile("global_store_dwordx2 %0, %1, off " TSDF_LOWP_STORE_ASM "\n\ts_nop 1" ::"v"(p), "v"(v) : "memory");
-}
-
-template <int V>
-struct Piece;
-template <>
-struct Piece<8> {
-  typedef lowp_u4 type;
-};
-template <>
-struct Piece<4> {
-  typedef lowp_u2 type;
 };
 
 // V = voxels per lane and item (8: 16-byte stores, 4: 8-byte stores)

@@ -1,0 +1,523 @@
+// tsdf_maplowp.hip — libtsdf_maplowp.so: the grid placement under a per-frame map on its own, and the augmented voxel
+// pass on a caller-supplied grid written as float16 / bfloat16 voxels (include/tsdf_maplowp.h).
+//
+// A translation unit and a library of its own, next to libtsdf_hip.so and the other extension libraries (all frozen).  It
+// takes the status codes, tsdf_cam and the layout enum from include/tsdf.h, the dtype enum from include/tsdf_lowp.h, the
+// host preamble every library here has from device.inc, the device primitives from prim.inc, the slab scaffold it shares
+// with tsdf_auggrid.hip and tsdf_lowp.hip from slab.inc and the store side it shares with tsdf_lowp.hip from narrow.inc.
+// The augmented voxel arithmetic (tsdf_auggrid.hip::tsdf_aug_grid_kernel) and the float32 glue (phase1.inc::glue,
+// frame.inc::place_grid) are RESTATED here operation for operation; nothing of the product's other .inc files is
+// included, and there is no device global: every launch is self-contained.
+//
+// tsdf_map_place_kernel: one workgroup of 1024 threads (16 wave64) per batch position, a grid-stride loop over positions
+// when n exceeds the grid — the shape of tsdf_obb_kernel.  Per position:
+//   1. the source frame (the index, if any) and the header rule (uniform); a bad frame's depth is not read;
+//   2. one pass over the crop: wave <-> rows, lane <-> groups of four consecutive columns, one 16-byte load per group
+//      through a vector type DECLARED 4-byte aligned, the W mod 4 last columns one by one.  A row narrower than 129
+//      columns needs 32 lanes or fewer, so a wave then takes 2, 4, 8 or 16 rows at a time (the pass is bound by its
+//      float64 arithmetic: idle lanes are lost time).  Per valid pixel the IEEE
+//      division by the focal length (the compiler's sequence: exact for every F), the back-projection, the three fused
+//      rows of the forward map, three roundings to float32 and six running extremes per lane;
+//   3. a butterfly over the wave, the wave extremes through LDS, and thread 0 takes the 16 of them, runs the float32 glue
+//      and the degenerate rule and writes the row, max_l, mid_p and the status with plain stores.
+// Minimum and maximum are order-free, so any split of the pixels gives the same bits.  No atomics, no communication
+// between workgroups, two barriers per position (the second keeps the next position's wave extremes out of s_red while
+// thread 0 still reads it).
+//
+// tsdf_map_grid_lowp_kernel: n x ceil(R / slab) workgroups of 256 threads; a workgroup owns `slab` consecutive slices of
+// one batch position.  It
+//   1. resolves its source frame and checks the frame's header and the POSITION's grid row (all uniform); a position that
+//      is not OK has its slab zero-filled and workgroup 0 of the position writes the status;
+//   2. tabulates the per-axis terms of tsdf_aug_grid_kernel (3 x R entries of 32 bytes in LDS);
+//   3. walks its slab in items of V consecutive voxels of the fastest axis (V = 8 when R % 8 == 0, else 4), one item per
+//      lane and pass, as V / 4 quads: a quad projects its four voxels and issues their four gathers (always in bounds: a
+//      rejected voxel reads the crop's first pixel) before the distance terms of the first one, then narrows its 3 x 4
+//      float32 values pairwise into 2 dwords per channel.  Only the packed dwords of an earlier quad stay live while
+//      the next one is computed; the item leaves as ONE 16-byte store per channel (V = 4: one 8-byte store).
+// No LDS staging of the crop, no work queue, no communication between workgroups, no atomics.
+// Compiled with -ffp-contract=off, fma only where __builtin_fma is written.
+
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+#include <string.h>
+
+#include <atomic>
+
+#include "../../include/tsdf_maplowp.h"
+
+namespace {
+
+#include "device.inc"   // check_device, launched, misaligned: the host preamble of every library here
+#include "prim.inc"     // kDefaultCam, trunc_i32, finite32, header_ok
+#include "slab.inc"     // workgroup <-> slab, the frame's header and grid row, zero-fill, host sizing
+#include "narrow.inc"   // narrow2, store_vol, Piece: the 2-byte store side
+
+constexpr int kPlaceWG = 1024;               // threads per workgroup of the placement
+constexpr int kPlaceWaves = kPlaceWG / 64;   // 16 wave64
+constexpr int kPlaceMaxBlocks = 1 << 16;     // positions beyond the grid are reached by the grid-stride loop
+
+typedef float map_f4 __attribute__((ext_vector_type(4), aligned(4)));   // 16 bytes on a 4-byte boundary
+typedef double map_d4 __attribute__((ext_vector_type(4)));
+
+struct PlaceArgs {
+  const float *depth;
+  int64_t depth_len;
+  const int64_t *offsets;   // [n_src + 1]
+  const int32_t *headers;   // [n_src][6]
+  int64_t n_src;
+  const int64_t *index;     // [n] or null
+  int n, R;
+  double focal, cx, cy;
+  float eps, trunc_vox;
+  const double *xforms;     // [n][24]
+  float *grid;              // [n][8]
+  float *max_l;             // [n] or null
+  float *mid_p;             // [n][3] or null
+  int32_t *status;          // [n] or null
+};
+
+// the running extremes of one lane: a NaN moves neither (the oracle's "v < mn", "v > mx")
+struct Ext6 {
+  float mn0, mn1, mn2, mx0, mx1, mx2;
+};
+
+__device__ __forceinline__ void place_pixel(float d, int col, double yc, double F, double cx, float eps,
+                                            const double (&m)[12], Ext6 &e, int &any) {
+  if (!(__builtin_fabsf(d) >= eps)) return;   // NaN is invalid
+  const double d64 = (double)d;
+  const double q = d64 / F;                   // IEEE division
+  const double px = q * ((double)col - cx);
+  const double py = (-q) * yc;
+  const double pz = -d64;
+  const float o0 = (float)__builtin_fma(m[0], px, __builtin_fma(m[1], py, __builtin_fma(m[2], pz, m[3])));
+  const float o1 = (float)__builtin_fma(m[4], px, __builtin_fma(m[5], py, __builtin_fma(m[6], pz, m[7])));
+  const float o2 = (float)__builtin_fma(m[8], px, __builtin_fma(m[9], py, __builtin_fma(m[10], pz, m[11])));
+  e.mn0 = o0 < e.mn0 ? o0 : e.mn0;
+  e.mn1 = o1 < e.mn1 ? o1 : e.mn1;
+  e.mn2 = o2 < e.mn2 ? o2 : e.mn2;
+  e.mx0 = o0 > e.mx0 ? o0 : e.mx0;
+  e.mx1 = o1 > e.mx1 ? o1 : e.mx1;
+  e.mx2 = o2 > e.mx2 ? o2 : e.mx2;
+  any = 1;
+}
+
+// the extremes held by the lanes of a wave are never NaN: fminf / fmaxf are the plain minimum and maximum
+__device__ __forceinline__ float wave_min(float v) {
+#pragma unroll
+  for (int k = 32; k >= 1; k >>= 1) v = __builtin_fminf(v, __shfl_xor(v, k, 64));
+  return v;
+}
+__device__ __forceinline__ float wave_max(float v) {
+#pragma unroll
+  for (int k = 32; k >= 1; k >>= 1) v = __builtin_fmaxf(v, __shfl_xor(v, k, 64));
+  return v;
+}
+
+// what thread 0 writes for one position; a row that is not OK is all zero
+__device__ __forceinline__ void place_write(const PlaceArgs &a, int64_t i, float ox, float oy, float oz, float vl, float td,
+                                            float max_l, float m0, float m1, float m2, int status) {
+  float *g = a.grid + 8 * i;
+  g[0] = ox, g[1] = oy, g[2] = oz, g[3] = vl, g[4] = td, g[5] = 0.f, g[6] = 0.f, g[7] = 0.f;
+  if (a.max_l) a.max_l[i] = max_l;
+  if (a.mid_p) {
+    float *p = a.mid_p + 3 * i;
+    p[0] = m0, p[1] = m1, p[2] = m2;
+  }
+  if (a.status) a.status[i] = status;
+}
+
+__global__ __launch_bounds__(kPlaceWG) void tsdf_map_place_kernel(PlaceArgs a) {
+#pragma clang fp contract(off)
+  __shared__ float s_red[kPlaceWaves][8];   // per wave: min xyz, max xyz, any, pad
+
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const double F = a.focal, cx = a.cx, cy = a.cy;
+  const float eps = a.eps;
+  const float inf = __builtin_inff();
+
+  for (int64_t i = blockIdx.x; i < a.n; i += gridDim.x) {
+    // the source frame; outside the tables it is a bad header and nothing of it is read
+    const int64_t g = a.index ? a.index[i] : i;
+    bool ok = g >= 0 && g < a.n_src;   // (uniform)
+    int left = 0, top = 0, right = 0, bottom = 0;
+    int64_t off0 = 0;
+    if (ok) {
+      const int32_t *hd = a.headers + 6 * g;
+      left = hd[2], top = hd[3], right = hd[4], bottom = hd[5];
+      const int64_t off1 = a.offsets[g + 1], depth_len = a.depth_len;
+      off0 = a.offsets[g];
+      ok = header_ok(left, top, right, bottom, off0, off1, depth_len);
+    }
+    if (!ok) {
+      if (tid == 0) place_write(a, i, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, TSDF_FRAME_BAD_HEADER);
+      continue;
+    }
+    const int bw = right - left, bh = bottom - top;   // header_ok: both are positive ints
+    const float *__restrict__ d = a.depth + off0;
+    double m[12];
+#pragma unroll
+    for (int k = 0; k < 12; ++k) m[k] = a.xforms[24 * i + k];
+
+    Ext6 e = {inf, inf, inf, -inf, -inf, -inf};
+    int any = 0;
+    const int ngrp = bw >> 2, tail0 = ngrp << 2, ntail = bw - tail0;
+    // gl lanes per row: the smallest power of two that holds the row's groups (4..64), so a wave takes 64 / gl rows at
+    // a time and a crop of 130 columns keeps all 64 lanes busy, not 32 (uniform)
+    int sh = 6;
+    while (sh > 2 && (1 << (sh - 1)) >= ngrp) --sh;
+    const int gl = 1 << sh, rpw = 64 >> sh;
+    const int sub = lane >> sh, gq = lane & (gl - 1);
+    for (int r = wave * rpw + sub; r < bh; r += kPlaceWaves * rpw) {
+      const float *__restrict__ row = d + (int64_t)r * bw;
+      const double yc = (double)(top + r) - cy;
+      for (int q = gq; q < ngrp; q += gl) {
+        const map_f4 v = *reinterpret_cast<const map_f4 *>(row + 4 * q);
+        const int c0 = left + 4 * q;
+        place_pixel(v.x, c0, yc, F, cx, eps, m, e, any);
+        place_pixel(v.y, c0 + 1, yc, F, cx, eps, m, e, any);
+        place_pixel(v.z, c0 + 2, yc, F, cx, eps, m, e, any);
+        place_pixel(v.w, c0 + 3, yc, F, cx, eps, m, e, any);
+      }
+      if (gq < ntail) place_pixel(row[tail0 + gq], left + tail0 + gq, yc, F, cx, eps, m, e, any);
+    }
+    {
+      const float w0 = wave_min(e.mn0), w1 = wave_min(e.mn1), w2 = wave_min(e.mn2);
+      const float w3 = wave_max(e.mx0), w4 = wave_max(e.mx1), w5 = wave_max(e.mx2);
+      const float w6 = wave_max((float)any);
+      if (lane == 0) {
+        s_red[wave][0] = w0, s_red[wave][1] = w1, s_red[wave][2] = w2;
+        s_red[wave][3] = w3, s_red[wave][4] = w4, s_red[wave][5] = w5;
+        s_red[wave][6] = w6;
+      }
+    }
+    __syncthreads();
+    if (tid == 0) {
+      float mn0 = s_red[0][0], mn1 = s_red[0][1], mn2 = s_red[0][2];
+      float mx0 = s_red[0][3], mx1 = s_red[0][4], mx2 = s_red[0][5], anyf = s_red[0][6];
+#pragma unroll
+      for (int w = 1; w < kPlaceWaves; ++w) {
+        mn0 = __builtin_fminf(mn0, s_red[w][0]);
+        mn1 = __builtin_fminf(mn1, s_red[w][1]);
+        mn2 = __builtin_fminf(mn2, s_red[w][2]);
+        mx0 = __builtin_fmaxf(mx0, s_red[w][3]);
+        mx1 = __builtin_fmaxf(mx1, s_red[w][4]);
+        mx2 = __builtin_fmaxf(mx2, s_red[w][5]);
+        anyf = __builtin_fmaxf(anyf, s_red[w][6]);
+      }
+      if (!(anyf > 0.f)) {   // no valid pixel
+        place_write(a, i, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, TSDF_FRAME_DEGENERATE);
+      } else {
+        // the glue: float32, one rounding per operation, left to right
+        float mid0 = __fdiv_rn(__fadd_rn(mn0, mx0), 2.0f), len0 = __fsub_rn(mx0, mn0);
+        float mid1 = __fdiv_rn(__fadd_rn(mn1, mx1), 2.0f), len1 = __fsub_rn(mx1, mn1);
+        float mid2 = __fdiv_rn(__fadd_rn(mn2, mx2), 2.0f), len2 = __fsub_rn(mx2, mn2);
+        float max_l = len0;
+        if (len1 > max_l) max_l = len1;
+        if (len2 > max_l) max_l = len2;
+        float vl = __fdiv_rn(max_l, (float)a.R);
+        float td = __fmul_rn(vl, a.trunc_vox);
+        const float half_l = __fdiv_rn(max_l, 2.0f), half_v = __fdiv_rn(vl, 2.0f);
+        float ox = __fadd_rn(__fsub_rn(mid0, half_l), half_v);
+        float oy = __fadd_rn(__fsub_rn(mid1, half_l), half_v);
+        float oz = __fadd_rn(__fsub_rn(mid2, half_l), half_v);
+        // the degenerate rule: the extent positive and finite, the centre finite
+        const bool ext_ok = max_l > 0.f && finite32(max_l);
+        const bool mid_ok = finite32(mid0) && finite32(mid1) && finite32(mid2);
+        int status = TSDF_FRAME_OK;
+        if (!ext_ok || !mid_ok) {
+          status = TSDF_FRAME_DEGENERATE;
+          max_l = ox = oy = oz = vl = td = 0.f;
+          if (!mid_ok) mid0 = mid1 = mid2 = 0.f;   // a zero extent keeps its finite centre
+        }
+        place_write(a, i, ox, oy, oz, vl, td, max_l, mid0, mid1, mid2, status);
+      }
+    }
+    __syncthreads();   // the next position writes s_red: not before thread 0 has read this one's
+  }
+}
+
+struct MapLowpArgs {
+  const float *depth;
+  int64_t depth_len;
+  const int64_t *offsets;   // [n_src + 1]
+  const int32_t *headers;   // [n_src][6]
+  int64_t n_src;
+  const int64_t *index;     // [n] or null
+  int n, R;
+  int slab;    // slices per workgroup
+  int nslab;   // workgroups per batch position
+  double focal, cx, cy;
+  float eps;
+  const double *xforms;     // [n][24]
+  const float *grid;        // [n][8]
+  uint16_t *out;            // [n][3][R][R][R]
+  int32_t *status;          // [n] or null
+};
+
+// the per-frame constants of the distance terms (tsdf_aug_grid_kernel's)
+struct MapK {
+  double F, cx, cy, it;
+  double g00, g10, g20, g01, g11, g21, a02, a12, a22;
+  float eps;
+  int left, top, right, bottom;
+  int64_t bw;
+};
+
+// Four consecutive voxels of the fastest axis starting at grid index f4, in the row y of slice sl: the float32 values
+// of tsdf_aug_grid_kernel, operation for operation.  s_tab: [axis][index] = {A'_0a v'_a, A'_1a v'_a, A'_2a v'_a,
+// v'_a - b_a}, the z axis with + b'_i in its first three.
+template <int LAYOUT>
+__device__ __forceinline__ void map_quad(const map_d4 (&s_tab)[3][kSlabMaxR], const MapK &k, const float *__restrict__ d,
+                                         const map_d4 &ty, const map_d4 &ts, int f4, float (&v0)[4], float (&v1)[4],
+                                         float (&v2)[4]) {
+#pragma clang fp contract(off)
+  // ---- project the four voxels and gather their depths ----
+  int px[4], py[4];
+  float pd[4];
+  bool inb[4];
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    const map_d4 tf = s_tab[LAYOUT == 0 ? 0 : 2][f4 + j];   // the lane's own axis
+    const map_d4 tx = LAYOUT == 0 ? tf : ts, tz = LAYOUT == 0 ? ts : tf;
+    // v = T^-1(v') = (A'_i0 x' + A'_i1 y') + (A'_i2 z' + b'_i)
+    const double s0 = tx.x + ty.x, s1 = tx.y + ty.y, s2 = tx.z + ty.z;
+    const double vx = s0 + tz.x, vy = s1 + tz.y, vz = s2 + tz.z;
+    const double q = -k.F / vz;                              // IEEE division
+    const double mx = vx * q, my = (-vy) * q;
+    px[j] = trunc_i32(mx + k.cx);
+    py[j] = trunc_i32(my + k.cy);
+    inb[j] = px[j] >= k.left && px[j] < k.right && py[j] >= k.top && py[j] < k.bottom;
+    const int64_t at = inb[j] ? (int64_t)(py[j] - k.top) * k.bw + (px[j] - k.left) : 0;   // the load is always in bounds
+    pd[j] = d[at];
+  }
+  // ---- the distance terms ----
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    const double wf = s_tab[LAYOUT == 0 ? 0 : 2][f4 + j].w;
+    const double wx = LAYOUT == 0 ? wf : ts.w, wz = LAYOUT == 0 ? ts.w : wf;
+    float r0 = 0.f, r1 = 0.f, r2 = 0.f;
+    if (inb[j] && __builtin_fabsf(pd[j]) >= k.eps) {         // NaN is invalid
+      const double dxi = (double)px[j] - k.cx, dyi = (double)py[j] - k.cy, pd64 = (double)pd[j];
+      const double c0 = __builtin_fma(k.g00, dxi, __builtin_fma(k.g01, dyi, k.a02));
+      const double c1 = __builtin_fma(k.g10, dxi, __builtin_fma(k.g11, dyi, k.a12));
+      const double c2 = __builtin_fma(k.g20, dxi, __builtin_fma(k.g21, dyi, k.a22));
+      const double u0 = __builtin_fma(pd64, c0, wx);         // v'_i - w'_i, mm
+      const double u1 = __builtin_fma(pd64, c1, ty.w);
+      const double u2 = __builtin_fma(pd64, c2, wz);
+      const double t0 = u0 * k.it, t1 = u1 * k.it, t2 = u2 * k.it;
+      const double xx = t0 * t0;
+      const double sq = __builtin_fma(t2, t2, __builtin_fma(t1, t1, xx));
+      const bool nearv = sq <= 1.0;
+      double m0 = __builtin_fabs(t0), m1 = __builtin_fabs(t1), m2 = __builtin_fabs(t2);
+      if (!(m0 < 1.0)) m0 = 1.0;                             // min(|t|, 1); a NaN distance counts as far
+      if (!(m1 < 1.0)) m1 = 1.0;
+      if (!(m2 < 1.0)) m2 = 1.0;
+      if (!nearv) m0 = m1 = m2 = 1.0;
+      if (u2 < 0.0) {
+        m0 = -m0;
+        m1 = -m1;
+        m2 = -m2;
+      }
+      r0 = (float)m0;
+      r1 = (float)m1;
+      r2 = (float)m2;
+    }
+    v0[j] = r0;
+    v1[j] = r1;
+    v2[j] = r2;
+  }
+}
+
+// V = voxels per lane and item (8: 16-byte stores, 4: 8-byte stores)
+template <int LAYOUT, bool BF16, int V>
+__global__ __launch_bounds__(kSlabWG) void tsdf_map_grid_lowp_kernel(MapLowpArgs a) {
+#pragma clang fp contract(off)
+  typedef typename Piece<V>::type piece;
+  __shared__ map_d4 s_tab[3][kSlabMaxR];
+
+  const int tid = threadIdx.x;
+  const int R = a.R, RV = R / V;
+  const Slab blk = slab_of_block(a.nslab, a.slab, R);
+  const int64_t i = blk.i;
+  const int sb = blk.sb, se = blk.se;
+  const int64_t R3 = (int64_t)R * R * R;
+  uint16_t *__restrict__ out = a.out + i * 3 * R3;
+
+  // the source frame; outside the tables it is a bad header and nothing of it is read.  The grid row is the POSITION's.
+  const int64_t g = a.index ? a.index[i] : i;
+  const bool src_ok = g >= 0 && g < a.n_src;
+  const int64_t gs = src_ok ? g : 0, depth_len = a.depth_len;
+  const SlabFrame fr = slab_frame_row(depth_len, a.offsets, a.headers, a.grid + 8 * i, gs, src_ok);
+  const float ox = fr.ox, oy = fr.oy, oz = fr.oz, vl = fr.vl, td = fr.td;
+  if (blk.first() && tid == 0 && a.status) a.status[i] = fr.status;
+
+  if (fr.status != TSDF_FRAME_OK) {   // (uniform)
+    slab_zero_fill<lowp_u4>(out, R, sb, (int64_t)(se - sb) * R * R / 8, tid);   // R * R is a multiple of 16
+    return;
+  }
+
+  const double *__restrict__ xf = a.xforms + 24 * i;
+  for (int e = tid; e < 3 * R; e += kSlabWG) {
+    const int ax = e / R, idx = e - ax * R;
+    const float o = ax == 0 ? ox : ax == 1 ? oy : oz;
+    const double prod = (double)idx * (double)vl;
+    const double vp = (double)o + prod;                       // v'_a
+    map_d4 t;
+    t.x = xf[12 + ax] * vp;                                   // A'_0a v'_a
+    t.y = xf[16 + ax] * vp;
+    t.z = xf[20 + ax] * vp;
+    if (ax == 2) {                                            // (A'_i2 z' + b'_i)
+      t.x = t.x + xf[15];
+      t.y = t.y + xf[19];
+      t.z = t.z + xf[23];
+    }
+    t.w = vp - xf[4 * ax + 3];                                // v'_a - b_a
+    s_tab[ax][idx] = t;
+  }
+
+  // per-frame constants of the distance terms
+  MapK k;
+  k.F = a.focal, k.cx = a.cx, k.cy = a.cy;
+  const double iF = 1.0 / k.F;
+  k.it = 1.0 / (double)td;
+  const double p00 = xf[0] * iF, p10 = xf[4] * iF, p20 = xf[8] * iF;
+  k.g00 = -p00, k.g10 = -p10, k.g20 = -p20;                   // g_i0 = -(A_i0 * iF)
+  k.g01 = xf[1] * iF, k.g11 = xf[5] * iF, k.g21 = xf[9] * iF; // g_i1 = A_i1 * iF
+  k.a02 = xf[2], k.a12 = xf[6], k.a22 = xf[10];
+  k.eps = a.eps;
+  k.left = fr.left, k.top = fr.top, k.right = fr.right, k.bottom = fr.bottom;
+  k.bw = fr.bw;
+  const float *__restrict__ d = a.depth + fr.off0;
+  __syncthreads();
+
+  const int nit = (se - sb) * R * RV;
+  for (int item = tid; item < nit; item += kSlabWG) {
+    const int fv = (item % RV) * V;
+    const int t1 = item / RV;
+    const int y = t1 % R, sl = sb + t1 / R;
+    const map_d4 ty = s_tab[1][y];
+    const map_d4 ts = s_tab[LAYOUT == 0 ? 2 : 0][sl];        // the slice's axis: z (czyx) or x (cxyz)
+    piece o0, o1, o2;
+#pragma unroll
+    for (int h = 0; h < V / 4; ++h) {
+      float v0[4], v1[4], v2[4];
+      map_quad<LAYOUT>(s_tab, k, d, ty, ts, fv + 4 * h, v0, v1, v2);
+      o0[2 * h] = narrow2<BF16>(v0[0], v0[1]);
+      o0[2 * h + 1] = narrow2<BF16>(v0[2], v0[3]);
+      o1[2 * h] = narrow2<BF16>(v1[0], v1[1]);
+      o1[2 * h + 1] = narrow2<BF16>(v1[2], v1[3]);
+      o2[2 * h] = narrow2<BF16>(v2[0], v2[1]);
+      o2[2 * h + 1] = narrow2<BF16>(v2[2], v2[3]);
+    }
+    const int64_t e = ((int64_t)sl * R + y) * R + fv;        // o[c][slow][y][fast]
+    store_vol((GlobalOut)(out + e), o0);
+    store_vol((GlobalOut)(out + R3 + e), o1);
+    store_vol((GlobalOut)(out + 2 * R3 + e), o2);
+  }
+}
+
+bool bad_dtype(int dtype) { return dtype != TSDF_LOWP_F16 && dtype != TSDF_LOWP_BF16; }
+
+template <int LAYOUT, bool BF16>
+void launch_grid(const MapLowpArgs &a, int64_t blocks, hipStream_t s) {
+  if (a.R % 8 == 0)
+    hipLaunchKernelGGL((tsdf_map_grid_lowp_kernel<LAYOUT, BF16, 8>), dim3((unsigned)blocks), dim3(kSlabWG), 0, s, a);
+  else
+    hipLaunchKernelGGL((tsdf_map_grid_lowp_kernel<LAYOUT, BF16, 4>), dim3((unsigned)blocks), dim3(kSlabWG), 0, s, a);
+}
+
+}  // namespace
+
+extern "C" {
+
+int tsdf_maplowp_version(void) { return TSDF_MAPLOWP_VERSION; }
+
+int tsdf_map_place_hip(const float *d_depth, int64_t depth_len, const int64_t *d_offsets, const int32_t *d_headers,
+                       int64_t n_src, const int64_t *d_index, int n, int R, const tsdf_cam *cam, void *hip_stream,
+                       const double *d_xforms, float *d_out_grid, float *d_out_max_l, float *d_out_mid_p,
+                       int32_t *d_out_status) {
+  // arguments first, then the device, then the launch
+  if (n < 0) return TSDF_ERR_INVALID_ARG;
+  if (slab_bad_shape(R, TSDF_LAYOUT_CZYX)) return TSDF_ERR_INVALID_ARG;
+  if (n == 0) return TSDF_OK;
+  if (!d_depth || !d_offsets || !d_headers || !d_xforms || !d_out_grid || depth_len < 0) return TSDF_ERR_INVALID_ARG;
+  if (n_src < 1 || (!d_index && n_src != n)) return TSDF_ERR_INVALID_ARG;
+  if (misaligned(d_xforms, 7)) return TSDF_ERR_INVALID_ARG;
+  const int rc = check_device(nullptr);
+  if (rc != TSDF_OK) return rc;
+  if (!cam) cam = &kDefaultCam;
+  PlaceArgs a;
+  a.depth = d_depth;
+  a.depth_len = depth_len;
+  a.offsets = d_offsets;
+  a.headers = d_headers;
+  a.n_src = n_src;
+  a.index = d_index;
+  a.n = n;
+  a.R = R;
+  a.focal = cam->focal;
+  a.cx = cam->cx;
+  a.cy = cam->cy;
+  a.eps = cam->invalid_eps;
+  a.trunc_vox = cam->trunc_voxels;
+  a.xforms = d_xforms;
+  a.grid = d_out_grid;
+  a.max_l = d_out_max_l;
+  a.mid_p = d_out_mid_p;
+  a.status = d_out_status;
+  const int blocks = n < kPlaceMaxBlocks ? n : kPlaceMaxBlocks;
+  hipLaunchKernelGGL(tsdf_map_place_kernel, dim3((unsigned)blocks), dim3(kPlaceWG), 0, static_cast<hipStream_t>(hip_stream),
+                     a);
+  return launched();
+}
+
+int tsdf_voxelize_map_grid_lowp_hip(const float *d_depth, int64_t depth_len, const int64_t *d_offsets,
+                                    const int32_t *d_headers, int64_t n_src, const int64_t *d_index, int n, int R,
+                                    const tsdf_cam *cam, int layout, int dtype, void *hip_stream, const double *d_xforms,
+                                    const float *d_grid, void *d_out_tsdf, int32_t *d_out_status) {
+  // arguments first, then the device, then the launch
+  if (n < 0) return TSDF_ERR_INVALID_ARG;
+  if (slab_bad_shape(R, layout)) return TSDF_ERR_INVALID_ARG;
+  if (bad_dtype(dtype)) return TSDF_ERR_INVALID_ARG;
+  if (n == 0) return TSDF_OK;
+  if (!d_depth || !d_offsets || !d_headers || !d_xforms || !d_grid || !d_out_tsdf || depth_len < 0)
+    return TSDF_ERR_INVALID_ARG;
+  if (n_src < 1 || (!d_index && n_src != n)) return TSDF_ERR_INVALID_ARG;
+  if (misaligned(d_xforms, 7) || misaligned(d_out_tsdf, 15)) return TSDF_ERR_INVALID_ARG;
+  SlabPlan plan;
+  if (!slab_plan(n, R, R % 8 == 0 ? 8 : 4, plan)) return TSDF_ERR_INVALID_ARG;   // a launch holds fewer than 2^32 work-items
+  const int rc = check_device(nullptr);
+  if (rc != TSDF_OK) return rc;
+  if (!cam) cam = &kDefaultCam;
+  MapLowpArgs a;
+  a.depth = d_depth;
+  a.depth_len = depth_len;
+  a.offsets = d_offsets;
+  a.headers = d_headers;
+  a.n_src = n_src;
+  a.index = d_index;
+  a.n = n;
+  a.R = R;
+  a.slab = plan.slab;
+  a.nslab = plan.nslab;
+  a.focal = cam->focal;
+  a.cx = cam->cx;
+  a.cy = cam->cy;
+  a.eps = cam->invalid_eps;
+  a.xforms = d_xforms;
+  a.grid = d_grid;
+  a.out = static_cast<uint16_t *>(d_out_tsdf);
+  a.status = d_out_status;
+  hipStream_t s = static_cast<hipStream_t>(hip_stream);
+  const bool bf = dtype == TSDF_LOWP_BF16;
+  if (layout == TSDF_LAYOUT_CZYX) {
+    if (bf) launch_grid<0, true>(a, plan.blocks, s);
+    else launch_grid<0, false>(a, plan.blocks, s);
+  } else {
+    if (bf) launch_grid<1, true>(a, plan.blocks, s);
+    else launch_grid<1, false>(a, plan.blocks, s);
+  }
+  return launched();
+}
+
+}  // extern "C"

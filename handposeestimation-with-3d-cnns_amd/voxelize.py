@@ -643,13 +643,23 @@ class AugmentedStep:
 
     The graph is the linear sequence of the two kernels on one stream: no branches, no copies inside, and the voxelizer
     takes the queue form it always takes under stream capture.  The draw kernel reads the state from device memory, which
-    is what lets a replay draw anew.  ``graph=False`` issues the same two calls eagerly on the same buffers."""
+    is what lets a replay draw anew.  ``graph=False`` issues the same two calls eagerly on the same buffers.
+
+    ``dtype`` (torch.float16 / torch.bfloat16): the volume is written in that type.  The step is then
+    :func:`aug_xforms_at`, :func:`map_grids`, :func:`voxelize_map_grid_lowp` and, with labels (``gt`` on the GPU), a gather of
+    the batch's joints, :func:`transform_joints` and :func:`normalize_joints` — still one linear graph on one stream over
+    static buffers, nothing allocated or copied inside; ``max_l`` / ``mid_p`` / ``status`` and the labels are those of the
+    float32 step bit for bit."""
 
     def __init__(self, depth: torch.Tensor, offsets: torch.Tensor, headers: torch.Tensor, n: int,
                  gt: Optional[torch.Tensor] = None, centres: Optional[torch.Tensor] = None, res: int = 32,
-                 layout: str = "czyx", clamp: bool = True, cam: Optional[_lib.TsdfCam] = None, graph: bool = True):
+                 layout: str = "czyx", clamp: bool = True, cam: Optional[_lib.TsdfCam] = None, graph: bool = True,
+                 dtype: Optional[torch.dtype] = None):
         if graph not in (False, True):
             raise ValueError(f"graph must be False or True, got {graph!r}")
+        if dtype is not None:
+            _lowp_dtype(dtype)
+        self.dtype = dtype
         n = int(n)
         if n < 1:
             raise ValueError("n must be >= 1")
@@ -667,12 +677,19 @@ class AugmentedStep:
         self._turn = 0
         self.xforms = torch.empty((n, 24), dtype=torch.float64, device=dev)
         self.out = empty_batch(n, R, dev)
+        if dtype is not None:   # the 2-byte volume, and the grid rows the placement hands to the voxel pass
+            self.out = self.out._replace(tsdf=torch.empty((n, 3, R, R, R), dtype=dtype, device=dev))
+            self._grid = MapGridBatch(torch.empty((n, 8), dtype=torch.float32, device=dev), *self.out[1:])
         self.gt_nor = self.gt_aug = None
         if gt is not None:
-            _dev_check("gt", gt, torch.float32, dev, host_ok=True)
+            _dev_check("gt", gt, torch.float32, dev, host_ok=dtype is None)
+            if dtype is not None and gt.shape[0] != n_pack:
+                raise ValueError("gt must hold the labels of every frame of the pack: [N, 3*J] or [N, J, 3]")
             shape = (n,) + tuple(gt.shape[1:])
             self.gt_nor = torch.empty(shape, dtype=torch.float32, device=dev)
             self.gt_aug = torch.empty(shape, dtype=torch.float32, device=dev)
+            if dtype is not None:   # the batch's frame numbers kept inside the pack, and its joints before the map
+                self._sel = (torch.empty(n, dtype=torch.int64, device=dev), torch.empty(shape, dtype=torch.float32, device=dev))
         self.graph = None
         self._run()                      # eagerly once: argument checks, library loads and the device check happen here
         if graph:
@@ -686,8 +703,16 @@ class AugmentedStep:
     def _run(self):
         aug_xforms_at(self.centres, self.state, index=self.index, out=self.xforms)
         d, o, h = self._pack_args
-        voxelize_indexed(d, o, h, self.index, self._gt, res=self.res, layout=self.layout, cam=self.cam, clamp=self.clamp,
-                         out=self.out, xforms=self.xforms, out_gt_nor=self.gt_nor, out_gt=self.gt_aug)
+        if self.dtype is None:
+            voxelize_indexed(d, o, h, self.index, self._gt, res=self.res, layout=self.layout, cam=self.cam, clamp=self.clamp,
+                             out=self.out, xforms=self.xforms, out_gt_nor=self.gt_nor, out_gt=self.gt_aug)
+            return
+        map_grids(d, o, h, self.xforms, res=self.res, cam=self.cam, index=self.index, out=self._grid)
+        _map_grid_lowp(d, o, h, self.xforms, self._grid.grid, self.res, self.layout, self.dtype, self.cam, self.index,
+                       self.out.tsdf, False)
+        if self._gt is not None:
+            _batch_labels(self._gt, self.index, h.shape[0], self.xforms, self.out.max_l, self.out.mid_p, self.clamp,
+                          sel=self._sel, out_aug=self.gt_aug, out_nor=self.gt_nor)
 
     def step(self, index, key: int, counter0: int = 0):
         """Voxelize pack frames ``index`` (n frame numbers: an int64 tensor on the device or the host, or any sequence of
@@ -861,11 +886,11 @@ def voxelize_aug_grid(depth: torch.Tensor, offsets: torch.Tensor, headers: torch
     return tsdf, st
 
 
-def transform_joints(gt: torch.Tensor, xforms: torch.Tensor) -> torch.Tensor:
+def transform_joints(gt: torch.Tensor, xforms: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """The joints under each frame's forward map, on their own (``tsdf_transform_joints_hip`` of libtsdf_auggrid.so):
     ``fma(A_i0, x, fma(A_i1, y, fma(A_i2, z, b_i)))`` in float64, rounded to float32 — bit-identical to the ``gt_aug``
     :func:`voxelize_aug` ``(..., gt=)`` returns.  gt float32[n,3J] or [n,J,3] on the GPU, xforms float64[n,24]; the result
-    has gt's shape."""
+    has gt's shape (``out``: a preallocated tensor of that shape to write into)."""
     G = _lib.load_auggrid()
     _dev_check("gt", gt, torch.float32)
     if gt.dim() < 2:
@@ -873,7 +898,7 @@ def transform_joints(gt: torch.Tensor, xforms: torch.Tensor) -> torch.Tensor:
     dev, n = gt.device, gt.shape[0]
     nc = _coords("gt", gt, n)
     _shaped("xforms", xforms, (n, 24), torch.float64, dev)
-    out = _out("gt_aug", None, tuple(gt.shape), torch.float32, dev)
+    out = _out("gt_aug", out, tuple(gt.shape), torch.float32, dev)
     if n:
         _call(dev, G.tsdf_transform_joints_hip, [gt.data_ptr(), xforms.data_ptr(), n, nc // 3, None, out.data_ptr()], 4)
     return out
@@ -881,7 +906,7 @@ def transform_joints(gt: torch.Tensor, xforms: torch.Tensor) -> torch.Tensor:
 
 class ProcessAugBatch(NamedTuple):
     points: torch.Tensor       # float64[n, P, 3]  the resampled clouds
-    tsdf: torch.Tensor         # float32[n, 3, R, R, R]
+    tsdf: torch.Tensor         # float32[n, 3, R, R, R] (float16 / bfloat16 with process_batch_aug(dtype=...), and tsdf_aug)
     max_l: torch.Tensor        # float32[n]
     mid_p: torch.Tensor        # float32[n, 3]
     points_aug: torch.Tensor   # float64[n, P, 3]  the mapped clouds, resampled with their own draw
@@ -898,7 +923,8 @@ class ProcessAugBatch(NamedTuple):
 def process_batch_aug(depth: torch.Tensor, offsets: torch.Tensor, headers: torch.Tensor,
                       xforms: Optional[torch.Tensor] = None, gt: Optional[torch.Tensor] = None, points: int = 6000,
                       seed: int = 0, aug_seed: int = 0, key: int = 0, frame_base: int = 0, res: int = 32,
-                      layout: str = "czyx", cam: Optional[_lib.TsdfCam] = None) -> ProcessAugBatch:
+                      layout: str = "czyx", cam: Optional[_lib.TsdfCam] = None,
+                      dtype: Optional[torch.dtype] = None) -> ProcessAugBatch:
     """``DataProcess(aug=True).process()`` (pre/process.py:13-28) for n packed frames: the nine entries of the reference's
     dictionary plus the bookkeeping, every stage on the current stream, no synchronisation, nothing on the host.
 
@@ -911,14 +937,23 @@ def process_batch_aug(depth: torch.Tensor, offsets: torch.Tensor, headers: torch
       4. ``tsdf_aug = voxelize_aug_grid(..., xforms, grid)``;
       5. ``gt_aug = transform_joints(gt, xforms)`` when ``gt`` (float32[n,3J] or [n,J,3]) is given.
     ``status_aug`` is the first non-zero status among the augmented cloud, grid and volume stages.  A batch split over
-    several calls with ``frame_base`` gives the same result as one call."""
+    several calls with ``frame_base`` gives the same result as one call.
+
+    ``dtype`` (torch.float16 / torch.bfloat16): ``tsdf`` comes from :func:`process_batch` ``(dtype=)`` and ``tsdf_aug`` from
+    :func:`voxelize_map_grid_lowp` on the same rows, both of that type; every other field is unchanged bit for bit."""
+    if dtype is not None:
+        _lowp_dtype(dtype)
     pb = process_batch(depth, offsets, headers, points=points, seed=seed, frame_base=frame_base, res=res, layout=layout,
-                       cam=cam)
+                       cam=cam, dtype=dtype)
     if xforms is None:
         xforms = aug_xforms(pb.mid_p, key=key, counter0=frame_base)
     pa = point_clouds(depth, offsets, headers, points=points, seed=aug_seed, frame_base=frame_base, xforms=xforms, cam=cam)
     cg = cloud_grids(pa.points, res=res, cam=cam)
-    tsdf_aug, st = voxelize_aug_grid(depth, offsets, headers, xforms, cg.grid, res=res, layout=layout, cam=cam)
+    if dtype is None:
+        tsdf_aug, st = voxelize_aug_grid(depth, offsets, headers, xforms, cg.grid, res=res, layout=layout, cam=cam)
+    else:
+        tsdf_aug, st = voxelize_map_grid_lowp(depth, offsets, headers, xforms, cg.grid, res=res, layout=layout, dtype=dtype,
+                                              cam=cam)
     status_aug = torch.where(pa.status != 0, pa.status, torch.where(cg.status != 0, cg.status, st))
     gt_aug = transform_joints(gt, xforms) if gt is not None else None
     return ProcessAugBatch(pb.points, pb.tsdf, pb.max_l, pb.mid_p, pa.points, tsdf_aug, cg.max_l, cg.mid_p, gt_aug,
@@ -975,14 +1010,23 @@ def obb_xforms(depth: torch.Tensor, offsets: torch.Tensor, headers: torch.Tensor
 
 
 def voxelize_obb(depth: torch.Tensor, offsets: torch.Tensor, headers: torch.Tensor, res: int = 32, layout: str = "czyx",
-                 cam: Optional[_lib.TsdfCam] = None, gt: Optional[torch.Tensor] = None, clamp: bool = True):
+                 cam: Optional[_lib.TsdfCam] = None, gt: Optional[torch.Tensor] = None, clamp: bool = True,
+                 dtype: Optional[torch.dtype] = None):
     """Volumes cut in every cloud's own principal axes: :func:`obb_xforms` followed by :func:`voxelize_aug` on the same
     stream, nothing on the host in between.  Returns ``(TsdfBatch, xforms)``, or with ``gt`` (float32[n,3J] on the GPU)
     ``(TsdfBatch, gt_nor, gt_obb, xforms)``: ``gt_obb`` are the joints in the mapped frame, ``gt_nor`` their labels;
     ``max_l`` / ``mid_p`` are in the mapped frame, as for :func:`voxelize_aug`.  Predictions go back to the camera frame
-    with ``transform_joints(pred, invert_xforms(xforms))``."""
+    with ``transform_joints(pred, invert_xforms(xforms))``.
+
+    ``dtype`` (torch.float16 / torch.bfloat16): :func:`voxelize_aug_lowp` takes :func:`voxelize_aug`'s place and ``tsdf``
+    has that type; everything else is unchanged bit for bit."""
+    if dtype is not None:
+        _lowp_dtype(dtype)
     xf = obb_xforms(depth, offsets, headers, cam=cam).xforms
-    r = voxelize_aug(depth, offsets, headers, xf, res=res, layout=layout, cam=cam, gt=gt, clamp=clamp)
+    if dtype is None:
+        r = voxelize_aug(depth, offsets, headers, xf, res=res, layout=layout, cam=cam, gt=gt, clamp=clamp)
+    else:
+        r = voxelize_aug_lowp(depth, offsets, headers, xf, res=res, layout=layout, dtype=dtype, cam=cam, gt=gt, clamp=clamp)
     return (r, xf) if gt is None else (r[0], r[1], r[2], xf)
 
 
@@ -1073,3 +1117,131 @@ def narrow_volumes(tsdf32: torch.Tensor, dtype: torch.dtype = torch.bfloat16,
     if tsdf32.numel():
         _call(dev, P.tsdf_lowp_narrow_hip, [tsdf32.data_ptr(), tsdf32.numel(), code, None, out.data_ptr()], 3)
     return out
+
+
+class MapGridBatch(NamedTuple):
+    grid: torch.Tensor    # float32[n, 8]  vox_ori[3], voxel_len, trunc_dis, 0, 0, 0 (the ``grid`` of the voxel passes)
+    max_l: torch.Tensor   # float32[n]     in the mapped frame
+    mid_p: torch.Tensor   # float32[n, 3]
+    status: torch.Tensor  # int32[n]  (_lib.TSDF_FRAME_*)
+
+
+def _mapped(depth, offsets, headers, xforms, res, layout, index):
+    """The one validation of the entries of libtsdf_maplowp.so: the source tables, the optional index and one map per
+    batch position.  Returns (device, n_src, n, R)."""
+    dev, n_src, R = _pack(_lib.load(), depth, offsets, headers, res, layout)
+    n = n_src
+    if index is not None:
+        _dev_check("index", index, torch.int64, dev)
+        if index.dim() != 1:
+            raise ValueError("index must have shape [n]")
+        n = int(index.shape[0])
+        if n and not n_src:
+            raise ValueError("index needs at least one source frame")
+    _shaped("xforms", xforms, (n, 24), torch.float64, dev)
+    return dev, n_src, n, R
+
+
+def map_grids(depth: torch.Tensor, offsets: torch.Tensor, headers: torch.Tensor, xforms: torch.Tensor, res: int = 32,
+              cam: Optional[_lib.TsdfCam] = None, index: Optional[torch.Tensor] = None,
+              out: Optional[MapGridBatch] = None) -> MapGridBatch:
+    """The grid placement of :func:`voxelize_aug` on its own (``tsdf_map_place_hip`` of libtsdf_maplowp.so;
+    include/tsdf_maplowp.h has the contract): the float32 AABB of every valid pixel's point under the frame's forward map,
+    the float32 glue and the degenerate rule.  ``max_l`` / ``mid_p`` / ``status`` are those of :func:`voxelize_aug`, bit for
+    bit; ``grid`` goes straight to :func:`voxelize_map_grid_lowp` or :func:`voxelize_aug_grid`.
+
+    depth / offsets / headers   the n_src source frames, as for :func:`voxelize`
+    xforms  float64[n,24] on the GPU: one map per BATCH POSITION, forward rows then inverse rows
+    index   optional int64[n] on the GPU: batch position i places source frame index[i] (repeats allowed; an entry
+            outside [0, n_src) gives that position status 2).  Without it the batch is the n_src frames
+    out     optional preallocated :class:`MapGridBatch` to write into
+    A position that is not OK gets an all-zero grid row and ``max_l`` 0.  One launch on the current stream, no
+    synchronisation."""
+    M = _lib.load_maplowp()
+    dev, n_src, n, R = _mapped(depth, offsets, headers, xforms, res, "czyx", index)
+    fields = (("grid", (n, 8), torch.float32), ("max_l", (n,), torch.float32), ("mid_p", (n, 3), torch.float32),
+              ("status", (n,), torch.int32))
+    if out is None:
+        out = MapGridBatch(*[_out(name, None, shape, dtype, dev) for name, shape, dtype in fields])
+    else:
+        for name, shape, dtype in fields:
+            _shaped("out." + name, getattr(out, name), shape, dtype, dev)
+    if n:
+        _call(dev, M.tsdf_map_place_hip,
+              [depth.data_ptr(), depth.numel(), offsets.data_ptr(), headers.data_ptr(), n_src, _ptr(index), n, R, _cam(cam),
+               None, xforms.data_ptr(), out.grid.data_ptr(), out.max_l.data_ptr(), out.mid_p.data_ptr(),
+               out.status.data_ptr()], 9)
+    return out
+
+
+def _map_grid_lowp(depth, offsets, headers, xforms, grid, res, layout, dtype, cam, index, out, want_status):
+    """:func:`voxelize_map_grid_lowp`; without ``want_status`` the launch writes no status and, given ``out``, the call
+    allocates nothing.  Returns (volume, status or None)."""
+    code = _lowp_dtype(dtype)
+    M = _lib.load_maplowp()
+    dev, n_src, n, R = _mapped(depth, offsets, headers, xforms, res, layout, index)
+    _shaped("grid", grid, (n, 8), torch.float32, dev)
+    tsdf = _out("out", out, (n, 3, R, R, R), dtype, dev)
+    status = _out("status", None, (n,), torch.int32, dev) if want_status else None
+    if n:
+        _call(dev, M.tsdf_voxelize_map_grid_lowp_hip,
+              [depth.data_ptr(), depth.numel(), offsets.data_ptr(), headers.data_ptr(), n_src, _ptr(index), n, R, _cam(cam),
+               _lib.LAYOUTS[layout], code, None, xforms.data_ptr(), grid.data_ptr(), tsdf.data_ptr(), _ptr(status)], 11)
+    return tsdf, status
+
+
+def voxelize_map_grid_lowp(depth: torch.Tensor, offsets: torch.Tensor, headers: torch.Tensor, xforms: torch.Tensor,
+                           grid: torch.Tensor, res: int = 32, layout: str = "czyx", dtype: torch.dtype = torch.bfloat16,
+                           cam: Optional[_lib.TsdfCam] = None, index: Optional[torch.Tensor] = None,
+                           out: Optional[torch.Tensor] = None):
+    """:func:`voxelize_aug_grid` written as float16 / bfloat16 voxels (``tsdf_voxelize_map_grid_lowp_hip`` of
+    libtsdf_maplowp.so; include/tsdf_maplowp.h has the contract): every voxel is the float32 value of the augmented pass
+    narrowed by round-to-nearest-even in registers, so the volume is written once, at half the bytes.
+
+    depth / offsets / headers   the n_src source frames, as for :func:`voxelize`
+    xforms  float64[n,24] on the GPU  }  per BATCH POSITION: position i voxelizes its source frame under map i on row i
+    grid    float32[n,8] on the GPU   }  (vox_ori[3], voxel_len, trunc_dis, 3 pad words: what :func:`map_grids` returns)
+    dtype   torch.float16 or torch.bfloat16
+    index   optional int64[n] on the GPU: batch position i voxelizes source frame index[i] (repeats allowed; an entry
+            outside [0, n_src) gives that position status 2 and a zero volume).  Without it the batch is the n_src frames
+    out     optional preallocated ``dtype[n,3,R,R,R]`` (a contiguous view of a larger buffer will do) to write into
+    Returns ``(tsdf dtype[n,3,R,R,R], status int32[n])``.  A bad header (2) or an unusable grid row (1) gives a zero volume;
+    the crop is not scanned, so a frame without a valid pixel on a usable row gets a zero volume with status 0.  One launch
+    on the current stream, no synchronisation."""
+    return _map_grid_lowp(depth, offsets, headers, xforms, grid, res, layout, dtype, cam, index, out, True)
+
+
+def _batch_labels(gt, index, n_src, xforms, max_l, mid_p, clamp, sel=None, out_aug=None, out_nor=None):
+    """The labels of a batch under its maps: the batch's joints (``index``: gathered from the n_src source frames, an
+    entry outside them reads the nearest frame and its position is not OK anyway), :func:`transform_joints`, then
+    :func:`normalize_joints` in the mapped grid.  Returns (gt_nor, gt_aug)."""
+    if index is not None:
+        safe = index.clamp(0, n_src - 1) if sel is None else torch.clamp(index, 0, n_src - 1, out=sel[0])
+        gt = gt.index_select(0, safe) if sel is None else torch.index_select(gt, 0, safe, out=sel[1])
+    gt_aug = transform_joints(gt, xforms, out=out_aug)
+    return normalize_joints(gt_aug, max_l, mid_p, clamp=clamp, out=out_nor), gt_aug
+
+
+def voxelize_aug_lowp(depth: torch.Tensor, offsets: torch.Tensor, headers: torch.Tensor, xforms: torch.Tensor,
+                      res: int = 32, layout: str = "czyx", dtype: torch.dtype = torch.bfloat16,
+                      cam: Optional[_lib.TsdfCam] = None, gt: Optional[torch.Tensor] = None, clamp: bool = True,
+                      index: Optional[torch.Tensor] = None):
+    """:func:`voxelize_aug` with a float16 / bfloat16 volume: :func:`map_grids` places the grid under the maps and
+    :func:`voxelize_map_grid_lowp` writes the volume on its rows, on one stream with nothing on the host in between.  It
+    is TWO launches and the crop is read twice (the fused float32 entry reads it once).  ``max_l`` / ``mid_p`` / ``status``
+    are the placement's, bit for bit those of :func:`voxelize_aug`; ``tsdf`` is ``dtype[n,3,R,R,R]``.
+
+    xforms  float64[n,24] on the GPU, one map per batch position; ``index`` (int64[n] on the GPU) draws the batch from the
+            source frames as for :func:`voxelize_map_grid_lowp`
+    gt      optional float32[n_src,3J] (or [n_src,J,3]) on the GPU: returns ``(TsdfBatch, gt_nor, gt_aug)`` with
+            ``gt_aug = transform_joints(gt of the batch, xforms)`` and ``gt_nor = normalize_joints(gt_aug, max_l, mid_p)``
+            (two more small launches), the values the fused entry writes."""
+    _lowp_dtype(dtype)
+    mg = map_grids(depth, offsets, headers, xforms, res=res, cam=cam, index=index)
+    tsdf, _ = _map_grid_lowp(depth, offsets, headers, xforms, mg.grid, res, layout, dtype, cam, index, None, False)
+    batch = TsdfBatch(tsdf, mg.max_l, mg.mid_p, mg.status)
+    if gt is None:
+        return batch
+    _dev_check("gt", gt, torch.float32, depth.device)
+    gt_nor, gt_aug = _batch_labels(gt, index, headers.shape[0], xforms, mg.max_l, mg.mid_p, clamp)
+    return batch, gt_nor, gt_aug

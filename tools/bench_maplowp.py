@@ -1,0 +1,96 @@
+#!/usr/bin/env python3
+"""What a float16 / bfloat16 volume costs UNDER A PER-FRAME MAP (one JSON line; ``--out`` also writes it to a file,
+default profiles/maplowp/bench_maplowp.json).
+
+Legs, per shape, on the same frames and the same maps (``aug_xforms`` about the plain grid centres) in the same run:
+  aug_f32          voxelize_aug()                        the fused float32 kernel (tsdf_voxelize_aug_hip)
+  aug_f32_cast     voxelize_aug() + .to(dtype)           what a user does today: THE YARDSTICK
+  aug_lowp         voxelize_aug_lowp()                   map_grids + voxelize_map_grid_lowp, libtsdf_maplowp.so
+  place            map_grids() alone                     tsdf_map_place_hip
+  aabb             aabb() alone                          the plain placement (tsdf_aabb_hip), next to `place`
+  grid_lowp        voxelize_map_grid_lowp() alone        tsdf_voxelize_map_grid_lowp_hip on the rows of `place`
+  grid_f32_cast    voxelize_aug_grid() + .to(dtype)      the float32 pass on the same rows, next to `grid_lowp`
+at 1024 crops R = 32, 16 crops R = 32 and 256 crops R = 64, bfloat16 (``--dtype float16`` for the other type).
+
+Method: inputs resident on the device, --warmup launches, then device events around --iters back-to-back launches (at
+least 50); the legs of a shape take turns for --rounds rounds and the median round is reported with min and max, so a
+drift of the machine meets all alike.  The float32 legs and the composite allocate their outputs (torch's caching
+allocator: no device allocation in the steady state), grid_lowp writes into one buffer.  Bytes written per launch: 12 R^3 n
+for a float32 volume, 6 R^3 n for a low-precision one.
+
+    python tools/bench_maplowp.py [--iters 100] [--warmup 20] [--rounds 5] [--dtype bfloat16] [--out x.json]
+"""
+from __future__ import annotations
+
+import argparse
+import importlib
+import json
+import os
+import sys
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+pkg = importlib.import_module("handposeestimation-with-3d-cnns_amd")
+synth = importlib.import_module("handposeestimation-with-3d-cnns_amd.synth")
+from _timing import take_turns  # noqa: E402  (tools/_timing.py, beside this file)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--iters", type=int, default=100)
+    ap.add_argument("--warmup", type=int, default=20)
+    ap.add_argument("--rounds", type=int, default=5)
+    ap.add_argument("--dtype", choices=("bfloat16", "float16"), default="bfloat16")
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "maplowp", "bench_maplowp.json"))
+    a = ap.parse_args()
+    assert a.iters >= 50, "time at least 50 launches"
+    assert torch.cuda.is_available(), "bench_maplowp.py needs a HIP device"
+    dev = torch.device("cuda:0")
+    dt = getattr(torch, a.dtype)
+    rows = []
+    for n, R in ((1024, 32), (16, 32), (256, 64)):
+        depth, off, hdr = synth.synth_batch(n, "crop", seed0=0, threads=8)
+        td, to, th = (torch.from_numpy(np.ascontiguousarray(x)).to(dev) for x in (depth, off, hdr))
+        ab = pkg.aabb(td, to, th, res=R)
+        assert not ab.status.any()
+        xf = pkg.aug_xforms(ab.grid[:, :3].contiguous(), key=0x5EED, counter0=0)
+        mg = pkg.map_grids(td, to, th, xf, res=R)
+        assert not mg.status.any()
+        vol32 = pkg.voxelize_aug(td, to, th, xf, res=R).tsdf
+        low = torch.empty(vol32.shape, dtype=dt, device=dev)
+        legs = {"aug_f32": lambda: pkg.voxelize_aug(td, to, th, xf, res=R),
+                "aug_f32_cast": lambda: pkg.voxelize_aug(td, to, th, xf, res=R).tsdf.to(dt),
+                "aug_lowp": lambda: pkg.voxelize_aug_lowp(td, to, th, xf, res=R, dtype=dt),
+                "place": lambda: pkg.map_grids(td, to, th, xf, res=R),
+                "aabb": lambda: pkg.aabb(td, to, th, res=R),
+                "grid_lowp": lambda: pkg.voxelize_map_grid_lowp(td, to, th, xf, mg.grid, res=R, dtype=dt, out=low),
+                "grid_f32_cast": lambda: pkg.voxelize_aug_grid(td, to, th, xf, mg.grid, res=R)[0].to(dt)}
+        t = take_turns(legs, a.iters, a.warmup, a.rounds)
+        differ = int((pkg.voxelize_aug_lowp(td, to, th, xf, res=R, dtype=dt).tsdf.view(torch.int16)
+                      != vol32.to(dt).view(torch.int16)).sum())
+        low_bytes = 2 * vol32.numel()
+        row = dict(n=n, kind="crop", res=R, dtype=a.dtype, pixels=int(depth.size), volume_bytes_f32=2 * low_bytes,
+                   volume_bytes_lowp=low_bytes, voxels_differing_from_fused_cast=differ, **t,
+                   lowp_over_f32_cast=round(t["aug_lowp"]["us"] / t["aug_f32_cast"]["us"], 3),
+                   lowp_over_f32=round(t["aug_lowp"]["us"] / t["aug_f32"]["us"], 3),
+                   place_over_aabb=round(t["place"]["us"] / t["aabb"]["us"], 3),
+                   grid_lowp_over_grid_f32_cast=round(t["grid_lowp"]["us"] / t["grid_f32_cast"]["us"], 3),
+                   grid_lowp_write_GBps=round(low_bytes / t["grid_lowp"]["us"] / 1e3, 1),
+                   place_read_GBps=round(4 * depth.size / t["place"]["us"] / 1e3, 1))
+        rows.append(row)
+        print(json.dumps(row), file=sys.stderr)
+        del td, to, th, ab, xf, mg, vol32, low, legs
+        torch.cuda.empty_cache()
+    line = json.dumps(dict(device=torch.cuda.get_device_name(0), iters=a.iters, rounds=a.rounds, rows=rows))
+    print(line)
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as f:
+            f.write(line + "\n")
+
+
+if __name__ == "__main__":
+    main()
