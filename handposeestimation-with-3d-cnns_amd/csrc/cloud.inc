@@ -268,6 +268,7 @@ int run_point_clouds(const float *d_depth, int64_t depth_len, const int64_t *d_o
   if (misaligned(d_xforms, 7)) return TSDF_ERR_INVALID_ARG;
   if (n == 0) return TSDF_OK;
   if (!d_depth || !d_offsets || !d_headers || depth_len < 0) return TSDF_ERR_INVALID_ARG;
+  if (!cam_ok(cam)) return TSDF_ERR_INVALID_ARG;   // the whole camera, though only focal is read
   const int rc = check_device(nullptr);
   if (rc != TSDF_OK) return rc;
   // split a frame's slots over workgroups until the launch has about two workgroups per CU

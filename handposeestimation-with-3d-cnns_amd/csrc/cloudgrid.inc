@@ -153,6 +153,7 @@ int run_cloud_grid(const double *d_points, int n, int points, int R, const tsdf_
   if (n == 0) return TSDF_OK;
   if (!d_points || !d_out_grid || !d_out_max_l || !d_out_mid_p) return TSDF_ERR_INVALID_ARG;
   if (misaligned(d_points, 7)) return TSDF_ERR_INVALID_ARG;
+  if (!cam_ok(cam)) return TSDF_ERR_INVALID_ARG;   // the whole camera, though only trunc_voxels is read
   const int rc = check_device(nullptr);
   if (rc != TSDF_OK) return rc;
   CloudGridArgs a;

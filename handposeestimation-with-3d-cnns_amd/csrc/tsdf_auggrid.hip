@@ -208,6 +208,7 @@ int tsdf_voxelize_aug_grid_hip(const float *d_depth, int64_t depth_len, const in
   if (!d_depth || !d_offsets || !d_headers || !d_xforms || !d_grid || !d_out_tsdf || depth_len < 0) return TSDF_ERR_INVALID_ARG;
   if (slab_bad_shape(R, layout)) return TSDF_ERR_INVALID_ARG;
   if (misaligned(d_xforms, 7) || misaligned(d_out_tsdf, 15)) return TSDF_ERR_INVALID_ARG;
+  if (!cam_ok(cam)) return TSDF_ERR_INVALID_ARG;
   SlabPlan plan;
   if (!slab_plan(n, R, 4, plan)) return TSDF_ERR_INVALID_ARG;   // a launch holds fewer than 2^32 work-items
   const int rc = check_device(nullptr);

@@ -27,6 +27,11 @@
 
 namespace tsdf_host {
 
+// the camera rule (cam_ok) as every library here applies it; the device primitives of prim.inc stay out of this file
+#define TSDF_PRIM_HOST_ONLY
+#include "prim.inc"
+#undef TSDF_PRIM_HOST_ONLY
+
 // ---- frames index[0..n) of a packed host buffer copied back to back into dst ------------------------------------
 // dst_offsets[n+1] is filled in; `threads` workers split the bytes evenly.  src_len < 0: unknown (the v4 entry).
 // Everything is validated before the first byte is copied: an index outside the pack, offsets that run backwards or
@@ -159,8 +164,7 @@ inline int check_run_args(const Frames &f, const Outs &out, const RunOpts &o, in
   if ((o.needs & kNeedPixmap) && !o.pixmap) return TSDF_ERR_INVALID_ARG;
   if (!f.depth || !f.offsets || !f.headers || f.depth_len < 0) return TSDF_ERR_INVALID_ARG;
   if (!o.aabb_only && (!out.tsdf || (reinterpret_cast<uintptr_t>(out.tsdf) & 15))) return TSDF_ERR_INVALID_ARG;
-  if (f.cam && (!(f.cam->focal > 0.0) || !(f.cam->invalid_eps > 0.0f) || !(f.cam->trunc_voxels > 0.0f)))
-    return TSDF_ERR_INVALID_ARG;  // (written so that NaN fails)
+  if (!cam_ok(f.cam)) return TSDF_ERR_INVALID_ARG;
   return TSDF_OK;
 }
 

@@ -252,6 +252,7 @@ int tsdf_voxelize_grid_lowp_hip(const float *d_depth, int64_t depth_len, const i
   if (!d_depth || !d_offsets || !d_headers || !d_grid || !d_out_tsdf || depth_len < 0) return TSDF_ERR_INVALID_ARG;
   if (n_src < 1 || (!d_index && n_src != n)) return TSDF_ERR_INVALID_ARG;
   if (misaligned(d_out_tsdf, 15)) return TSDF_ERR_INVALID_ARG;
+  if (!cam_ok(cam)) return TSDF_ERR_INVALID_ARG;
   SlabPlan plan;
   if (!slab_plan(n, R, R % 8 == 0 ? 8 : 4, plan)) return TSDF_ERR_INVALID_ARG;   // a launch holds fewer than 2^32 work-items
   const int rc = check_device(nullptr);

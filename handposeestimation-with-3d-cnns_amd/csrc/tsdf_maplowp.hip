@@ -443,6 +443,7 @@ int tsdf_map_place_hip(const float *d_depth, int64_t depth_len, const int64_t *d
   if (!d_depth || !d_offsets || !d_headers || !d_xforms || !d_out_grid || depth_len < 0) return TSDF_ERR_INVALID_ARG;
   if (n_src < 1 || (!d_index && n_src != n)) return TSDF_ERR_INVALID_ARG;
   if (misaligned(d_xforms, 7)) return TSDF_ERR_INVALID_ARG;
+  if (!cam_ok(cam)) return TSDF_ERR_INVALID_ARG;
   const int rc = check_device(nullptr);
   if (rc != TSDF_OK) return rc;
   if (!cam) cam = &kDefaultCam;
@@ -484,6 +485,7 @@ int tsdf_voxelize_map_grid_lowp_hip(const float *d_depth, int64_t depth_len, con
     return TSDF_ERR_INVALID_ARG;
   if (n_src < 1 || (!d_index && n_src != n)) return TSDF_ERR_INVALID_ARG;
   if (misaligned(d_xforms, 7) || misaligned(d_out_tsdf, 15)) return TSDF_ERR_INVALID_ARG;
+  if (!cam_ok(cam)) return TSDF_ERR_INVALID_ARG;
   SlabPlan plan;
   if (!slab_plan(n, R, R % 8 == 0 ? 8 : 4, plan)) return TSDF_ERR_INVALID_ARG;   // a launch holds fewer than 2^32 work-items
   const int rc = check_device(nullptr);

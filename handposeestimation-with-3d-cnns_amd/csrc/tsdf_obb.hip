@@ -356,6 +356,7 @@ int tsdf_obb_xforms_hip(const float *d_depth, int64_t depth_len, const int64_t *
   if (n == 0) return TSDF_OK;
   if (!d_depth || !d_offsets || !d_headers || !d_out_xforms || depth_len < 0) return TSDF_ERR_INVALID_ARG;
   if (misaligned(d_out_xforms, 7) || misaligned(d_out_moments, 7) || misaligned(d_out_status, 3)) return TSDF_ERR_INVALID_ARG;
+  if (!cam_ok(cam)) return TSDF_ERR_INVALID_ARG;
   const int rc = check_device(nullptr);
   if (rc != TSDF_OK) return rc;
   if (!cam) cam = &kDefaultCam;

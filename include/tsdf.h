@@ -133,7 +133,9 @@ int tsdf_resolution_supported(int R);
  *                                   unchanged until the launch has finished.  Everything else is device memory.
  *   n          number of frames (0 is allowed and is a no-op).
  *   R          grid resolution (reference: 32).
- *   cam        constants, or NULL for the MSRA defaults.
+ *   cam        constants, or NULL for the MSRA defaults.  A non-NULL cam whose focal, invalid_eps or trunc_voxels is
+ *              not > 0 (a NaN is not) is TSDF_ERR_INVALID_ARG when n > 0 — in every entry that takes a cam,
+ *              whichever fields that entry reads.
  *   layout     enum tsdf_layout.
  *   hip_stream hipStream_t to enqueue on.
  *   d_out_tsdf   float32[n][3][R][R][R], 16-byte aligned (required); 256-byte alignment recommended: a wave
@@ -416,7 +418,9 @@ int tsdf_pose_error_hip(const float *d_pred, const tsdf_pca *pca, const float *d
  *   2. Point of crop pixel (row r, column c), float64, one rounding per operation, no fma: with W, H, left, top from the
  *      header and F = cam->focal (NULL cam: 241.42),
  *          x = (((c + left) - W/2) * d) / F,   y = -((((r + top) - H/2) * d)) / F,   z = -d
- *      (the header's W/2, H/2 as process.py uses them, not cam->cx / cy; invalid_eps and trunc_voxels are unused).
+ *      (the header's W/2, H/2 as process.py uses them, not cam->cx / cy; invalid_eps and trunc_voxels are unused, but
+ *      a cam is valid or not as a whole: one whose focal, invalid_eps or trunc_voxels is not > 0 is
+ *      TSDF_ERR_INVALID_ARG when n > 0).
  *   3. Resample (the rule of set_length): g = frame_base + i (mod 2^64), mix = splitmix64
  *      (z += 0x9E3779B97F4A7C15; z = (z ^ z>>30) * 0xBF58476D1CE4E5B9; z = (z ^ z>>27) * 0x94D049BB133111EB;
  *      z ^= z>>31, all mod 2^64), u(j) = mix(mix(seed + g) + j), k(j) = ((u >> 32) * m) >> 32 (exact product).
@@ -448,7 +452,9 @@ int tsdf_point_clouds_hip(const float *d_depth, int64_t depth_len, const int64_t
  *      first and reduces in float32; rounding to nearest is monotone, so the values are the same).  Where an extreme is
  *      +-0 its sign is unspecified.
  *   3. Glue, float32, one rounding per operation, in this order (pre/tsdf_for.py:11-16): mid = (max + min) / 2;
- *      max_l = max_i(max_i - min_i); voxel_len = max_l / R; trunc_dis = voxel_len * cam->trunc_voxels (NULL cam: 3);
+ *      max_l = max_i(max_i - min_i); voxel_len = max_l / R; trunc_dis = voxel_len * cam->trunc_voxels (NULL cam: 3;
+ *      a cam whose focal, invalid_eps or trunc_voxels is not > 0 is TSDF_ERR_INVALID_ARG when n > 0, though only
+ *      trunc_voxels is read);
  *      vox_ori = (mid - max_l / 2) + voxel_len / 2.
  *   4. A frame with no point of z != 0, with a NaN among the values that enter an extreme (a NaN z is never dropped), with
  *      a non-finite extent or centre, or with max_l == 0 gets TSDF_FRAME_DEGENERATE: its grid row is all zero,

@@ -42,7 +42,9 @@ int tsdf_auggrid_version(void);
  *   n          number of frames; 0 is a no-op (TSDF_OK), whatever else is passed
  *   R          grid resolution: a multiple of 4 in 4..128
  *   cam        constants, or NULL for the MSRA defaults (focal 241.42, principal point (160, 120), invalid_eps 1),
- *              restated in this library; trunc_voxels is unused (the truncation distance comes with the grid)
+ *              restated in this library; trunc_voxels is unused (the truncation distance comes with the grid).
+ *              A non-NULL cam whose focal, invalid_eps or trunc_voxels is not > 0 (a NaN is not) is
+ *              TSDF_ERR_INVALID_ARG when n > 0, whichever fields the entry reads.
  *   d_xforms   float64[n][24], 8-byte aligned: per frame the forward affine map T(p) = A p + b as three rows
  *              {A_i0, A_i1, A_i2, b_i}, then its inverse in the same form (the d_xforms of tsdf_voxelize_aug_hip)
  *   d_grid     float32[n][8]: vox_ori[3], voxel_len, trunc_dis, then 3 pad words per frame — exactly what

@@ -54,7 +54,9 @@ int tsdf_lowp_version(void);
  *   n          number of batch positions; 0 is a no-op (TSDF_OK)
  *   R          grid resolution: a multiple of 4 in 4..128
  *   cam        constants, or NULL for the MSRA defaults (focal 241.42, principal point (160, 120), invalid_eps 1),
- *              restated in this library; trunc_voxels is unused (the truncation distance comes with the grid)
+ *              restated in this library; trunc_voxels is unused (the truncation distance comes with the grid).
+ *              A non-NULL cam whose focal, invalid_eps or trunc_voxels is not > 0 (a NaN is not) is
+ *              TSDF_ERR_INVALID_ARG when n > 0, whichever fields the entry reads.
  *   layout     enum tsdf_layout
  *   dtype      enum tsdf_lowp_dtype
  *   d_out_tsdf   2-byte elements [n][3][R][R][R] in `layout`, 16-byte aligned.  Every byte of it is written by the

@@ -51,7 +51,9 @@ int tsdf_maplowp_version(void);
  *   n          number of batch positions; 0 is a no-op (TSDF_OK)
  *   R          grid resolution: a multiple of 4 in 4..128
  *   cam        constants, or NULL for the MSRA defaults (focal 241.42, principal point (160, 120), invalid_eps 1,
- *              trunc_voxels 3), restated in this library
+ *              trunc_voxels 3), restated in this library.
+ *              A non-NULL cam whose focal, invalid_eps or trunc_voxels is not > 0 (a NaN is not) is
+ *              TSDF_ERR_INVALID_ARG when n > 0, whichever fields the entry reads.
  *   d_xforms   float64[n][24], 8-byte aligned: ONE MAP PER BATCH POSITION (as for tsdf_voxelize_indexed_aug_hip), the
  *              forward rows {A_i0, A_i1, A_i2, b_i} then the inverse rows; only the forward rows are read
  *   d_out_grid   float32[n][8], required: vox_ori[3], voxel_len, trunc_dis, 0, 0, 0 per batch position — the row

@@ -43,7 +43,9 @@ int tsdf_obb_version(void);
  *              to back, int64[n+1] element offsets, int32[n][6] = W, H, left, top, right, bottom
  *   n          number of frames; 0 is a no-op (TSDF_OK), whatever else is passed
  *   cam        constants, or NULL for the MSRA defaults (focal 241.42, principal point (160, 120), invalid_eps 1),
- *              restated in this library; trunc_voxels is unused
+ *              restated in this library; trunc_voxels is unused.
+ *              A non-NULL cam whose focal, invalid_eps or trunc_voxels is not > 0 (a NaN is not) is
+ *              TSDF_ERR_INVALID_ARG when n > 0, whichever fields the entry reads.
  *   d_out_xforms   float64[n][24], 8-byte aligned: per frame the forward map T(p) = A p + b as three rows
  *                  {A_i0, A_i1, A_i2, b_i}, then its inverse in the same form — the d_xforms of tsdf_voxelize_aug_hip
  *   d_out_moments  float64[n][16], 8-byte aligned, or NULL: N, mu[3], C as xx xy xz yy yz zz, lambda[3] descending,

@@ -91,24 +91,25 @@ def _p(a, ct):
     return a.ctypes.data_as(ctypes.POINTER(ct)) if a is not None else None
 
 
-def aabb(depth, header):
-    """A.1 -> (n_valid, min_p f32[3], max_p f32[3])."""
+def aabb(depth, header, cam=None):
+    """A.1 -> (n_valid, min_p f32[3], max_p f32[3]); ``cam`` as in :func:`voxelize`."""
     depth = np.ascontiguousarray(depth, dtype=np.float32)
     header = np.ascontiguousarray(header, dtype=np.int32)
     mn = np.zeros(3, np.float32)
     mx = np.zeros(3, np.float32)
-    nv = lib().tsdf_oracle_aabb(_p(depth, ctypes.c_float), _p(header, ctypes.c_int32), None,
+    nv = lib().tsdf_oracle_aabb(_p(depth, ctypes.c_float), _p(header, ctypes.c_int32), _cam(cam),
                                 _p(mn, ctypes.c_float), _p(mx, ctypes.c_float))
     return int(nv), mn, mx
 
 
-def glue(min_p, max_p, R=32):
-    """A.2 -> (grid f32[8] = mid_p[3],max_l,voxel_len,trunc,0,0 ; ori f32[3])."""
+def glue(min_p, max_p, R=32, cam=None):
+    """A.2 -> (grid f32[8] = mid_p[3],max_l,voxel_len,trunc,0,0 ; ori f32[3]); of ``cam`` (as in :func:`voxelize`) only
+    ``trunc_voxels`` is read."""
     mn = np.ascontiguousarray(min_p, dtype=np.float32)
     mx = np.ascontiguousarray(max_p, dtype=np.float32)
     grid = np.zeros(8, np.float32)
     ori = np.zeros(3, np.float32)
-    lib().tsdf_oracle_glue(_p(mn, ctypes.c_float), _p(mx, ctypes.c_float), R, None,
+    lib().tsdf_oracle_glue(_p(mn, ctypes.c_float), _p(mx, ctypes.c_float), R, _cam(cam),
                            _p(grid, ctypes.c_float), _p(ori, ctypes.c_float))
     return grid, ori
 

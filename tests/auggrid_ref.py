@@ -76,15 +76,17 @@ def aabb_aug(depth, header, xf, cam=None):
     return int(nv), mn, mx
 
 
-def pixel_grids(depth, off, hdr, xforms, R):
+def pixel_grids(depth, off, hdr, xforms, R, cam=None):
     """float32[n,8] grid rows (vox_ori[3], voxel_len, trunc_dis, 0, 0, 0) that oracle.glue derives for the augmented AABB
-    of all valid pixels — the placement of tsdf_voxelize_aug_hip —, and (max_l float32[n], mid_p float32[n,3])."""
+    of all valid pixels — the placement of tsdf_voxelize_aug_hip —, and (max_l float32[n], mid_p float32[n,3]).  ``cam``
+    (None, an oracle.TsdfCam or the five constants) goes to both: the AABB reads focal, cx, cy and invalid_eps, the glue
+    trunc_voxels."""
     n = len(hdr)
     grid, max_l, mid_p = np.zeros((n, 8), np.float32), np.zeros(n, np.float32), np.zeros((n, 3), np.float32)
     for i in range(n):
-        nv, mn, mx = aabb_aug(depth[off[i]:off[i + 1]], hdr[i], xforms[i])
+        nv, mn, mx = aabb_aug(depth[off[i]:off[i + 1]], hdr[i], xforms[i], cam)
         assert nv > 0
-        g, ori = oracle.glue(mn, mx, R)
+        g, ori = oracle.glue(mn, mx, R, cam)
         grid[i, :3], grid[i, 3], grid[i, 4] = ori, g[4], g[5]
         max_l[i], mid_p[i] = g[3], g[:3]
     return grid, max_l, mid_p

@@ -15,18 +15,19 @@ def header_ok(hdr, off0, off1, depth_len):
     return bw > 0 and bh > 0 and bw * bh == off1 - off0 and off0 >= 0 and off1 <= depth_len
 
 
-def cloud(depth, hdr):
-    """float64[N,3]: the valid pixels of one crop (row-major order), by the contract's point formula."""
+def cloud(depth, hdr, focal=F, cx=CX, cy=CY, eps=EPS):
+    """float64[N,3]: the valid pixels of one crop (row-major order), by the contract's point formula under the camera
+    constants ``focal``, ``cx``, ``cy`` and ``eps`` (tsdf_cam.invalid_eps)."""
     left, top, right, bottom = (int(v) for v in hdr[2:6])
     bw, bh = right - left, bottom - top
     d = np.asarray(depth, np.float32).reshape(bh, bw)
     with np.errstate(invalid="ignore"):
-        valid = np.abs(d) >= np.float32(EPS)          # NaN compares false
+        valid = np.abs(d) >= np.float32(eps)          # NaN compares false
     i, j = np.nonzero(valid)
     d64 = d[i, j].astype(np.float64)
-    s = d64 / F
-    x = ((left + j).astype(np.float64) - CX) * s
-    y = -(((top + i).astype(np.float64) - CY) * s)
+    s = d64 / focal
+    x = ((left + j).astype(np.float64) - cx) * s
+    y = -(((top + i).astype(np.float64) - cy) * s)
     return np.stack([x, y, -d64], axis=1)
 
 
@@ -50,10 +51,10 @@ def identity():
     return xf
 
 
-def frame(depth, hdr):
+def frame(depth, hdr, focal=F, cx=CX, cy=CY, eps=EPS):
     """dict(status, N, mu, C [3,3], lam [3] descending, A [3,3] rows e1 e2 e3, xf [24], pts) of one crop whose header is
-    good."""
-    pts = cloud(depth, hdr)
+    good, under the camera constants of :func:`cloud`."""
+    pts = cloud(depth, hdr, focal, cx, cy, eps)
     N = len(pts)
     out = dict(status=1, N=N, mu=np.zeros(3), C=np.zeros((3, 3)), lam=np.zeros(3), A=np.eye(3), xf=identity(), pts=pts)
     if N < 3:
@@ -76,8 +77,9 @@ def frame(depth, hdr):
     return out
 
 
-def batch(depth, offsets, headers, depth_len=None):
-    """One :func:`frame` per frame of a packed batch; a bad header gives status 2, N = 0 and the identity."""
+def batch(depth, offsets, headers, depth_len=None, focal=F, cx=CX, cy=CY, eps=EPS):
+    """One :func:`frame` per frame of a packed batch (camera constants as for :func:`cloud`); a bad header gives status 2,
+    N = 0 and the identity."""
     depth_len = len(depth) if depth_len is None else depth_len
     out = []
     for i, h in enumerate(np.asarray(headers).reshape(-1, 6)):
@@ -86,7 +88,7 @@ def batch(depth, offsets, headers, depth_len=None):
             out.append(dict(status=2, N=0, mu=np.zeros(3), C=np.zeros((3, 3)), lam=np.zeros(3), A=np.eye(3), xf=identity(),
                             pts=np.zeros((0, 3))))
         else:
-            out.append(frame(depth[o0:o1], h))
+            out.append(frame(depth[o0:o1], h, focal, cx, cy, eps))
     return out
 
 

@@ -1172,17 +1172,25 @@ def test_metadata_in_page_locked_host_memory(pkg, synth):
 
 
 @pytest.mark.parametrize("camv", [(300.0, 150.5, 118.25, 2.0, 2.5), (588.03, 320.0, 240.0, 1.0, 3.0),
-                                  (120.7, 80.0, 60.0, 0.5, 1.0), (241.42, 160.0, 120.0, 250.0, 8.0)])
+                                  (120.7, 80.0, 60.0, 0.5, 1.0), (241.42, 160.0, 120.0, 250.0, 8.0),
+                                  (241.42, 160.0, 120.0, 420.5, 3.0)])
 def test_custom_camera_constants(pkg, synth, camv):
     """tsdf_cam other than the MSRA defaults (focal length, principal point, the invalid-depth threshold of
     tsdf_numba.py:40,87 and the truncation distance in voxels of :147): every entry point against the oracle given the
     same constants — the kernel's reciprocal of the focal length, its folded pixel constants and its truncation
-    reciprocal all derive from them."""
+    reciprocal all derive from them.  The invalid_eps of the first four does not change one valid pixel of the seeded
+    frames (their depths start near 240 mm); the fifth, tests/camera_ref.py's CAM_EPS, runs on that module's batch B
+    instead of the seeded crops: its 420.5 mm lies inside B's depths and invalidates about half of every frame."""
+    import camera_ref
     d = dev()
     cam_o = camv
     cam_h = pkg.TsdfCam(*camv)
     for n, kind in ((150, "crop"), (9, "full")):
         depth, off, hdr = synth.synth_batch(n, kind, seed0=5200)
+        if camv == camera_ref.CAM_EPS and kind == "crop":
+            depth, off, hdr = camera_ref.batch_b()
+            kept = camera_ref.valid_counts(depth, off, camv[3]) / camera_ref.valid_counts(depth, off, 1.0)
+            assert 0.3 <= kept.min() and kept.max() <= 0.7
         td, to, th = (torch.from_numpy(a).to(d) for a in (depth, off, hdr))
         for R, layout in ((32, "czyx"), (40, "cxyz")):
             got = pkg.voxelize(td, to, th, res=R, layout=layout, cam=cam_h)
