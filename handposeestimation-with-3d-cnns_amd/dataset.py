@@ -544,7 +544,9 @@ class ResidentLoader(_BatchLoader):
     augmented entry.  The yielded ``gt`` are the joints in the mapped frame and ``gt_nor`` their labels, as with
     ``augment``; the map is rigid, so pose error is what it is in the camera frame, and
     ``transform_joints(pred, invert_xforms(loader.obb[index]))`` carries predictions back.  The default ``"camera"`` is the
-    loader without it, bit for bit.  ``frame="obb"`` does not combine with ``augment`` or ``graph=True``.
+    loader without it, bit for bit.  ``frame="obb"`` does not combine with ``augment`` or ``graph=True`` HERE: the
+    augmentation in the principal-axis frame is ``voxelize.AugmentedStep(..., base=obb_xforms(...).xforms)`` on
+    :class:`ResidentPacks` (the two maps composed on the device; include/tsdf_mapstep.h).
 
     ``volume_dtype=torch.float16`` / ``torch.bfloat16`` yields the volumes in that type, written once at half the bytes
     (:func:`voxelize.voxelize_grid_lowp`; include/tsdf_lowp.h) — what a network under autocast reads, and half the ring of a

@@ -649,17 +649,30 @@ class AugmentedStep:
     :func:`aug_xforms_at`, :func:`map_grids`, :func:`voxelize_map_grid_lowp` and, with labels (``gt`` on the GPU), a gather of
     the batch's joints, :func:`transform_joints` and :func:`normalize_joints` — still one linear graph on one stream over
     static buffers, nothing allocated or copied inside; ``max_l`` / ``mid_p`` / ``status`` and the labels are those of the
-    float32 step bit for bit."""
+    float32 step bit for bit.
+
+    ``base`` float64[N,24] on the GPU, one map per pack frame (``obb_xforms(...).xforms``): position i is voxelized under
+    ``draw_i o base[index[i]]`` — the augmentation about the frame's pose in ITS BASE FRAME, e.g. its principal axes.  The
+    default ``centres`` are then the base-frame grid centres, ``map_grids(depth, offsets, headers, base).mid_p`` (one launch
+    over the pack).  With ``base`` the step starts with :func:`map_step_head`: without ``dtype`` its maps alone
+    (``place=False``) and then :func:`voxelize_indexed`; with ``dtype`` the whole head — maps, placement and labels in one
+    launch — and then :func:`voxelize_map_grid_lowp`, two launches in all.  ``step`` leaves the composed maps in
+    ``self.xforms``.  ``fused_head=True`` takes that two-launch form without a ``base`` as well; its results are those of
+    the default step bit for bit.  The defaults ``base=None, fused_head=False`` issue exactly the launches listed above."""
 
     def __init__(self, depth: torch.Tensor, offsets: torch.Tensor, headers: torch.Tensor, n: int,
                  gt: Optional[torch.Tensor] = None, centres: Optional[torch.Tensor] = None, res: int = 32,
                  layout: str = "czyx", clamp: bool = True, cam: Optional[_lib.TsdfCam] = None, graph: bool = True,
-                 dtype: Optional[torch.dtype] = None):
+                 dtype: Optional[torch.dtype] = None, base: Optional[torch.Tensor] = None, fused_head: bool = False):
         if graph not in (False, True):
             raise ValueError(f"graph must be False or True, got {graph!r}")
+        if fused_head not in (False, True):
+            raise ValueError(f"fused_head must be False or True, got {fused_head!r}")
         if dtype is not None:
             _lowp_dtype(dtype)
         self.dtype = dtype
+        self.base = base
+        self._head = bool(fused_head) or base is not None
         n = int(n)
         if n < 1:
             raise ValueError("n must be >= 1")
@@ -667,7 +680,14 @@ class AugmentedStep:
         self.n, self.res, self.layout, self.clamp, self.cam, self.device = n, R, layout, clamp, cam, dev
         self._pack_args = (depth, offsets, headers)
         self._gt = gt
-        self.centres = aabb(depth, offsets, headers, res=R, cam=cam).grid[:, :3].contiguous() if centres is None else centres
+        if base is not None:
+            _shaped("base", base, (n_pack, 24), torch.float64, dev)
+        if centres is not None:
+            self.centres = centres
+        elif base is not None:   # the un-augmented grid centre in the frame the volume is cut in
+            self.centres = map_grids(depth, offsets, headers, base, res=R, cam=cam).mid_p
+        else:
+            self.centres = aabb(depth, offsets, headers, res=R, cam=cam).grid[:, :3].contiguous()
         _shaped("centres", self.centres, (n_pack, 3), torch.float32, dev)
         # index and state share one buffer, so that a step whose index comes from the host uploads both with one copy
         self._in = torch.zeros(n + 2, dtype=torch.int64, device=dev)
@@ -688,8 +708,11 @@ class AugmentedStep:
             shape = (n,) + tuple(gt.shape[1:])
             self.gt_nor = torch.empty(shape, dtype=torch.float32, device=dev)
             self.gt_aug = torch.empty(shape, dtype=torch.float32, device=dev)
-            if dtype is not None:   # the batch's frame numbers kept inside the pack, and its joints before the map
+            if dtype is not None and not self._head:   # the batch's frame numbers kept inside the pack, and its joints before the map
                 self._sel = (torch.empty(n, dtype=torch.int64, device=dev), torch.empty(shape, dtype=torch.float32, device=dev))
+        if self._head:   # what map_step_head writes into: the object's own buffers
+            g = self._grid if dtype is not None else MapGridBatch(None, None, None, None)
+            self._head_out = MapStepBatch(self.xforms, g.grid, g.max_l, g.mid_p, g.status, self.gt_aug, self.gt_nor)
         self.graph = None
         self._run()                      # eagerly once: argument checks, library loads and the device check happen here
         if graph:
@@ -701,8 +724,21 @@ class AugmentedStep:
             self.graph = g
 
     def _run(self):
-        aug_xforms_at(self.centres, self.state, index=self.index, out=self.xforms)
         d, o, h = self._pack_args
+        if self._head:
+            lowp = self.dtype is not None
+            map_step_head(d, o, h, self.centres, self.state, base=self.base, index=self.index,
+                          gt=self._gt if lowp else None, res=self.res, cam=self.cam, clamp=self.clamp, place=lowp,
+                          out=self._head_out)
+            if lowp:
+                _map_grid_lowp(d, o, h, self.xforms, self._grid.grid, self.res, self.layout, self.dtype, self.cam, self.index,
+                               self.out.tsdf, False)
+            else:
+                voxelize_indexed(d, o, h, self.index, self._gt, res=self.res, layout=self.layout, cam=self.cam,
+                                 clamp=self.clamp, out=self.out, xforms=self.xforms, out_gt_nor=self.gt_nor,
+                                 out_gt=self.gt_aug)
+            return
+        aug_xforms_at(self.centres, self.state, index=self.index, out=self.xforms)
         if self.dtype is None:
             voxelize_indexed(d, o, h, self.index, self._gt, res=self.res, layout=self.layout, cam=self.cam, clamp=self.clamp,
                              out=self.out, xforms=self.xforms, out_gt_nor=self.gt_nor, out_gt=self.gt_aug)
@@ -1245,3 +1281,109 @@ def voxelize_aug_lowp(depth: torch.Tensor, offsets: torch.Tensor, headers: torch
     _dev_check("gt", gt, torch.float32, depth.device)
     gt_nor, gt_aug = _batch_labels(gt, index, headers.shape[0], xforms, mg.max_l, mg.mid_p, clamp)
     return batch, gt_nor, gt_aug
+
+
+def compose_xforms(outer: torch.Tensor, inner: torch.Tensor, index: Optional[torch.Tensor] = None,
+                   out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Two sets of per-frame maps composed into one (``tsdf_compose_xforms_hip`` of libtsdf_mapstep.so;
+    include/tsdf_mapstep.h has the contract): ``out[i] = outer[i] o inner[g]``, the map that applies ``inner[g]`` first and
+    ``outer[i]`` second, ``g = index[i]`` (without ``index``: ``i``).  The forward rows are composed in that order and the
+    inverse rows the other way round, in float64 with every product and sum rounded on its own; no matrix is inverted.
+
+    outer   float64[n,24] on the GPU: one map per batch position (an augmentation: :func:`aug_xforms_at`)
+    inner   float64[N,24] on the GPU: one map per source frame (a principal-axis map: :func:`obb_xforms`)
+    index   optional int64[n] on the GPU; without it N must equal n.  An entry outside [0, N) gives ``out[i] = outer[i]``
+    out     optional float64[n,24] to write into (it is returned; it may be ``outer``)
+    One small launch on the current stream, no synchronisation."""
+    S = _lib.load_mapstep()
+    _dev_check("outer", outer, torch.float64)
+    dev = outer.device
+    if outer.dim() != 2 or outer.shape[1] != 24:
+        raise ValueError("outer must have shape [n, 24] (forward rows then inverse rows)")
+    n = outer.shape[0]
+    _dev_check("inner", inner, torch.float64, dev)
+    if inner.dim() != 2 or inner.shape[1] != 24:
+        raise ValueError("inner must have shape [N, 24] (forward rows then inverse rows)")
+    n_inner = inner.shape[0]
+    if index is not None:
+        _shaped("index", index, (n,), torch.int64, dev)
+        if n and not n_inner:
+            raise ValueError("index needs at least one inner map")
+    elif n_inner != n:
+        raise ValueError("without index, inner must hold one map per map of outer")
+    out = _out("out", out, (n, 24), torch.float64, dev)
+    if n:
+        _call(dev, S.tsdf_compose_xforms_hip, [outer.data_ptr(), inner.data_ptr(), n_inner, _ptr(index), n, None,
+                                               out.data_ptr()], 5)
+    return out
+
+
+class MapStepBatch(NamedTuple):
+    xforms: torch.Tensor             # float64[n, 24]  the map of every batch position: the draw, composed with its base
+    grid: Optional[torch.Tensor]     # float32[n, 8]   the placement's rows (None with place=False, as the three below)
+    max_l: Optional[torch.Tensor]    # float32[n]      in the mapped frame
+    mid_p: Optional[torch.Tensor]    # float32[n, 3]
+    status: Optional[torch.Tensor]   # int32[n]  (_lib.TSDF_FRAME_*)
+    gt_aug: Optional[torch.Tensor]   # the batch's joints under the maps (None without gt)
+    gt_nor: Optional[torch.Tensor]   # their labels in the mapped grid
+
+
+def map_step_head(depth: torch.Tensor, offsets: torch.Tensor, headers: torch.Tensor, centres: torch.Tensor,
+                  state: torch.Tensor, *, base: Optional[torch.Tensor] = None, index: Optional[torch.Tensor] = None,
+                  counters: Optional[torch.Tensor] = None, gt: Optional[torch.Tensor] = None, res: int = 32,
+                  cam: Optional[_lib.TsdfCam] = None, clamp: bool = True, place: bool = True,
+                  out: Optional[MapStepBatch] = None, return_params: bool = False):
+    """Everything the augmented step does before its voxel pass, in ONE launch (``tsdf_map_step_head_hip`` of
+    libtsdf_mapstep.so; include/tsdf_mapstep.h has the contract): the draw of :func:`aug_xforms_at`, its composition with
+    the source frame's ``base`` map (:func:`compose_xforms`), the grid placement of :func:`map_grids` under the result and
+    the batch's labels (:func:`transform_joints`, :func:`normalize_joints`) — every output bit for bit what that chain of
+    five or six launches writes.
+
+    depth / offsets / headers   the N source frames, as for :func:`voxelize`
+    centres   float32[N,3] on the GPU: the centre each frame's augmentation turns about, in the frame the volume is cut in
+    state     int64[2] on the GPU: ``{key, counter0}``, read by the kernel (:func:`aug_state`)
+    base      optional float64[N,24] on the GPU: one map per SOURCE frame (``obb_xforms(...).xforms``); position i is
+              voxelized under ``draw_i o base[index[i]]``
+    index, counters   optional int64[n] (device or page-locked host memory), as for :func:`aug_xforms_at`
+    gt        optional float32[N,3J] (or [N,J,3]) on the GPU: the joints of every source frame (needs ``place``)
+    place     False: the maps alone — the depth is not read, and ``grid`` / ``max_l`` / ``mid_p`` / ``status`` are None
+    out       optional preallocated :class:`MapStepBatch` to write into (fields that the call does not write are ignored)
+    Returns :class:`MapStepBatch`, or with ``return_params`` ``(MapStepBatch, stretch float64[n], rot int32[n,2])``.
+    ``xforms`` and ``grid`` go straight to :func:`voxelize_map_grid_lowp`, ``xforms`` alone to :func:`voxelize_indexed`."""
+    S = _lib.load_mapstep()
+    dev, n_src, R = _pack(_lib.load(), depth, offsets, headers, res)
+    _, n_c, n, xf, stretch, rot = _draw_args(centres, None, index, counters, out.xforms if out is not None else None,
+                                             return_params, state)
+    if centres.device != dev:
+        raise ValueError(f"centres is on {centres.device}, expected {dev}")
+    if n_c != n_src:
+        raise ValueError("centres must hold one centre per source frame: [N, 3]")
+    if base is not None:
+        _shaped("base", base, (n_src, 24), torch.float64, dev)
+    grid = max_l = mid_p = status = gt_aug = gt_nor = None
+    nj = 0
+    if place:
+        fields = (("grid", (n, 8), torch.float32), ("max_l", (n,), torch.float32), ("mid_p", (n, 3), torch.float32),
+                  ("status", (n,), torch.int32))
+        grid, max_l, mid_p, status = (_out("out." + name, getattr(out, name) if out is not None else None, shape, dtype, dev)
+                                      for name, shape, dtype in fields)
+    if gt is not None:
+        if not place:
+            raise ValueError("gt needs place=True (the labels are normalised in the placed grid)")
+        _dev_check("gt", gt, torch.float32, dev)
+        if gt.dim() < 2:
+            raise ValueError("gt must hold the labels of every source frame: [N, 3*J] or [N, J, 3]")
+        nj = (_coords("gt", gt, n_src) or 63) // 3
+        shape = (n,) + tuple(gt.shape[1:])
+        gt_aug = _out("out.gt_aug", out.gt_aug if out is not None else None, shape, torch.float32, dev)
+        gt_nor = _out("out.gt_nor", out.gt_nor if out is not None else None, shape, torch.float32, dev)
+    if n:
+        c = cam if cam is not None else _lib.default_cam()   # the entry takes the five constants by value
+        _call(dev, S.tsdf_map_step_head_hip,
+              [depth.data_ptr(), depth.numel(), offsets.data_ptr(), headers.data_ptr(), n_src, _ptr(index), n, R, c.focal, c.cx,
+               c.cy, c.invalid_eps, c.trunc_voxels, centres.data_ptr(), _ptr(base), state.data_ptr(), _ptr(counters), _ptr(gt), nj,
+               1 if clamp else 0, None,
+               xf.data_ptr(), _ptr(grid), _ptr(max_l), _ptr(mid_p), _ptr(status), _ptr(gt_aug), _ptr(gt_nor), _ptr(stretch),
+               _ptr(rot)], 20)
+    batch = MapStepBatch(xf, grid, max_l, mid_p, status, gt_aug, gt_nor)
+    return (batch, stretch, rot) if return_params else batch
