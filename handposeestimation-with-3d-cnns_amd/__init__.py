@@ -34,6 +34,9 @@ Volumes in float16 / bfloat16:           voxelize_grid_lowp (the plain voxel pas
 Augmentation in a base (OBB) frame:      compose_xforms (two per-frame maps as one), map_step_head (draw, compose, grid
                                          placement and labels in one launch: libtsdf_mapstep.so, include/tsdf_mapstep.h),
                                          AugmentedStep(base=..., fused_head=...)
+Raw frames without a bounding box:       locate_hands (the nearest object's centre of mass, a fixed cube about it, the crops
+                                         packed as depth / offsets / headers: libtsdf_locate.so, include/tsdf_locate.h),
+                                         voxelize_frames (placement="aabb" | "cube")
 """
 from . import _lib  # noqa: F401
 from ._lib import TsdfCam, TsdfError, default_cam  # noqa: F401
@@ -44,7 +47,8 @@ from .voxelize import (AabbBatch, AugmentedStep, CloudGridBatch, MapGridBatch, O
                        project_joints, release_stream, transform_joints, voxel_pixels, voxelize_aug_grid,
                        voxelize, voxelize_aug, voxelize_grid, voxelize_indexed, voxelize_labels, widen_depth16,
                        invert_xforms, obb_xforms, voxelize_obb, narrow_volumes, voxelize_grid_lowp, voxelize_lowp,
-                       map_grids, voxelize_aug_lowp, voxelize_map_grid_lowp, MapStepBatch, compose_xforms, map_step_head)
+                       map_grids, voxelize_aug_lowp, voxelize_map_grid_lowp, MapStepBatch, compose_xforms, map_step_head,
+                       HandCrops, locate_hands, voxelize_frames)
 from .pca import JointPCA, fit_joint_pca  # noqa: F401
 from . import augment, dataset, export, packing, pca, shard, synth  # noqa: F401
 from .dataset import MSRA_Dataset, MSRADepthDataset, ResidentLoader, VoxelBatch, VoxelLoader  # noqa: F401
@@ -60,4 +64,5 @@ __all__ = ["voxelize", "voxelize_labels", "voxelize_indexed", "ResidentLoader", 
            "aug_xforms_at", "aug_state", "AugmentedStep", "voxelize_aug_grid", "transform_joints", "process_batch_aug",
            "ProcessAugBatch", "widen_depth16", "obb_xforms", "voxelize_obb", "invert_xforms", "ObbBatch",
            "voxelize_grid_lowp", "voxelize_lowp", "narrow_volumes", "map_grids", "MapGridBatch", "voxelize_map_grid_lowp",
-           "voxelize_aug_lowp", "compose_xforms", "map_step_head", "MapStepBatch"]
+           "voxelize_aug_lowp", "compose_xforms", "map_step_head", "MapStepBatch", "locate_hands", "voxelize_frames",
+           "HandCrops"]

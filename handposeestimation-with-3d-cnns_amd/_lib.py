@@ -129,6 +129,13 @@ MAPLOWP_VERSION = 1
 MAPSTEP_LIB_PATH = os.path.join(_HERE, "libtsdf_mapstep.so")
 MAPSTEP_VERSION = 1
 
+# The extension library of include/tsdf_locate.h (make -C csrc locate): the hand located in raw depth frames (the nearest
+# object's centre of mass, a fixed cube around it) and the crops packed as depth / offsets / headers.  A binary of its own.
+LOCATE_LIB_PATH = os.path.join(_HERE, "libtsdf_locate.so")
+LOCATE_VERSION = 1
+TSDF_LOCATE_F32 = 0   # `frame_type` of include/tsdf_locate.h
+TSDF_LOCATE_U16 = 1
+
 
 class _Ext(NamedTuple):
     """A row of the extension table: libtsdf_<name>.so, built by ``make -C csrc <name>`` from include/tsdf_<name>.h."""
@@ -201,6 +208,16 @@ _EXTS_OPEN = {
         "tsdf_map_step_head_hip": [_vp, _i64, _vp, _vp, _i64, _vp, _i, _i, ctypes.c_double, ctypes.c_double, ctypes.c_double,
                                    ctypes.c_float, ctypes.c_float, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp,
                                    _vp, _vp, _vp, _vp, _vp],
+    }),
+    "locate": _Ext(LOCATE_LIB_PATH, "tsdf_locate_version", LOCATE_VERSION, {
+        # H, W, cube, near, focal, per_frame (an int64 in host memory)
+        "tsdf_locate_capacity": [_i, _i, ctypes.c_float, ctypes.c_float, ctypes.c_double, ctypes.POINTER(_i64)],
+        # frames, frame_type, shift, n_src, H, W, index, n, near, far, cube, seed_band, refine, R, focal, cx, cy, invalid_eps,
+        # trunc_voxels (the camera by value), depth_capacity, stream, depth, offsets, headers, com, count, status, grid,
+        # max_l, mid_p
+        "tsdf_locate_hip": [_vp, _i, _i, _i64, _i, _i, _vp, _i, ctypes.c_float, ctypes.c_float, ctypes.c_float,
+                            ctypes.c_float, _i, _i, ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_float,
+                            ctypes.c_float, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     }),
 }
 
@@ -351,6 +368,11 @@ def load_maplowp():
 def load_mapstep():
     """libtsdf_mapstep.so, the library of include/tsdf_mapstep.h."""
     return _load_ext("mapstep")
+
+
+def load_locate():
+    """libtsdf_locate.so, the library of include/tsdf_locate.h."""
+    return _load_ext("locate")
 
 
 @contextlib.contextmanager

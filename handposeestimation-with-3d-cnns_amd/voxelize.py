@@ -1387,3 +1387,152 @@ def map_step_head(depth: torch.Tensor, offsets: torch.Tensor, headers: torch.Ten
                _ptr(rot)], 20)
     batch = MapStepBatch(xf, grid, max_l, mid_p, status, gt_aug, gt_nor)
     return (batch, stretch, rot) if return_params else batch
+
+
+class HandCrops(NamedTuple):
+    depth: torch.Tensor              # float32[capacity]  the crops packed back to back; the tail past offsets[n] is unwritten
+    offsets: torch.Tensor            # int64[n + 1]
+    headers: torch.Tensor            # int32[n, 6]     W, H, left, top, right, bottom
+    com: torch.Tensor                # float64[n, 3]   the centre c of the cube, camera frame, mm
+    count: torch.Tensor              # int32[n]        pixels kept in the crop
+    status: torch.Tensor             # int32[n]        0, 1 (no valid pixel), 2 (index outside the frames)
+    grid: Optional[torch.Tensor]     # float32[n, 8]   the CUBE grid rows (None with grid=False, as the two below)
+    max_l: Optional[torch.Tensor]    # float32[n]      cube
+    mid_p: Optional[torch.Tensor]    # float32[n, 3]   float32(c)
+
+
+_LOCATE_TYPES = {torch.float32: _lib.TSDF_LOCATE_F32, torch.uint16: _lib.TSDF_LOCATE_U16}
+
+
+def locate_hands(frames: torch.Tensor, *, cube: float = 250.0, near: float = 100.0, far: float = 1500.0,
+                 seed_band: float = 150.0, refine: int = 2, res: int = 32, cam: Optional[_lib.TsdfCam] = None,
+                 shift: Optional[int] = None, index: Optional[torch.Tensor] = None, grid: bool = True,
+                 out: Optional[HandCrops] = None) -> HandCrops:
+    """The hand located in raw depth frames on the GPU (``tsdf_locate_hip`` of libtsdf_locate.so; include/tsdf_locate.h
+    has the contract): per frame the nearest object's centre of mass — the valid pixels (finite, ``|d| >= invalid_eps``,
+    ``near <= d <= far``) within ``seed_band`` mm of the nearest one —, a cube of edge ``cube`` mm about it, ``refine``
+    rounds of "the centre of what is inside the cube", and the cube's pixels (everything else zeroed) packed as the
+    ``depth / offsets / headers`` triple every entry here takes: :func:`voxelize`, :func:`voxelize_lowp`,
+    :func:`voxelize_obb`, :func:`process_batch`, :class:`AugmentedStep`.  Nothing goes through the host.
+
+    frames   float32[N,H,W] mm, or uint16[N,H,W] with ``shift`` (0..7): the depth is ``u * 2^-shift``, packing's encoding
+    index    optional int64[n] on the GPU: batch position i is frame index[i] (outside [0, N): status 2)
+    res      enters the cube grid rows alone
+    grid     False: no ``grid`` / ``max_l`` / ``mid_p``
+    out      optional preallocated :class:`HandCrops` to write into (capturable); ``out.depth`` must hold n times the
+             capacity rule's pixels (``min(W, s) * min(H, s)``, ``s = floor(cube * focal / near) + 2``)
+    A position without a valid pixel (status 1) or with a bad index (2) gets the header [W, H, 0, 0, 1, 1], one pixel of
+    0 and zero rows: the voxelizers report their own status 1 for it.  ``grid`` goes to :func:`voxelize_grid`: the
+    fixed-cube placement of DeepPrior++ / V2V-PoseNet, with ``max_l`` = cube and ``mid_p`` = the centre for the labels.
+    Three small launches on the current stream, no synchronisation; two calls give identical bits."""
+    K = _lib.load_locate()
+    if not isinstance(frames, torch.Tensor):
+        raise TypeError("frames must be a torch.Tensor")
+    # what the frames ARE (type, shape, encoding) before where they live: each refusal names its own cause
+    if frames.dtype not in _LOCATE_TYPES:
+        raise TypeError(f"frames must be torch.float32 or torch.uint16, got {frames.dtype}")
+    if frames.dim() != 3 or frames.shape[1] < 1 or frames.shape[2] < 1:
+        raise ValueError("frames must have shape [N, H, W]")
+    u16 = frames.dtype is torch.uint16
+    if u16:
+        if isinstance(shift, bool) or not isinstance(shift, int) or not 0 <= shift <= _lib.DEPTH16_MAX_SHIFT:
+            raise ValueError(f"uint16 frames need shift, an integer in 0..{_lib.DEPTH16_MAX_SHIFT}; got {shift!r}")
+    elif shift is not None:
+        raise ValueError("shift belongs to uint16 frames")
+    if not _lib.load().tsdf_resolution_supported(int(res)):
+        raise ValueError(f"unsupported grid resolution {res} (multiple of 4 in 4..128)")
+    if isinstance(refine, bool) or not isinstance(refine, int):
+        raise TypeError("refine must be an integer")
+    if not frames.is_contiguous():
+        raise ValueError("frames must be contiguous")
+    _dev_check("frames", frames, frames.dtype)
+    dev = frames.device
+    n_src, H, W = (int(v) for v in frames.shape)
+    n = n_src
+    if index is not None:
+        _dev_check("index", index, torch.int64, dev)
+        if index.dim() != 1:
+            raise ValueError("index must have shape [n]")
+        n = int(index.shape[0])
+        if n and not n_src:
+            raise ValueError("index needs at least one frame")
+    c = cam if cam is not None else _lib.default_cam()   # the entry takes the five constants by value
+    per = ctypes.c_int64(0)
+    _lib.check(K.tsdf_locate_capacity(H, W, cube, near, c.focal, ctypes.byref(per)), "tsdf_locate_capacity")
+    need = n * per.value
+    get = (lambda name: getattr(out, name)) if out is not None else (lambda name: None)
+    if out is not None:
+        _dev_check("out.depth", out.depth, torch.float32, dev)
+        if out.depth.dim() != 1 or out.depth.numel() < need:
+            raise ValueError(f"out.depth must be a vector of at least {need} elements ({n} frames of {per.value})")
+        depth = out.depth
+    else:
+        depth = torch.empty((need,), dtype=torch.float32, device=dev)
+    if n == 0:
+        offsets = torch.zeros((1,), dtype=torch.int64, device=dev) if out is None else \
+            _shaped("out.offsets", out.offsets, (1,), torch.int64, dev).zero_()
+    else:
+        offsets = _out("out.offsets", get("offsets"), (n + 1,), torch.int64, dev)
+    headers = _out("out.headers", get("headers"), (n, 6), torch.int32, dev)
+    com = _out("out.com", get("com"), (n, 3), torch.float64, dev)
+    count = _out("out.count", get("count"), (n,), torch.int32, dev)
+    status = _out("out.status", get("status"), (n,), torch.int32, dev)
+    g = max_l = mid_p = None
+    if grid:
+        g = _out("out.grid", get("grid"), (n, 8), torch.float32, dev)
+        max_l = _out("out.max_l", get("max_l"), (n,), torch.float32, dev)
+        mid_p = _out("out.mid_p", get("mid_p"), (n, 3), torch.float32, dev)
+    if n:
+        _call(dev, K.tsdf_locate_hip,
+              [frames.data_ptr(), _LOCATE_TYPES[frames.dtype], shift if u16 else 0, n_src, H, W, _ptr(index), n, near, far, cube,
+               seed_band, refine, int(res), c.focal, c.cx, c.cy, c.invalid_eps, c.trunc_voxels, depth.numel(), None,
+               depth.data_ptr(), offsets.data_ptr(), headers.data_ptr(), com.data_ptr(), count.data_ptr(), status.data_ptr(),
+               _ptr(g), _ptr(max_l), _ptr(mid_p)], 20)
+    return HandCrops(depth, offsets, headers, com, count, status, g, max_l, mid_p)
+
+
+def voxelize_frames(frames: torch.Tensor, res: int = 32, *, placement: str = "aabb", dtype: Optional[torch.dtype] = None,
+                    gt: Optional[torch.Tensor] = None, layout: str = "czyx", **locate):
+    """Raw depth frames to volumes: :func:`locate_hands` chained into the existing voxelizers on one stream, nothing on
+    the host in between.  Returns ``(TsdfBatch, HandCrops)``, or with ``gt`` (float32[n,3J] or [n,J,3] on the GPU, the
+    joints of every batch position, camera frame) ``(TsdfBatch, HandCrops, gt_nor)``.
+
+    placement   "aabb": the grid on the located cloud's extremes, as the reference places it — :func:`voxelize` /
+                :func:`voxelize_labels` (``dtype=None``) or :func:`voxelize_lowp`; the volumes, ``max_l`` and ``mid_p`` are
+                exactly what those entries give for the located pack.
+                "cube": the grid on the located cube — :func:`voxelize_grid` or :func:`voxelize_grid_lowp` on
+                ``HandCrops.grid``; ``max_l`` / ``mid_p`` of the batch are the cube's (its edge and centre), so a frame's
+                scale does not move with a finger, and the labels are ``normalize_joints(gt, max_l, mid_p)``.
+    dtype       None (float32 volumes), torch.float16 or torch.bfloat16
+    **locate    :func:`locate_hands`' keywords (``cube``, ``near``, ``far``, ``seed_band``, ``refine``, ``cam``, ``shift``,
+                ``index``, ``out``); ``cam`` goes to the voxelizer as well."""
+    if placement not in ("aabb", "cube"):
+        raise ValueError("placement must be 'aabb' or 'cube'")
+    if layout not in _lib.LAYOUTS:
+        raise ValueError("layout must be 'czyx' or 'cxyz'")
+    if dtype is not None:
+        _lowp_dtype(dtype)
+    if "grid" in locate or "res" in locate:
+        raise TypeError("voxelize_frames sets locate_hands' grid and res itself")
+    cam = locate.get("cam")
+    crops = locate_hands(frames, res=res, grid=placement == "cube", **locate)
+    d, o, h = crops.depth, crops.offsets, crops.headers
+    gt_nor = None
+    if placement == "aabb":
+        if dtype is not None:
+            batch = voxelize_lowp(d, o, h, res=res, layout=layout, dtype=dtype, cam=cam)
+        elif gt is not None:
+            batch, gt_nor = voxelize_labels(d, o, h, gt, res=res, layout=layout, cam=cam)
+        else:
+            batch = voxelize(d, o, h, res=res, layout=layout, cam=cam)
+    else:
+        if dtype is not None:
+            tsdf, st = voxelize_grid_lowp(d, o, h, crops.grid, res=res, layout=layout, dtype=dtype, cam=cam)
+        else:
+            tsdf, st = voxelize_grid(d, o, h, crops.grid, res=res, layout=layout, cam=cam)
+        batch = TsdfBatch(tsdf, crops.max_l, crops.mid_p, st)
+    if gt is None:
+        return batch, crops
+    if gt_nor is None:
+        gt_nor = normalize_joints(gt, batch.max_l, batch.mid_p)
+    return batch, crops, gt_nor
