@@ -147,8 +147,9 @@ class _Ext(NamedTuple):
 
 _vp, _i, _i64, _u64 = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_uint64
 
-# The extension libraries, in the order of csrc/Makefile's EXTS.  Adding one is a row in _EXTS_OPEN below, a name in EXTS (with what its
-# tsdf_<name>.hip includes besides device.inc / prim.inc in <name>_DEPS) and a one-line load_<name> below.
+# The extension libraries, in the order of csrc/Makefile's EXTS.  Adding one is a row here, a name in EXTS (with what its
+# tsdf_<name>.hip includes besides device.inc in <name>_DEPS), a one-line load_<name> below and a name in the list of
+# tests/test_ext_table_cpu.py, which checks every row against its header and its binary.
 _EXTS = {
     "augment": _Ext(AUGMENT_LIB_PATH, "tsdf_augment_version", AUGMENT_VERSION, {
         # centres, n_src, index, n, key, counter0, stream, xforms, stretch, rot
@@ -181,11 +182,6 @@ _EXTS = {
         # in, count, dtype, stream, out
         "tsdf_lowp_narrow_hip": [_vp, _i64, _i, _vp, _vp],
     }),
-}
-
-# The rows added since the table above was pinned at six by the tests of the libraries it holds; _load_ext looks here
-# after _EXTS.  One table again is a clean-up of its own ("Adding an extension library").
-_EXTS_MORE = {
     "maplowp": _Ext(MAPLOWP_LIB_PATH, "tsdf_maplowp_version", MAPLOWP_VERSION, {
         # depth, depth_len, offsets, headers, n_src, index, n, R, cam, stream, xforms, grid, max_l, mid_p, status
         "tsdf_map_place_hip": [_vp, _i64, _vp, _vp, _i64, _vp, _i, _i, ctypes.POINTER(TsdfCam), _vp, _vp, _vp, _vp, _vp, _vp],
@@ -193,12 +189,6 @@ _EXTS_MORE = {
         "tsdf_voxelize_map_grid_lowp_hip": [_vp, _i64, _vp, _vp, _i64, _vp, _i, _i, ctypes.POINTER(TsdfCam), _i, _i, _vp, _vp,
                                             _vp, _vp, _vp],
     }),
-}
-
-# The OPEN table: the rows added since _EXTS_MORE was pinned at one by the test of the library it holds; _load_ext looks
-# here after the two above.  No test pins THIS table's key list — each library's own test checks its own row only — so the
-# next library is a row here, not a fourth table.
-_EXTS_OPEN = {
     "mapstep": _Ext(MAPSTEP_LIB_PATH, "tsdf_mapstep_version", MAPSTEP_VERSION, {
         # outer, inner, n_inner, index, n, stream, out
         "tsdf_compose_xforms_hip": [_vp, _vp, _i64, _vp, _i, _vp, _vp],
@@ -317,7 +307,7 @@ def _load_ext(name: str):
     L = _ext_libs.get(name)
     if L is not None:
         return L
-    ext = next(t[name] for t in (_EXTS, _EXTS_MORE, _EXTS_OPEN) if name in t)
+    ext = _EXTS[name]
     if not os.path.exists(ext.path):
         raise ImportError(f"{ext.path} not found: build it with `make -C handposeestimation-with-3d-cnns_amd/csrc "
                           f"{name}` (__graft_entry__.build() does). There is no CPU fallback.")

@@ -1,11 +1,12 @@
-// device.inc — the host preamble of every library here: tsdf_hip.hip and the extensions (tsdf_augment.hip,
-// tsdf_augstep.hip, tsdf_auggrid.hip, tsdf_depth16.hip, tsdf_obb.hip, tsdf_lowp.hip, tsdf_maplowp.hip) include it, so "is this a device the
-// code object runs on" and the two return idioms of an entry point exist once.  Host code only; it exports nothing.
+// device.inc — the host preamble of every library here: every tsdf_*.hip here, the product's and each extension's,
+// includes it, so "is this a device the code object runs on", the two return idioms of an entry point and the resolution
+// rule exist once.  Host code only; it exports nothing.
 // (The device primitives that exist once are in prim.inc.)
 //   check_device   the current device is a gfx950
 //   device_cus     its CU count, for an entry that sizes a grid by it
 //   launched       the status an entry returns after its launch
 //   misaligned     the alignment test of a pointer argument
+//   bad_res        the resolution rule of an extension's entry
 //
 // Included inside an anonymous namespace, after <hip/hip_runtime.h>, <stdint.h>, <string.h>, <atomic> and include/tsdf.h.
 
@@ -58,3 +59,6 @@ int launched() { return hipGetLastError() == hipSuccess ? TSDF_OK : TSDF_ERR_LAU
 
 // p is not a multiple of mask + 1 (mask: 1, 3, 7 or 15)
 bool misaligned(const void *p, uintptr_t mask) { return (reinterpret_cast<uintptr_t>(p) & mask) != 0; }
+
+// R is not a resolution an extension voxelizes or places at (include/tsdf.h: tsdf_resolution_supported)
+[[maybe_unused]] bool bad_res(int R) { return R < 4 || R > 128 || R % 4 != 0; }

@@ -1,8 +1,9 @@
 // narrow.inc — the store side of a kernel that writes float16 / bfloat16 volumes: tsdf_lowp.hip and tsdf_maplowp.hip
-// include it (inside their anonymous namespace, after <hip/hip_runtime.h>); the product does not.
+// include it (inside their anonymous namespace, after <hip/hip_runtime.h> and include/tsdf_lowp.h); the product does not.
 //   narrow2      two float32 -> one 32-bit word of two 2-byte values, round-to-nearest-even
 //   store_vol    one 16-byte or 8-byte store of the output volume with the scope bits of TSDF_LOWP_STORE_ASM
 //   Piece<V>     the vector type a lane's V voxels of one channel leave in
+//   bad_dtype    host: the dtype test of an entry
 // No device globals.  All stores are vector stores.
 
 typedef float lowp_f2 __attribute__((ext_vector_type(2)));
@@ -47,3 +48,5 @@ template <>
 struct Piece<4> {
   typedef lowp_u2 type;
 };
+
+bool bad_dtype(int dtype) { return dtype != TSDF_LOWP_F16 && dtype != TSDF_LOWP_BF16; }

@@ -6,11 +6,11 @@
 //   slab_frame       a source frame's crop, depth, grid row and status (slab_frame_row: on a row the kernel picks)
 //   slab_zero_fill   the zeros of a slab whose frame is not OK
 //   slab_plan        host: slices per workgroup, workgroups per position, workgroups in all
-//   slab_bad_shape   host: the R / layout test of an entry
+//   slab_bad_shape   host: the R / layout test of an entry (device.inc::bad_res and the layout enum)
 // The voxel arithmetic of each kernel stays in its own file.
 
 constexpr int kSlabWG = 256;       // threads per workgroup (4 wave64)
-constexpr int kSlabMaxR = 128;     // largest resolution (include/tsdf.h: tsdf_resolution_supported)
+constexpr int kSlabMaxR = 128;     // largest resolution (device.inc::bad_res)
 constexpr int kSlabItems = 512;    // items (V voxels each) a workgroup aims for: two per lane
 
 struct Slab {
@@ -95,5 +95,5 @@ bool slab_plan(int n, int R, int V, SlabPlan &p) {
 }
 
 bool slab_bad_shape(int R, int layout) {
-  return R < 4 || R > kSlabMaxR || (R & 3) || (layout != TSDF_LAYOUT_CZYX && layout != TSDF_LAYOUT_CXYZ);
+  return bad_res(R) || (layout != TSDF_LAYOUT_CZYX && layout != TSDF_LAYOUT_CXYZ);
 }

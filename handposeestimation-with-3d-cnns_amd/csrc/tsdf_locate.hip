@@ -455,8 +455,6 @@ __global__ __launch_bounds__(kLocWG) void tsdf_locate_copy_kernel(LocArgs a) {
   }
 }
 
-bool bad_res(int R) { return R < 4 || R > 128 || R % 4 != 0; }
-
 // the capacity rule's s, held to what an int holds (the sides are min(W, s), min(H, s))
 bool capacity_side(float cube, float near_mm, double focal, int *s) {
   if (!(cube > 0.f) || !(near_mm > 0.f) || !(focal > 0.0)) return false;

@@ -43,7 +43,7 @@ namespace {
 #include "device.inc"   // check_device, launched, misaligned: the host preamble of every library here
 #include "prim.inc"     // kDefaultCam, trunc_i32, finite32, f32_round_up, header_ok
 #include "slab.inc"     // workgroup <-> slab, the frame's header and grid row, zero-fill, host sizing
-#include "narrow.inc"   // narrow2, store_vol, Piece: the 2-byte store side, shared with tsdf_maplowp.hip
+#include "narrow.inc"   // narrow2, store_vol, Piece, bad_dtype: the 2-byte store side, shared with tsdf_maplowp.hip
 
 constexpr int kNarrowMaxBlocks = 1 << 16;   // the narrowing kernel strides over anything larger
 
@@ -224,8 +224,6 @@ __global__ __launch_bounds__(kSlabWG) void tsdf_lowp_narrow_kernel(NarrowArgs a)
   const int64_t t = (n8 << 3) + threadIdx.x;
   if (blockIdx.x == 0 && threadIdx.x < 8 && t < a.count) a.out[t] = (uint16_t)narrow2<BF16>(a.in[t], 0.0f);
 }
-
-bool bad_dtype(int dtype) { return dtype != TSDF_LOWP_F16 && dtype != TSDF_LOWP_BF16; }
 
 template <int LAYOUT, bool BF16>
 void launch_grid(const LowpArgs &a, int64_t blocks, hipStream_t s) {

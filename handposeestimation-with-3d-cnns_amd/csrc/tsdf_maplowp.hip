@@ -4,22 +4,23 @@
 // A translation unit and a library of its own, next to libtsdf_hip.so and the other extension libraries (all frozen).  It
 // takes the status codes, tsdf_cam and the layout enum from include/tsdf.h, the dtype enum from include/tsdf_lowp.h, the
 // host preamble every library here has from device.inc, the device primitives from prim.inc, the slab scaffold it shares
-// with tsdf_auggrid.hip and tsdf_lowp.hip from slab.inc and the store side it shares with tsdf_lowp.hip from narrow.inc.
-// The augmented voxel arithmetic (tsdf_auggrid.hip::tsdf_aug_grid_kernel) and the float32 glue (phase1.inc::glue,
-// frame.inc::place_grid) are RESTATED here operation for operation; nothing of the product's other .inc files is
-// included, and there is no device global: every launch is self-contained.
+// with tsdf_auggrid.hip and tsdf_lowp.hip from slab.inc, the store side it shares with tsdf_lowp.hip from narrow.inc and
+// the placement's arithmetic — the crop pass, the wave butterfly, the float32 glue and the degenerate rule — from
+// place.inc, which it shares with tsdf_mapstep.hip.  The augmented voxel arithmetic (tsdf_auggrid.hip::
+// tsdf_aug_grid_kernel) is RESTATED here operation for operation; nothing of the product's other .inc files is included,
+// and there is no device global: every launch is self-contained.
 //
 // tsdf_map_place_kernel: one workgroup of 1024 threads (16 wave64) per batch position, a grid-stride loop over positions
 // when n exceeds the grid — the shape of tsdf_obb_kernel.  Per position:
 //   1. the source frame (the index, if any) and the header rule (uniform); a bad frame's depth is not read;
-//   2. one pass over the crop: wave <-> rows, lane <-> groups of four consecutive columns, one 16-byte load per group
-//      through a vector type DECLARED 4-byte aligned, the W mod 4 last columns one by one.  A row narrower than 129
-//      columns needs 32 lanes or fewer, so a wave then takes 2, 4, 8 or 16 rows at a time (the pass is bound by its
-//      float64 arithmetic: idle lanes are lost time).  Per valid pixel the IEEE
-//      division by the focal length (the compiler's sequence: exact for every F), the back-projection, the three fused
+//   2. one pass over the crop (place.inc::place_crop): wave <-> rows, lane <-> groups of four consecutive columns, one
+//      16-byte load per group through a vector type DECLARED 4-byte aligned, the W mod 4 last columns one by one.  A
+//      row narrower than 129 columns needs 32 lanes or fewer, so a wave then takes 2, 4, 8 or 16 rows at a time (the
+//      pass is bound by its float64 arithmetic: idle lanes are lost time).  Per valid pixel the IEEE division by the
+//      focal length (the compiler's sequence: exact for every F), the back-projection, the three fused
 //      rows of the forward map, three roundings to float32 and six running extremes per lane;
 //   3. a butterfly over the wave, the wave extremes through LDS, and thread 0 takes the 16 of them, runs the float32 glue
-//      and the degenerate rule and writes the row, max_l, mid_p and the status with plain stores.
+//      and the degenerate rule (place.inc::place_glue) and writes the row, max_l, mid_p and the status with plain stores.
 // Minimum and maximum are order-free, so any split of the pixels gives the same bits.  No atomics, no communication
 // between workgroups, two barriers per position (the second keeps the next position's wave extremes out of s_red while
 // thread 0 still reads it).
@@ -50,13 +51,13 @@ namespace {
 #include "device.inc"   // check_device, launched, misaligned: the host preamble of every library here
 #include "prim.inc"     // kDefaultCam, trunc_i32, finite32, header_ok
 #include "slab.inc"     // workgroup <-> slab, the frame's header and grid row, zero-fill, host sizing
-#include "narrow.inc"   // narrow2, store_vol, Piece: the 2-byte store side
+#include "narrow.inc"   // narrow2, store_vol, Piece, bad_dtype: the 2-byte store side
+#include "place.inc"    // place_crop, place_glue, Placed: the placement's arithmetic, shared with tsdf_mapstep.hip
 
 constexpr int kPlaceWG = 1024;               // threads per workgroup of the placement
 constexpr int kPlaceWaves = kPlaceWG / 64;   // 16 wave64
 constexpr int kPlaceMaxBlocks = 1 << 16;     // positions beyond the grid are reached by the grid-stride loop
 
-typedef float map_f4 __attribute__((ext_vector_type(4), aligned(4)));   // 16 bytes on a 4-byte boundary
 typedef double map_d4 __attribute__((ext_vector_type(4)));
 
 struct PlaceArgs {
@@ -76,54 +77,16 @@ struct PlaceArgs {
   int32_t *status;          // [n] or null
 };
 
-// the running extremes of one lane: a NaN moves neither (the oracle's "v < mn", "v > mx")
-struct Ext6 {
-  float mn0, mn1, mn2, mx0, mx1, mx2;
-};
-
-__device__ __forceinline__ void place_pixel(float d, int col, double yc, double F, double cx, float eps,
-                                            const double (&m)[12], Ext6 &e, int &any) {
-  if (!(__builtin_fabsf(d) >= eps)) return;   // NaN is invalid
-  const double d64 = (double)d;
-  const double q = d64 / F;                   // IEEE division
-  const double px = q * ((double)col - cx);
-  const double py = (-q) * yc;
-  const double pz = -d64;
-  const float o0 = (float)__builtin_fma(m[0], px, __builtin_fma(m[1], py, __builtin_fma(m[2], pz, m[3])));
-  const float o1 = (float)__builtin_fma(m[4], px, __builtin_fma(m[5], py, __builtin_fma(m[6], pz, m[7])));
-  const float o2 = (float)__builtin_fma(m[8], px, __builtin_fma(m[9], py, __builtin_fma(m[10], pz, m[11])));
-  e.mn0 = o0 < e.mn0 ? o0 : e.mn0;
-  e.mn1 = o1 < e.mn1 ? o1 : e.mn1;
-  e.mn2 = o2 < e.mn2 ? o2 : e.mn2;
-  e.mx0 = o0 > e.mx0 ? o0 : e.mx0;
-  e.mx1 = o1 > e.mx1 ? o1 : e.mx1;
-  e.mx2 = o2 > e.mx2 ? o2 : e.mx2;
-  any = 1;
-}
-
-// the extremes held by the lanes of a wave are never NaN: fminf / fmaxf are the plain minimum and maximum
-__device__ __forceinline__ float wave_min(float v) {
-#pragma unroll
-  for (int k = 32; k >= 1; k >>= 1) v = __builtin_fminf(v, __shfl_xor(v, k, 64));
-  return v;
-}
-__device__ __forceinline__ float wave_max(float v) {
-#pragma unroll
-  for (int k = 32; k >= 1; k >>= 1) v = __builtin_fmaxf(v, __shfl_xor(v, k, 64));
-  return v;
-}
-
-// what thread 0 writes for one position; a row that is not OK is all zero
-__device__ __forceinline__ void place_write(const PlaceArgs &a, int64_t i, float ox, float oy, float oz, float vl, float td,
-                                            float max_l, float m0, float m1, float m2, int status) {
+// what thread 0 writes for one position
+__device__ __forceinline__ void place_write(const PlaceArgs &a, int64_t i, const Placed &p) {
   float *g = a.grid + 8 * i;
-  g[0] = ox, g[1] = oy, g[2] = oz, g[3] = vl, g[4] = td, g[5] = 0.f, g[6] = 0.f, g[7] = 0.f;
-  if (a.max_l) a.max_l[i] = max_l;
+  g[0] = p.ox, g[1] = p.oy, g[2] = p.oz, g[3] = p.vl, g[4] = p.td, g[5] = 0.f, g[6] = 0.f, g[7] = 0.f;
+  if (a.max_l) a.max_l[i] = p.max_l;
   if (a.mid_p) {
-    float *p = a.mid_p + 3 * i;
-    p[0] = m0, p[1] = m1, p[2] = m2;
+    float *m = a.mid_p + 3 * i;
+    m[0] = p.m0, m[1] = p.m1, m[2] = p.m2;
   }
-  if (a.status) a.status[i] = status;
+  if (a.status) a.status[i] = p.status;
 }
 
 __global__ __launch_bounds__(kPlaceWG) void tsdf_map_place_kernel(PlaceArgs a) {
@@ -133,7 +96,6 @@ __global__ __launch_bounds__(kPlaceWG) void tsdf_map_place_kernel(PlaceArgs a) {
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const double F = a.focal, cx = a.cx, cy = a.cy;
   const float eps = a.eps;
-  const float inf = __builtin_inff();
 
   for (int64_t i = blockIdx.x; i < a.n; i += gridDim.x) {
     // the source frame; outside the tables it is a bad header and nothing of it is read
@@ -149,7 +111,7 @@ __global__ __launch_bounds__(kPlaceWG) void tsdf_map_place_kernel(PlaceArgs a) {
       ok = header_ok(left, top, right, bottom, off0, off1, depth_len);
     }
     if (!ok) {
-      if (tid == 0) place_write(a, i, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, TSDF_FRAME_BAD_HEADER);
+      if (tid == 0) place_write(a, i, place_none(TSDF_FRAME_BAD_HEADER));
       continue;
     }
     const int bw = right - left, bh = bottom - top;   // header_ok: both are positive ints
@@ -158,80 +120,9 @@ __global__ __launch_bounds__(kPlaceWG) void tsdf_map_place_kernel(PlaceArgs a) {
 #pragma unroll
     for (int k = 0; k < 12; ++k) m[k] = a.xforms[24 * i + k];
 
-    Ext6 e = {inf, inf, inf, -inf, -inf, -inf};
-    int any = 0;
-    const int ngrp = bw >> 2, tail0 = ngrp << 2, ntail = bw - tail0;
-    // gl lanes per row: the smallest power of two that holds the row's groups (4..64), so a wave takes 64 / gl rows at
-    // a time and a crop of 130 columns keeps all 64 lanes busy, not 32 (uniform)
-    int sh = 6;
-    while (sh > 2 && (1 << (sh - 1)) >= ngrp) --sh;
-    const int gl = 1 << sh, rpw = 64 >> sh;
-    const int sub = lane >> sh, gq = lane & (gl - 1);
-    for (int r = wave * rpw + sub; r < bh; r += kPlaceWaves * rpw) {
-      const float *__restrict__ row = d + (int64_t)r * bw;
-      const double yc = (double)(top + r) - cy;
-      for (int q = gq; q < ngrp; q += gl) {
-        const map_f4 v = *reinterpret_cast<const map_f4 *>(row + 4 * q);
-        const int c0 = left + 4 * q;
-        place_pixel(v.x, c0, yc, F, cx, eps, m, e, any);
-        place_pixel(v.y, c0 + 1, yc, F, cx, eps, m, e, any);
-        place_pixel(v.z, c0 + 2, yc, F, cx, eps, m, e, any);
-        place_pixel(v.w, c0 + 3, yc, F, cx, eps, m, e, any);
-      }
-      if (gq < ntail) place_pixel(row[tail0 + gq], left + tail0 + gq, yc, F, cx, eps, m, e, any);
-    }
-    {
-      const float w0 = wave_min(e.mn0), w1 = wave_min(e.mn1), w2 = wave_min(e.mn2);
-      const float w3 = wave_max(e.mx0), w4 = wave_max(e.mx1), w5 = wave_max(e.mx2);
-      const float w6 = wave_max((float)any);
-      if (lane == 0) {
-        s_red[wave][0] = w0, s_red[wave][1] = w1, s_red[wave][2] = w2;
-        s_red[wave][3] = w3, s_red[wave][4] = w4, s_red[wave][5] = w5;
-        s_red[wave][6] = w6;
-      }
-    }
+    place_crop<kPlaceWaves>(d, left, top, bw, bh, F, cx, cy, eps, m, lane, wave, s_red);
     __syncthreads();
-    if (tid == 0) {
-      float mn0 = s_red[0][0], mn1 = s_red[0][1], mn2 = s_red[0][2];
-      float mx0 = s_red[0][3], mx1 = s_red[0][4], mx2 = s_red[0][5], anyf = s_red[0][6];
-#pragma unroll
-      for (int w = 1; w < kPlaceWaves; ++w) {
-        mn0 = __builtin_fminf(mn0, s_red[w][0]);
-        mn1 = __builtin_fminf(mn1, s_red[w][1]);
-        mn2 = __builtin_fminf(mn2, s_red[w][2]);
-        mx0 = __builtin_fmaxf(mx0, s_red[w][3]);
-        mx1 = __builtin_fmaxf(mx1, s_red[w][4]);
-        mx2 = __builtin_fmaxf(mx2, s_red[w][5]);
-        anyf = __builtin_fmaxf(anyf, s_red[w][6]);
-      }
-      if (!(anyf > 0.f)) {   // no valid pixel
-        place_write(a, i, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, TSDF_FRAME_DEGENERATE);
-      } else {
-        // the glue: float32, one rounding per operation, left to right
-        float mid0 = __fdiv_rn(__fadd_rn(mn0, mx0), 2.0f), len0 = __fsub_rn(mx0, mn0);
-        float mid1 = __fdiv_rn(__fadd_rn(mn1, mx1), 2.0f), len1 = __fsub_rn(mx1, mn1);
-        float mid2 = __fdiv_rn(__fadd_rn(mn2, mx2), 2.0f), len2 = __fsub_rn(mx2, mn2);
-        float max_l = len0;
-        if (len1 > max_l) max_l = len1;
-        if (len2 > max_l) max_l = len2;
-        float vl = __fdiv_rn(max_l, (float)a.R);
-        float td = __fmul_rn(vl, a.trunc_vox);
-        const float half_l = __fdiv_rn(max_l, 2.0f), half_v = __fdiv_rn(vl, 2.0f);
-        float ox = __fadd_rn(__fsub_rn(mid0, half_l), half_v);
-        float oy = __fadd_rn(__fsub_rn(mid1, half_l), half_v);
-        float oz = __fadd_rn(__fsub_rn(mid2, half_l), half_v);
-        // the degenerate rule: the extent positive and finite, the centre finite
-        const bool ext_ok = max_l > 0.f && finite32(max_l);
-        const bool mid_ok = finite32(mid0) && finite32(mid1) && finite32(mid2);
-        int status = TSDF_FRAME_OK;
-        if (!ext_ok || !mid_ok) {
-          status = TSDF_FRAME_DEGENERATE;
-          max_l = ox = oy = oz = vl = td = 0.f;
-          if (!mid_ok) mid0 = mid1 = mid2 = 0.f;   // a zero extent keeps its finite centre
-        }
-        place_write(a, i, ox, oy, oz, vl, td, max_l, mid0, mid1, mid2, status);
-      }
-    }
+    if (tid == 0) place_write(a, i, place_glue<kPlaceWaves>(s_red, a.R, a.trunc_vox));
     __syncthreads();   // the next position writes s_red: not before thread 0 has read this one's
   }
 }
@@ -415,8 +306,6 @@ __global__ __launch_bounds__(kSlabWG) void tsdf_map_grid_lowp_kernel(MapLowpArgs
     store_vol((GlobalOut)(out + 2 * R3 + e), o2);
   }
 }
-
-bool bad_dtype(int dtype) { return dtype != TSDF_LOWP_F16 && dtype != TSDF_LOWP_BF16; }
 
 template <int LAYOUT, bool BF16>
 void launch_grid(const MapLowpArgs &a, int64_t blocks, hipStream_t s) {

@@ -5,10 +5,11 @@
 // takes the status codes from include/tsdf.h, the host preamble every library here has from device.inc, the
 // device primitives from prim.inc and the augmentation's draw and map arithmetic from augdraw.inc, which it includes
 // UNCHANGED: aug_draw_row writes its row through a generic pointer, and here that pointer is a row in LDS, so the
-// draw exists once for the three libraries that use it.  The placement's crop pass and glue (tsdf_maplowp.hip::
-// tsdf_map_place_kernel), the joints' map (tsdf_auggrid.hip::tsdf_transform_joints_kernel) and the label normalisation
-// (kernels.inc::tsdf_normalize_kernel) are RESTATED here operation for operation; there is no device global: every launch
-// is self-contained.
+// draw exists once for the three libraries that use it.  The placement's crop pass, wave butterfly, glue and degenerate
+// rule come from place.inc, the text tsdf_maplowp.hip::tsdf_map_place_kernel runs: the head's placement equals that
+// kernel's bit for bit because it is the same arithmetic, written once.  The joints' map (tsdf_auggrid.hip::
+// tsdf_transform_joints_kernel) and the label normalisation (kernels.inc::tsdf_normalize_kernel) are RESTATED here
+// operation for operation; there is no device global: every launch is self-contained.
 //
 // tsdf_compose_kernel: one lane per map, 256-thread workgroups, no LDS.  The two halves one after the other (a half is 24
 // doubles in, 12 out), every row as 16-byte accesses on its 8-byte boundary; the 192-byte result leaves as twelve 16-byte
@@ -19,7 +20,8 @@
 //   1. thread 0 draws U into LDS (aug_draw_row), composes it with the source frame's base row when there is one, and
 //      leaves T's 24 doubles in LDS and in global memory; meanwhile every lane resolves the source frame and its header;
 //   2. a barrier, then every lane takes T's forward rows from LDS;
-//   3. the placement's crop pass, its wave butterfly and its glue (thread 0), which also publishes max_l and mid_p in LDS;
+//   3. the placement's crop pass and wave butterfly (place.inc::place_crop), a barrier, and its glue (place_glue, thread
+//      0), which also publishes max_l and mid_p in LDS;
 //   4. a barrier, then lanes 0..J-1 map one joint of the source frame each and normalise it.
 // No atomics, no communication between workgroups, at most four barriers per position, all under uniform conditions.
 // Without d_out_grid there is nothing for a workgroup to do: tsdf_map_step_draw_kernel is step 1 alone, one lane per
@@ -39,12 +41,11 @@ namespace {
 #include "device.inc"    // check_device, launched, misaligned: the host preamble of every library here
 #include "prim.inc"      // cam_ok, finite32, header_ok
 #include "augdraw.inc"   // kAugWG, aug_d2, aug_store, aug_draw_row: shared with tsdf_augment.hip and tsdf_augstep.hip
+#include "place.inc"     // place_crop, place_glue, Placed: the placement's arithmetic, shared with tsdf_maplowp.hip
 
 constexpr int kHeadWG = 1024;              // threads per workgroup of the head
 constexpr int kHeadWaves = kHeadWG / 64;   // 16 wave64
 constexpr int kHeadMaxBlocks = 1 << 16;    // positions beyond the grid are reached by the grid-stride loop
-
-typedef float head_f4 __attribute__((ext_vector_type(4), aligned(4)));   // 16 bytes on a 4-byte boundary
 
 // One half of a composition: rows (A | b) of P after Q, every product and every sum rounded on its own.
 __device__ __forceinline__ void compose_half(const double (&P)[12], const double (&Q)[12], double (&o)[12]) {
@@ -153,56 +154,17 @@ __global__ __launch_bounds__(kAugWG) void tsdf_map_step_draw_kernel(HeadArgs a) 
   }
 }
 
-// the running extremes of one lane: a NaN moves neither (the oracle's "v < mn", "v > mx")
-struct Ext6 {
-  float mn0, mn1, mn2, mx0, mx1, mx2;
-};
-
-// tsdf_map_place_kernel's place_pixel
-__device__ __forceinline__ void place_pixel(float d, int col, double yc, double F, double cx, float eps,
-                                            const double (&m)[12], Ext6 &e, int &any) {
-  if (!(__builtin_fabsf(d) >= eps)) return;   // NaN is invalid
-  const double d64 = (double)d;
-  const double q = d64 / F;                   // IEEE division
-  const double px = q * ((double)col - cx);
-  const double py = (-q) * yc;
-  const double pz = -d64;
-  const float o0 = (float)__builtin_fma(m[0], px, __builtin_fma(m[1], py, __builtin_fma(m[2], pz, m[3])));
-  const float o1 = (float)__builtin_fma(m[4], px, __builtin_fma(m[5], py, __builtin_fma(m[6], pz, m[7])));
-  const float o2 = (float)__builtin_fma(m[8], px, __builtin_fma(m[9], py, __builtin_fma(m[10], pz, m[11])));
-  e.mn0 = o0 < e.mn0 ? o0 : e.mn0;
-  e.mn1 = o1 < e.mn1 ? o1 : e.mn1;
-  e.mn2 = o2 < e.mn2 ? o2 : e.mn2;
-  e.mx0 = o0 > e.mx0 ? o0 : e.mx0;
-  e.mx1 = o1 > e.mx1 ? o1 : e.mx1;
-  e.mx2 = o2 > e.mx2 ? o2 : e.mx2;
-  any = 1;
-}
-
-// the extremes held by the lanes of a wave are never NaN: fminf / fmaxf are the plain minimum and maximum
-__device__ __forceinline__ float wave_min(float v) {
-#pragma unroll
-  for (int k = 32; k >= 1; k >>= 1) v = __builtin_fminf(v, __shfl_xor(v, k, 64));
-  return v;
-}
-__device__ __forceinline__ float wave_max(float v) {
-#pragma unroll
-  for (int k = 32; k >= 1; k >>= 1) v = __builtin_fmaxf(v, __shfl_xor(v, k, 64));
-  return v;
-}
-
-// what thread 0 writes for one position (a row that is not OK is all zero), and what the labels read: s_pl = max_l, mid_p
-__device__ __forceinline__ void place_write(const HeadArgs &a, int64_t i, float (&s_pl)[4], float ox, float oy, float oz,
-                                            float vl, float td, float max_l, float m0, float m1, float m2, int status) {
+// what thread 0 writes for one position, and what the labels read: s_pl = max_l, mid_p
+__device__ __forceinline__ void place_write(const HeadArgs &a, int64_t i, float (&s_pl)[4], const Placed &p) {
   float *g = a.grid + 8 * i;
-  g[0] = ox, g[1] = oy, g[2] = oz, g[3] = vl, g[4] = td, g[5] = 0.f, g[6] = 0.f, g[7] = 0.f;
-  if (a.max_l) a.max_l[i] = max_l;
+  g[0] = p.ox, g[1] = p.oy, g[2] = p.oz, g[3] = p.vl, g[4] = p.td, g[5] = 0.f, g[6] = 0.f, g[7] = 0.f;
+  if (a.max_l) a.max_l[i] = p.max_l;
   if (a.mid_p) {
-    float *p = a.mid_p + 3 * i;
-    p[0] = m0, p[1] = m1, p[2] = m2;
+    float *m = a.mid_p + 3 * i;
+    m[0] = p.m0, m[1] = p.m1, m[2] = p.m2;
   }
-  if (a.status) a.status[i] = status;
-  s_pl[0] = max_l, s_pl[1] = m0, s_pl[2] = m1, s_pl[3] = m2;
+  if (a.status) a.status[i] = p.status;
+  s_pl[0] = p.max_l, s_pl[1] = p.m0, s_pl[2] = p.m1, s_pl[3] = p.m2;
 }
 
 __global__ __launch_bounds__(kHeadWG) void tsdf_map_step_head_kernel(HeadArgs a) {
@@ -214,7 +176,6 @@ __global__ __launch_bounds__(kHeadWG) void tsdf_map_step_head_kernel(HeadArgs a)
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const double F = a.focal, cx = a.cx, cy = a.cy;
   const float eps = a.eps;
-  const float inf = __builtin_inff();
 
   for (int64_t i = blockIdx.x; i < a.n; i += gridDim.x) {
     // the source frame; outside the tables the draw is the identity, the base is not read and the header is bad
@@ -243,7 +204,7 @@ __global__ __launch_bounds__(kHeadWG) void tsdf_map_step_head_kernel(HeadArgs a)
     __syncthreads();   // T is in s_T
 
     if (!ok) {         // (uniform) the depth is not read
-      if (tid == 0) place_write(a, i, s_pl, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, TSDF_FRAME_BAD_HEADER);
+      if (tid == 0) place_write(a, i, s_pl, place_none(TSDF_FRAME_BAD_HEADER));
     } else {
       const int bw = right - left, bh = bottom - top;   // header_ok: both are positive ints
       const float *__restrict__ d = a.depth + off0;
@@ -251,80 +212,9 @@ __global__ __launch_bounds__(kHeadWG) void tsdf_map_step_head_kernel(HeadArgs a)
 #pragma unroll
       for (int k = 0; k < 12; ++k) m[k] = s_T[k];
 
-      Ext6 e = {inf, inf, inf, -inf, -inf, -inf};
-      int any = 0;
-      const int ngrp = bw >> 2, tail0 = ngrp << 2, ntail = bw - tail0;
-      // gl lanes per row: the smallest power of two that holds the row's groups (4..64), so a wave takes 64 / gl rows
-      // at a time (uniform)
-      int sh = 6;
-      while (sh > 2 && (1 << (sh - 1)) >= ngrp) --sh;
-      const int gl = 1 << sh, rpw = 64 >> sh;
-      const int sub = lane >> sh, gq = lane & (gl - 1);
-      for (int r = wave * rpw + sub; r < bh; r += kHeadWaves * rpw) {
-        const float *__restrict__ row = d + (int64_t)r * bw;
-        const double yc = (double)(top + r) - cy;
-        for (int q = gq; q < ngrp; q += gl) {
-          const head_f4 v = *reinterpret_cast<const head_f4 *>(row + 4 * q);
-          const int c0 = left + 4 * q;
-          place_pixel(v.x, c0, yc, F, cx, eps, m, e, any);
-          place_pixel(v.y, c0 + 1, yc, F, cx, eps, m, e, any);
-          place_pixel(v.z, c0 + 2, yc, F, cx, eps, m, e, any);
-          place_pixel(v.w, c0 + 3, yc, F, cx, eps, m, e, any);
-        }
-        if (gq < ntail) place_pixel(row[tail0 + gq], left + tail0 + gq, yc, F, cx, eps, m, e, any);
-      }
-      {
-        const float w0 = wave_min(e.mn0), w1 = wave_min(e.mn1), w2 = wave_min(e.mn2);
-        const float w3 = wave_max(e.mx0), w4 = wave_max(e.mx1), w5 = wave_max(e.mx2);
-        const float w6 = wave_max((float)any);
-        if (lane == 0) {
-          s_red[wave][0] = w0, s_red[wave][1] = w1, s_red[wave][2] = w2;
-          s_red[wave][3] = w3, s_red[wave][4] = w4, s_red[wave][5] = w5;
-          s_red[wave][6] = w6;
-        }
-      }
+      place_crop<kHeadWaves>(d, left, top, bw, bh, F, cx, cy, eps, m, lane, wave, s_red);
       __syncthreads();
-      if (tid == 0) {
-        float mn0 = s_red[0][0], mn1 = s_red[0][1], mn2 = s_red[0][2];
-        float mx0 = s_red[0][3], mx1 = s_red[0][4], mx2 = s_red[0][5], anyf = s_red[0][6];
-#pragma unroll
-        for (int w = 1; w < kHeadWaves; ++w) {
-          mn0 = __builtin_fminf(mn0, s_red[w][0]);
-          mn1 = __builtin_fminf(mn1, s_red[w][1]);
-          mn2 = __builtin_fminf(mn2, s_red[w][2]);
-          mx0 = __builtin_fmaxf(mx0, s_red[w][3]);
-          mx1 = __builtin_fmaxf(mx1, s_red[w][4]);
-          mx2 = __builtin_fmaxf(mx2, s_red[w][5]);
-          anyf = __builtin_fmaxf(anyf, s_red[w][6]);
-        }
-        if (!(anyf > 0.f)) {   // no valid pixel
-          place_write(a, i, s_pl, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, TSDF_FRAME_DEGENERATE);
-        } else {
-          // the glue: float32, one rounding per operation, left to right
-          float mid0 = __fdiv_rn(__fadd_rn(mn0, mx0), 2.0f), len0 = __fsub_rn(mx0, mn0);
-          float mid1 = __fdiv_rn(__fadd_rn(mn1, mx1), 2.0f), len1 = __fsub_rn(mx1, mn1);
-          float mid2 = __fdiv_rn(__fadd_rn(mn2, mx2), 2.0f), len2 = __fsub_rn(mx2, mn2);
-          float max_l = len0;
-          if (len1 > max_l) max_l = len1;
-          if (len2 > max_l) max_l = len2;
-          float vl = __fdiv_rn(max_l, (float)a.R);
-          float td = __fmul_rn(vl, a.trunc_vox);
-          const float half_l = __fdiv_rn(max_l, 2.0f), half_v = __fdiv_rn(vl, 2.0f);
-          float ox = __fadd_rn(__fsub_rn(mid0, half_l), half_v);
-          float oy = __fadd_rn(__fsub_rn(mid1, half_l), half_v);
-          float oz = __fadd_rn(__fsub_rn(mid2, half_l), half_v);
-          // the degenerate rule: the extent positive and finite, the centre finite
-          const bool ext_ok = max_l > 0.f && finite32(max_l);
-          const bool mid_ok = finite32(mid0) && finite32(mid1) && finite32(mid2);
-          int status = TSDF_FRAME_OK;
-          if (!ext_ok || !mid_ok) {
-            status = TSDF_FRAME_DEGENERATE;
-            max_l = ox = oy = oz = vl = td = 0.f;
-            if (!mid_ok) mid0 = mid1 = mid2 = 0.f;   // a zero extent keeps its finite centre
-          }
-          place_write(a, i, s_pl, ox, oy, oz, vl, td, max_l, mid0, mid1, mid2, status);
-        }
-      }
+      if (tid == 0) place_write(a, i, s_pl, place_glue<kHeadWaves>(s_red, a.R, a.trunc_vox));
     }
 
     if (a.gt) {          // (uniform)
@@ -356,8 +246,6 @@ __global__ __launch_bounds__(kHeadWG) void tsdf_map_step_head_kernel(HeadArgs a)
     __syncthreads();   // the next position writes s_T, s_red and s_pl: not before this one's readers are done
   }
 }
-
-bool bad_res(int R) { return R < 4 || R > 128 || R % 4 != 0; }
 
 }  // namespace
 

@@ -1,21 +1,28 @@
-"""CPU tier of the extension table (_lib._EXTS): every row binds exactly what its header declares, with the types
-declared — an entry added to a header without a row of argtypes would otherwise load with ctypes' defaults, int arguments
-and all —, every loader hands out one library object, and a library of another version or none at all is an ImportError
-that says what to do.  Nothing here touches a GPU."""
+"""CPU tier of the extension table (_lib._EXTS), and the only place that pins it: the table is csrc/Makefile's EXTS, every
+row binds exactly what its header declares and its binary exports, with the types declared — an entry added to a header
+without a row of argtypes would otherwise load with ctypes' defaults, int arguments and all —, every loader hands out one
+library object, and a library of another version or none at all is an ImportError that says what to do.  What is specific
+to one library (its literal names and argument types, its refusals) is in that library's own file.  Nothing here touches
+a GPU."""
 import ctypes
 import os
+import re
 
 import pytest
-from abi_util import declared_functions
+from abi_util import declared_functions, exported
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-EXTS = ["augment", "augstep", "auggrid", "depth16", "obb", "lowp"]   # csrc/Makefile's EXTS, in its order
+# csrc/Makefile's EXTS, in its order: a new library is a name here, a name there and a row in _lib._EXTS
+EXTS = ["augment", "augstep", "auggrid", "depth16", "obb", "lowp", "maplowp", "mapstep", "locate"]
 
 
 def test_the_table_has_a_row_and_a_loader_per_extension(pkg):
     assert list(pkg._lib._EXTS) == EXTS
+    makefile = open(os.path.join(ROOT, "handposeestimation-with-3d-cnns_amd", "csrc", "Makefile")).read()
+    assert re.search(r"^EXTS := (.*)$", makefile, flags=re.M).group(1).split() == EXTS
     for name in EXTS:
         ext = pkg._lib._EXTS[name]
+        assert isinstance(ext, pkg._lib._Ext)
         assert ext.path == getattr(pkg._lib, name.upper() + "_LIB_PATH")
         assert ext.version == getattr(pkg._lib, name.upper() + "_VERSION")
 
@@ -23,7 +30,10 @@ def test_the_table_has_a_row_and_a_loader_per_extension(pkg):
 @pytest.mark.parametrize("name", EXTS)
 def test_row_binds_exactly_its_header_with_types(pkg, name):
     ext = pkg._lib._EXTS[name]
-    assert sorted([ext.version_symbol, *ext.entries]) == declared_functions(f"tsdf_{name}.h")
+    want = sorted([ext.version_symbol, *ext.entries])
+    assert want == declared_functions(f"tsdf_{name}.h")
+    funcs, named = exported(ext.path)
+    assert funcs == want and named == want
     L = getattr(pkg._lib, "load_" + name)()
     assert getattr(L, ext.version_symbol)() == ext.version
     for entry in (ext.version_symbol, *ext.entries):
@@ -39,6 +49,7 @@ def test_loading_twice_gives_the_same_object(pkg, name):
     load = getattr(pkg._lib, "load_" + name)
     assert load() is load()
     assert load() is not pkg._lib.load()
+    assert all(load() is not getattr(pkg._lib, "load_" + other)() for other in EXTS if other != name)
 
 
 @pytest.mark.parametrize("name", EXTS)

@@ -1,5 +1,5 @@
 """CPU tier of the hand locator (include/tsdf_locate.h): libtsdf_locate.so as far as it goes without a GPU — the build rule
-and its resource report, the binding through _lib._EXTS_OPEN, the version, every argument check before device work —, the
+and its resource report, the binding through _lib._EXTS, the version, every argument check before device work —, the
 public names and their refusals, and the reference the GPU tier compares against (tests/locate_ref.py): the margin
 condition on every input the GPU tier compares exactly, the round trip, the capacity bound, refine = 0, the cube row.
 Nothing here touches a GPU."""
@@ -48,7 +48,7 @@ def test_make_rules_cross_compile_for_gfx950_without_scratch():
 
 # ---- binding ----
 def test_row_binds_exactly_its_header_with_types(pkg):
-    ext = pkg._lib._EXTS_OPEN["locate"]
+    ext = pkg._lib._EXTS["locate"]
     assert isinstance(ext, pkg._lib._Ext)
     assert declared_functions("tsdf_locate.h") == WANT == sorted([ext.version_symbol, *ext.entries])
     funcs, named = exported(pkg._lib.LOCATE_LIB_PATH)
@@ -72,24 +72,8 @@ def test_row_binds_exactly_its_header_with_types(pkg):
     assert "tsdf_cam" not in text
     assert (pkg._lib.TSDF_LOCATE_F32, pkg._lib.TSDF_LOCATE_U16) == (0, 1)
     assert "#define TSDF_LOCATE_F32 0" in text and "#define TSDF_LOCATE_U16 1" in text
-    # the pinned tables keep their rows, no name is in two tables, and the product beside them is what it was
-    assert list(pkg._lib._EXTS) == ["augment", "augstep", "auggrid", "depth16", "obb", "lowp"]
-    assert list(pkg._lib._EXTS_MORE) == ["maplowp"]
-    assert "mapstep" in pkg._lib._EXTS_OPEN
-    assert not (set(pkg._lib._EXTS) | set(pkg._lib._EXTS_MORE)) & set(pkg._lib._EXTS_OPEN)
+    # the product beside it is what it was
     assert pkg._lib.load().tsdf_version() == 7
-
-
-def test_wrong_version_and_missing_library_raise_import_error(pkg, monkeypatch):
-    row = pkg._lib._EXTS_OPEN["locate"]
-    monkeypatch.delitem(pkg._lib._ext_libs, "locate", raising=False)
-    monkeypatch.setitem(pkg._lib._EXTS_OPEN, "locate", row._replace(version=row.version + 1))
-    with pytest.raises(ImportError, match="version 1"):
-        pkg._lib.load_locate()
-    monkeypatch.setitem(pkg._lib._EXTS_OPEN, "locate",
-                        row._replace(path=os.path.join(ROOT, "build", "no_such_libtsdf_locate.so")))
-    with pytest.raises(ImportError, match="csrc locate"):
-        pkg._lib.load_locate()
 
 
 # ---- argument checks ----

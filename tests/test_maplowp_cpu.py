@@ -1,5 +1,5 @@
 """CPU tier of the mapped low-precision volumes (include/tsdf_maplowp.h): libtsdf_maplowp.so as far as it goes without a
-GPU — the build rule, the binding through _lib._EXTS_MORE, the version, the argument checks before device work —, the
+GPU — the build rule, the binding through _lib._EXTS, the version, the argument checks before device work —, the
 public names and refusals, and the proof that the inputs of the GPU tier's volume tests are not trivial.  Nothing here
 touches a GPU."""
 import ctypes
@@ -35,8 +35,7 @@ def test_make_rules_cross_compile_for_gfx950_without_scratch():
 
 # ---- binding ----
 def test_row_binds_exactly_its_header_with_types(pkg):
-    assert list(pkg._lib._EXTS_MORE) == ["maplowp"]
-    ext = pkg._lib._EXTS_MORE["maplowp"]
+    ext = pkg._lib._EXTS["maplowp"]
     assert isinstance(ext, pkg._lib._Ext)
     assert declared_functions("tsdf_maplowp.h") == WANT == sorted([ext.version_symbol, *ext.entries])
     funcs, named = exported(pkg._lib.MAPLOWP_LIB_PATH)
@@ -55,22 +54,8 @@ def test_row_binds_exactly_its_header_with_types(pkg):
     for name, args in ext.entries.items():
         assert list(getattr(L, name).argtypes) == args and args
     assert pkg._lib.load_maplowp() is L and L is not pkg._lib.load() and L is not pkg._lib.load_lowp()
-    # the first table still holds its six rows, no name is in both, and the product beside them is what it was
-    assert list(pkg._lib._EXTS) == ["augment", "augstep", "auggrid", "depth16", "obb", "lowp"]
-    assert not set(pkg._lib._EXTS) & set(pkg._lib._EXTS_MORE)
+    # the product beside it is what it was
     assert pkg._lib.load().tsdf_version() == 7
-
-
-def test_wrong_version_and_missing_library_raise_import_error(pkg, monkeypatch):
-    row = pkg._lib._EXTS_MORE["maplowp"]
-    monkeypatch.delitem(pkg._lib._ext_libs, "maplowp", raising=False)
-    monkeypatch.setitem(pkg._lib._EXTS_MORE, "maplowp", row._replace(version=row.version + 1))
-    with pytest.raises(ImportError, match="version 1"):
-        pkg._lib.load_maplowp()
-    monkeypatch.setitem(pkg._lib._EXTS_MORE, "maplowp",
-                        row._replace(path=os.path.join(ROOT, "build", "no_such_libtsdf_maplowp.so")))
-    with pytest.raises(ImportError, match="csrc maplowp"):
-        pkg._lib.load_maplowp()
 
 
 # ---- argument checks ----

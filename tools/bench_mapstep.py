@@ -23,9 +23,12 @@ not have yet are left out, so the tool measures the yardstick on an older tree.
 
 Method: device events around --iters back-to-back steps (at least 50); the legs of a shape take turns for --rounds
 rounds and the median round is reported with min and max, so a drift of the machine meets all alike.  No threshold is
-applied: the ratios to the yardstick are printed next to the spread of the yardstick's own rounds.
+applied: the ratios to the yardstick are printed next to the spread of the yardstick's own rounds.  ``--lib`` names
+another build of libtsdf_mapstep.so and ``--maplowp-lib`` one of libtsdf_maplowp.so, whose placement the chained legs and
+`place` launch (an A/B against the parent commit's: one process per build, taking turns).
 
-    python tools/bench_mapstep.py [--iters 100] [--warmup 20] [--rounds 5] [--dtype bfloat16] [--out x.json]
+    python tools/bench_mapstep.py [--iters 100] [--warmup 20] [--rounds 5] [--dtype bfloat16] [--lib x.so]
+                                  [--maplowp-lib y.so] [--out x.json]
 """
 from __future__ import annotations
 
@@ -83,10 +86,16 @@ def main():
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--dtype", choices=("bfloat16", "float16"), default="bfloat16")
+    ap.add_argument("--lib")
+    ap.add_argument("--maplowp-lib")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "mapstep", "bench_mapstep.json"))
     a = ap.parse_args()
     assert a.iters >= 50, "time at least 50 steps"
     assert torch.cuda.is_available(), "bench_mapstep.py needs a HIP device"
+    for name, path in (("mapstep", a.lib), ("maplowp", a.maplowp_lib)):
+        if path:
+            row = pkg._lib._EXTS[name]
+            pkg._lib._EXTS[name] = row._replace(path=os.path.abspath(path))
     dev = torch.device("cuda:0")
     dt = getattr(torch, a.dtype)
     have = hasattr(pkg, "map_step_head")
