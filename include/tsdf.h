@@ -181,8 +181,16 @@ int tsdf_voxelize_grid_hip(const float *d_depth, int64_t depth_len, const int64_
  * kernel).  Replaces what DataProcess.data_aug + tsdf_f were meant to do (pre/process.py:19-24,202-261)
  * but could not: data_aug raises AxisError on its own input, and where a variant of it runs
  * (cut_version/pre/process.py:69-134,207) the augmented cloud only moves the grid while the TSDF still
- * samples the un-augmented depth image.  This entry is therefore a RE-SPECIFICATION,
- * parity unpinned; its arithmetic contract is oracle/tsdf_oracle.c::tsdf_oracle_voxels_aug:
+ * samples the un-augmented depth image.  This entry is therefore a RE-SPECIFICATION:
+ * no reference output exists.  Its arithmetic contract is oracle/tsdf_oracle.c::tsdf_oracle_voxels_aug, and that
+ * contract — oracle and kernels alike — is pinned to two things (tests/map_geom_ref.py, test_map_geom_cpu.py,
+ * test_map_geom_gpu.py): (1) the geometric definition below, "the truncated distances are those between v' and T(w)",
+ * formed explicitly in extended precision, within 1e-5 in every voxel that is not within 2^-30 of a discontinuity,
+ * under a named family of affine T: turns of 90..180 degrees about each axis, an anisotropic scale, a shear, a
+ * reflection, a general affine map, the frame's own principal-axis map; (2) exact relations to the golden-backed plain
+ * path: T = s I with s a power of two gives the identity map's volume bit for bit (max_l, mid_p scaled exactly), a
+ * cyclic permutation of the axes gives its magnitudes with channels and grid axes permuted bit for bit, and the
+ * identity map is the plain path.
  *
  *   d_xforms  float64[n][24]  per frame: the forward affine map T(p) = A p + b as three rows
  *                             {A_i0, A_i1, A_i2, b_i}, then its inverse in the same form.

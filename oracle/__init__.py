@@ -163,7 +163,7 @@ def voxelize(depth, offsets, headers, R=32, layout=0, n_threads=1, want_tsdf=Tru
 
 
 def voxelize_aug(depth, offsets, headers, xforms, R=32, layout=0, n_threads=1, cam=None):
-    """Augmented form (re-specified, parity unpinned; see tsdf_oracle.c): xforms float64[n,24] =
+    """Augmented form (re-specified: no reference output; what pins it is listed in tsdf_oracle.c): xforms float64[n,24] =
     forward affine rows {A_i0,A_i1,A_i2,b_i} then the inverse.  Returns dict(tsdf,max_l,mid_p,status)."""
     depth = np.ascontiguousarray(depth, dtype=np.float32)
     offsets = np.ascontiguousarray(offsets, dtype=np.int64)

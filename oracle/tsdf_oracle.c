@@ -263,9 +263,17 @@ int tsdf_oracle_voxelize(const float *depth, const int64_t *offsets, const int32
  * Augmented form (BASELINE.json configs[4]).  The reference's data_aug
  * (pre/process.py:202-261) raises AxisError on its own input and, where it runs (cut_version), only
  * moves the grid while the TSDF still samples the un-augmented depth image (App. B#8-9), so there is
- * NO reference output to match: this is a re-specification, parity unpinned, checked by construction
- * (identity transform == plain path: grid, pixel map, zero mask, sign and z component bit for bit, x / y to the
- * float32 rounding) and against the HIP kernel.
+ * NO reference output to match: this is a re-specification.  What it is pinned to instead:
+ *   - the identity transform == the plain, golden-backed path: grid, pixel map, zero mask, sign and z component bit
+ *     for bit, x / y to the float32 rounding (tests/test_oracle_golden.py);
+ *   - the geometric definition — the distances between v' and T(w), with w and T(w) formed explicitly in extended
+ *     precision (tests/map_geom_ref.py) — within 1e-5 in every voxel not within 2^-30 of a discontinuity, under a
+ *     named family of maps: turns of 90..180 degrees about each axis, anisotropic scale, shear, reflection, a general
+ *     affine map, the frame's own principal-axis map, on both layouts and two cameras (tests/test_map_geom_cpu.py; the
+ *     kernels against the same reference: tests/test_map_geom_gpu.py).  A transposed A, forward rows where the inverse
+ *     rows belong, a dropped b or a sign from the wrong axis all pass the identity and fail there;
+ *   - exact relations to the identity volume: T = s I, s a power of two, gives it bit for bit with max_l / mid_p scaled
+ *     exactly; a cyclic permutation of the axes gives its magnitudes with channels and grid axes permuted, bit for bit.
  *
  * xf = double[24] per frame: forward affine T(p) = A p + b as rows {A_i0, A_i1, A_i2, b_i} (12 values),
  * then its inverse in the same form (12 values).  Every product/sum below is a separately rounded
