@@ -37,6 +37,9 @@ Augmentation in a base (OBB) frame:      compose_xforms (two per-frame maps as o
 Raw frames without a bounding box:       locate_hands (the nearest object's centre of mass, a fixed cube about it, the crops
                                          packed as depth / offsets / headers: libtsdf_locate.so, include/tsdf_locate.h),
                                          voxelize_frames (placement="aabb" | "cube")
+The accurate directional TSDF:           voxelize_grid_accurate (per voxel the nearest surface point among ALL valid pixels:
+                                         libtsdf_accurate.so, include/tsdf_accurate.h), voxelize_accurate,
+                                         voxelize_frames(tsdf="accurate"), export.preprocess_tree(tsdf="accurate")
 """
 from . import _lib  # noqa: F401
 from ._lib import TsdfCam, TsdfError, default_cam  # noqa: F401
@@ -48,7 +51,7 @@ from .voxelize import (AabbBatch, AugmentedStep, CloudGridBatch, MapGridBatch, O
                        voxelize, voxelize_aug, voxelize_grid, voxelize_indexed, voxelize_labels, widen_depth16,
                        invert_xforms, obb_xforms, voxelize_obb, narrow_volumes, voxelize_grid_lowp, voxelize_lowp,
                        map_grids, voxelize_aug_lowp, voxelize_map_grid_lowp, MapStepBatch, compose_xforms, map_step_head,
-                       HandCrops, locate_hands, voxelize_frames)
+                       HandCrops, locate_hands, voxelize_frames, voxelize_accurate, voxelize_grid_accurate)
 from .pca import JointPCA, fit_joint_pca  # noqa: F401
 from . import augment, dataset, export, packing, pca, shard, synth  # noqa: F401
 from .dataset import MSRA_Dataset, MSRADepthDataset, ResidentLoader, VoxelBatch, VoxelLoader  # noqa: F401
@@ -65,4 +68,4 @@ __all__ = ["voxelize", "voxelize_labels", "voxelize_indexed", "ResidentLoader", 
            "ProcessAugBatch", "widen_depth16", "obb_xforms", "voxelize_obb", "invert_xforms", "ObbBatch",
            "voxelize_grid_lowp", "voxelize_lowp", "narrow_volumes", "map_grids", "MapGridBatch", "voxelize_map_grid_lowp",
            "voxelize_aug_lowp", "compose_xforms", "map_step_head", "MapStepBatch", "locate_hands", "voxelize_frames",
-           "HandCrops"]
+           "HandCrops", "voxelize_grid_accurate", "voxelize_accurate"]

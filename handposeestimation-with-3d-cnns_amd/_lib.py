@@ -136,6 +136,11 @@ LOCATE_VERSION = 1
 TSDF_LOCATE_F32 = 0   # `frame_type` of include/tsdf_locate.h
 TSDF_LOCATE_U16 = 1
 
+# The extension library of include/tsdf_accurate.h (make -C csrc accurate): the accurate directional TSDF on a
+# caller-supplied grid — per voxel the nearest surface point among all valid pixels of the crop.  A binary of its own.
+ACCURATE_LIB_PATH = os.path.join(_HERE, "libtsdf_accurate.so")
+ACCURATE_VERSION = 1
+
 
 class _Ext(NamedTuple):
     """A row of the extension table: libtsdf_<name>.so, built by ``make -C csrc <name>`` from include/tsdf_<name>.h."""
@@ -147,9 +152,9 @@ class _Ext(NamedTuple):
 
 _vp, _i, _i64, _u64 = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_uint64
 
-# The extension libraries, in the order of csrc/Makefile's EXTS.  Adding one is a row here, a name in EXTS (with what its
-# tsdf_<name>.hip includes besides device.inc in <name>_DEPS), a one-line load_<name> below and a name in the list of
-# tests/test_ext_table_cpu.py, which checks every row against its header and its binary.
+# The nine extension libraries of csrc/Makefile's `EXTS :=` line, in its order: tests/test_ext_table_cpu.py pins this table
+# to exactly these and checks every row against its header and its binary.  A NEW library does not go here but into
+# _EXTS2 below.
 _EXTS = {
     "augment": _Ext(AUGMENT_LIB_PATH, "tsdf_augment_version", AUGMENT_VERSION, {
         # centres, n_src, index, n, key, counter0, stream, xforms, stretch, rot
@@ -208,6 +213,18 @@ _EXTS = {
         "tsdf_locate_hip": [_vp, _i, _i, _i64, _i, _i, _vp, _i, ctypes.c_float, ctypes.c_float, ctypes.c_float,
                             ctypes.c_float, _i, _i, ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_float,
                             ctypes.c_float, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+    }),
+}
+
+# The extension libraries added since, in the order of csrc/Makefile's `EXTS +=` lines.  Adding one is a row here, an
+# `EXTS += <name>` line there (with what its tsdf_<name>.hip includes besides device.inc in <name>_DEPS), a one-line
+# load_<name> below and a name in the list of tests/test_ext_table2_cpu.py, which makes the same checks over this table.
+_EXTS2 = {
+    "accurate": _Ext(ACCURATE_LIB_PATH, "tsdf_accurate_version", ACCURATE_VERSION, {
+        # depth, depth_len, offsets, headers, n_src, index, n, R, focal, cx, cy, invalid_eps, trunc_voxels (the camera by
+        # value), layout, stream, grid, tsdf, nearest, status
+        "tsdf_voxelize_grid_accurate_hip": [_vp, _i64, _vp, _vp, _i64, _vp, _i, _i, ctypes.c_double, ctypes.c_double,
+                                            ctypes.c_double, ctypes.c_float, ctypes.c_float, _i, _vp, _vp, _vp, _vp, _vp],
     }),
 }
 
@@ -307,7 +324,7 @@ def _load_ext(name: str):
     L = _ext_libs.get(name)
     if L is not None:
         return L
-    ext = _EXTS[name]
+    ext = _EXTS[name] if name in _EXTS else _EXTS2[name]
     if not os.path.exists(ext.path):
         raise ImportError(f"{ext.path} not found: build it with `make -C handposeestimation-with-3d-cnns_amd/csrc "
                           f"{name}` (__graft_entry__.build() does). There is no CPU fallback.")
@@ -363,6 +380,11 @@ def load_mapstep():
 def load_locate():
     """libtsdf_locate.so, the library of include/tsdf_locate.h."""
     return _load_ext("locate")
+
+
+def load_accurate():
+    """libtsdf_accurate.so, the library of include/tsdf_accurate.h."""
+    return _load_ext("accurate")
 
 
 @contextlib.contextmanager

@@ -1,0 +1,328 @@
+// tsdf_accurate.hip — libtsdf_accurate.so: the ACCURATE directional TSDF on a caller-supplied grid: per voxel the nearest
+// surface point among all valid pixels of the crop (include/tsdf_accurate.h has the contract).
+//
+// A translation unit and a library of its own, next to libtsdf_hip.so and the other extension libraries (all frozen).  It
+// takes the status codes and the layout enum from include/tsdf.h, the host preamble every library here has from
+// device.inc, the device primitives from prim.inc and the slab scaffold it shares with tsdf_auggrid.hip, tsdf_lowp.hip and
+// tsdf_maplowp.hip from slab.inc; the plain contract's projection and sign rule are RESTATED here operation for operation
+// as tsdf_lowp.hip has them, and there is no device global: every launch is self-contained.
+//
+// tsdf_grid_accurate_kernel: n x ceil(R / slab) workgroups of 256 threads; a workgroup owns `slab` consecutive slices
+// (indices of the slowest output axis) of one batch position — slab.inc's slab, halved while the launch would hold fewer
+// than kMinBlocks workgroups.  It
+//   1. resolves its source frame (the index, if any) and checks the frame's header and grid row (all uniform); a position
+//      that is not OK has its slab filled with zeros (nearest: -1) and workgroup 0 of the position writes the status;
+//   2. walks its slab in items of 4 consecutive voxels of the fastest axis, one item per lane and pass.  Per item:
+//      a. the plain contract's projection, gather and sign rule for each of the 4 voxels (`sv`: 0 rejected, else +-1);
+//      b. the SEARCH REGION of the item, a pixel rectangle (below);
+//      c. one row-major walk of that rectangle: per valid pixel the z term of each voxel first (one per item in layout
+//         czyx, where the 4 voxels share z) and, where some |tz| <= 1, the float64 evaluation of s for those voxels;
+//         (best s, row, column) is kept with a strict <, so ties stay with the lowest index;
+//      d. per voxel the values from the best pixel, recomputed by the same sequence; three 16-byte stores, one per
+//         channel, and one for `nearest` if asked.  Items are numbered in output order.
+// No LDS, no work queue, no communication between workgroups, no atomics.  Compiled with -ffp-contract=off, fma only where
+// __builtin_fma is written.
+//
+// WHAT MAY BE DISCARDED BEFORE s IS EVALUATED.  The contract allows only candidates that provably have
+// s > min(1, best so far).  A candidate with s > 1 never decides anything: if the true minimum is <= 1 the minimiser and
+// every pixel that ties with it have s <= 1, and if it is > 1 the voxel is far and names no pixel.  Two tests use that:
+//   The z term.  The kernel's s is fma(tz, tz, fma(ty, ty, tx * tx)) with tz = fma(d, it, vs_z).  For a float64 |tz| > 1,
+//     tz^2 >= (1 + 2^-52)^2 > 1 + 2^-52, the inner fma is the rounding of a non-negative real and so >= 0, and rounding is
+//     monotone: the evaluated s would be >= 1 + 2^-52 > 1.  Skipping on !(|tz| <= 1) therefore skips exactly candidates
+//     whose EVALUATED s exceeds 1 (or is a NaN, which wins no comparison): no margin is needed.
+//   The rectangle.  |v - w| <= T (T = trunc_dis) bounds each coordinate: |w_z - v_z| <= T puts the depth d = -w_z into
+//     [-v_z - T, -v_z + T], and |w_x - v_x| <= T with w_x = (col - cx) * d / F gives col = cx + F * w_x / d, a quotient that
+//     is monotone in w_x and in d separately while d keeps one sign — so over the box [v_x - T, v_x + T] x [d_lo, d_hi] its
+//     extremes are at the four corners (likewise row = cy - F * w_y / d).  The kernel uses T' = T * (1 + 2^-20) and, for
+//     the 4 voxels of an item, the union of their coordinate ranges; it rounds the corner values outwards by floor - 1 /
+//     ceil + 1 and clips to the crop.  A pixel outside has a real |t_c| > 1 + 2^-20 in some coordinate, a real
+//     s > 1 + 2^-19, and with the contract's evaluation error of 2^-40 (relative beyond s = 2) an evaluated s > 1.  The
+//     corner values carry a few roundings of relative 2^-53 on pixel coordinates that matter only inside the crop, i.e.
+//     below 2^31: far less than the one pixel added; a NaN bound (cx or cy is not judged) selects the whole side.
+//     A valid pixel has |d| >= eps.  When the depth interval does not stay on one side of zero by eps — the voxel lies
+//     within T' (+ eps) of the camera plane — the quotient is unbounded: there is NO finite rectangle and the whole crop is
+//     walked.
+// Tried and not kept ("Accurate directional TSDF"): a per-tile (min, max) depth cull in LDS — on hand crops a
+// tile's depth range meets most voxels' interval, and the tile walk cost twice the time of this one.  Not tried: a float32
+// screen, the slab's union window staged in LDS, several pixels per loop trip.
+//
+// The stores: plain 16-byte vector stores, as in tsdf_auggrid.hip; the kernel is bound by its search, not by its stores.
+
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+#include <string.h>
+
+#include <atomic>
+
+#include "../../include/tsdf_accurate.h"
+
+namespace {
+
+#include "device.inc"   // check_device, launched, misaligned: the host preamble of every library here
+#include "prim.inc"     // cam_ok, trunc_i32, finite32, f32_round_up, header_ok
+#include "slab.inc"     // workgroup <-> slab, the frame's header and grid row, zero-fill, host sizing
+
+typedef float acc_f4 __attribute__((ext_vector_type(4)));
+typedef int acc_i4 __attribute__((ext_vector_type(4)));
+
+constexpr int V = 4;   // voxels per lane and item: one 16-byte store per channel
+constexpr int64_t kMinBlocks = 1024;   // workgroups a launch aims for at least: four per CU of an MI355X
+
+struct AccArgs {
+  const float *depth;
+  int64_t depth_len;
+  const int64_t *offsets;   // [n_src + 1]
+  const int32_t *headers;   // [n_src][6]
+  int64_t n_src;
+  const int64_t *index;     // [n] or null
+  int n, R;
+  int slab;    // slices per workgroup
+  int nslab;   // workgroups per batch position
+  double focal, cx, cy, inv_focal;
+  float eps;
+  const float *grid;        // [n_src][8]
+  float *out;               // [n][3][R][R][R]
+  int32_t *nearest;         // [n][R][R][R] or null
+  int32_t *status;          // [n] or null
+};
+
+// lower clip of a window bound: max(lo, min(hi, b)) as an int; a NaN gives lo (the whole side)
+__device__ __forceinline__ int clip_lo(double b, int lo, int hi) {
+  return !(b > (double)lo) ? lo : (b < (double)hi ? trunc_i32(b) : hi);
+}
+
+// upper clip: min(hi, max(lo, b)); a NaN gives hi
+__device__ __forceinline__ int clip_hi(double b, int lo, int hi) {
+  return !(b < (double)hi) ? hi : (b > (double)lo ? trunc_i32(b) : lo);
+}
+
+template <int LAYOUT>
+__global__ __launch_bounds__(kSlabWG) void tsdf_grid_accurate_kernel(AccArgs a) {
+#pragma clang fp contract(off)
+  const int tid = threadIdx.x;
+  const int R = a.R, RV = R / V;
+  const Slab blk = slab_of_block(a.nslab, a.slab, R);
+  const int64_t i = blk.i;
+  const int sb = blk.sb, se = blk.se;
+  const int64_t R3 = (int64_t)R * R * R;
+  float *__restrict__ out = a.out + i * 3 * R3;
+  int32_t *__restrict__ nearest = a.nearest ? a.nearest + i * R3 : nullptr;
+
+  // the source frame; outside the tables it is a bad header and nothing of it is read
+  const int64_t g = a.index ? a.index[i] : i;
+  const bool src_ok = g >= 0 && g < a.n_src;
+  const int64_t gs = src_ok ? g : 0, depth_len = a.depth_len;
+  const SlabFrame fr = slab_frame(depth_len, a.offsets, a.headers, a.grid, gs, src_ok);
+  const int left = fr.left, top = fr.top, right = fr.right, bottom = fr.bottom;
+  const int64_t bw = fr.bw;
+  if (blk.first() && tid == 0 && a.status) a.status[i] = fr.status;
+
+  if (fr.status != TSDF_FRAME_OK) {   // (uniform)
+    const int64_t per = (int64_t)(se - sb) * R * RV;   // 16-byte pieces of the slab, per channel
+    slab_zero_fill<acc_f4>(out, R, sb, per, tid);
+    if (nearest) {
+      const acc_i4 none = {-1, -1, -1, -1};
+      acc_i4 *p = reinterpret_cast<acc_i4 *>(nearest + (int64_t)sb * R * R);
+      for (int64_t q = tid; q < per; q += kSlabWG) p[q] = none;
+    }
+    return;
+  }
+
+  // per-frame constants, as tsdf_lowp.hip has them
+  const double F = a.focal, cx = a.cx, cy = a.cy;
+  const double ox = (double)fr.ox, oy = (double)fr.oy, oz = (double)fr.oz, vl = (double)fr.vl;
+  const double T = (double)fr.td;
+  const double it = 1.0 / T;
+  const double kq = a.inv_focal * it;
+  const double Tw = T * (1.0 + 0x1p-20);   // the window's truncation distance (see the head of this file)
+  const float eps = a.eps;
+  const double epsd = (double)eps;
+  const float *__restrict__ d = a.depth + fr.off0;
+
+  const int nit = (se - sb) * R * RV;
+  for (int item = tid; item < nit; item += kSlabWG) {
+    const int fv = (item % RV) * V;
+    const int t1 = item / RV;
+    const int y = t1 % R, sl = sb + t1 / R;
+    const double vy = oy + (double)y * vl;
+    const double vys = vy * it;
+
+    // ---- a. the plain contract per voxel: centre, projection, gather, sign ----
+    double vxs[V], vzs[V];
+    float sv[V];
+    double xlo = __builtin_inf(), xhi = -__builtin_inf(), zlo = __builtin_inf(), zhi = -__builtin_inf();
+#pragma unroll
+    for (int j = 0; j < V; ++j) {
+      const int xi = LAYOUT == 0 ? fv + j : sl, zi = LAYOUT == 0 ? sl : fv + j;
+      const double px_ = (double)xi * vl, pz_ = (double)zi * vl;
+      const double vx = ox + px_, vz = oz + pz_;
+      vxs[j] = vx * it;
+      vzs[j] = vz * it;
+      xlo = __builtin_fmin(xlo, vx), xhi = __builtin_fmax(xhi, vx);
+      zlo = __builtin_fmin(zlo, vz), zhi = __builtin_fmax(zhi, vz);
+      const double q = -F / vz;                                  // IEEE division
+      const double mx = vx * q, my = (-vy) * q;
+      const int px = trunc_i32(mx + cx), py = trunc_i32(my + cy);
+      const bool inb = px >= left && px < right && py >= top && py < bottom;
+      const int64_t at = inb ? (int64_t)(py - top) * bw + (px - left) : 0;   // the load is always in bounds
+      const float pd = d[at];
+      const bool ok = inb & (__builtin_fabsf(pd) >= eps);        // NaN is invalid
+      const bool neg = pd < f32_round_up(-vz);                   // w_z > v_z
+      sv[j] = ok ? (neg ? -1.0f : 1.0f) : 0.0f;
+    }
+
+    // ---- b. the item's search rectangle [c0, c1) x [r0, r1), image coordinates ----
+    int c0 = left, c1 = right, r0 = top, r1 = bottom;
+    {
+      const double dlo = -zhi - Tw, dhi = -zlo + Tw;             // depths of points within T' along z
+      if (dlo >= epsd || dhi <= -epsd) {                         // one sign, away from zero: a finite rectangle
+        const double i0 = 1.0 / dlo, i1 = 1.0 / dhi;
+        const double xa = xlo - Tw, xb = xhi + Tw, ya = vy - Tw, yb = vy + Tw;
+        const double x00 = xa * i0, x01 = xa * i1, x10 = xb * i0, x11 = xb * i1;
+        const double y00 = ya * i0, y01 = ya * i1, y10 = yb * i0, y11 = yb * i1;
+        const double qxlo = __builtin_fmin(__builtin_fmin(x00, x01), __builtin_fmin(x10, x11));
+        const double qxhi = __builtin_fmax(__builtin_fmax(x00, x01), __builtin_fmax(x10, x11));
+        const double qylo = __builtin_fmin(__builtin_fmin(y00, y01), __builtin_fmin(y10, y11));
+        const double qyhi = __builtin_fmax(__builtin_fmax(y00, y01), __builtin_fmax(y10, y11));
+        // col = cx + F * (w_x / d), row = cy - F * (w_y / d); outwards by one pixel beyond floor / ceil
+        c0 = clip_lo(__builtin_floor(cx + F * qxlo) - 1.0, left, right);
+        c1 = clip_hi(__builtin_ceil(cx + F * qxhi) + 2.0, left, right);
+        r0 = clip_lo(__builtin_floor(cy - F * qyhi) - 1.0, top, bottom);
+        r1 = clip_hi(__builtin_ceil(cy - F * qylo) + 2.0, top, bottom);
+      }
+    }
+
+    // ---- c. the walk ----
+    double best[V];
+    int brow[V], bcol[V];
+#pragma unroll
+    for (int j = 0; j < V; ++j) best[j] = __builtin_inf(), brow[j] = 0, bcol[j] = -1;
+    if (c0 < c1 && r0 < r1) {
+      int row = r0, col = c0;
+      const float *__restrict__ p = d + (int64_t)(r0 - top) * bw + (c0 - left);
+      const int64_t skip = bw - (c1 - c0);
+      double dyi = (double)row - cy;
+      while (row < r1) {
+        const float pd = *p;
+        if (__builtin_fabsf(pd) >= eps) {
+          const double pd64 = (double)pd;
+          double tz[V];
+          bool any = false;
+#pragma unroll
+          for (int j = 0; j < V; ++j) {
+            tz[j] = LAYOUT == 0 && j > 0 ? tz[0] : __builtin_fma(pd64, it, vzs[j]);   // czyx: an item has one z
+            any |= __builtin_fabs(tz[j]) <= 1.0;
+          }
+          if (any) {                                             // otherwise the evaluated s exceeds 1 for all four
+            const double aq = pd64 * kq;
+            const double ndxi = -((double)col - cx);
+            const double ty = __builtin_fma(dyi, aq, vys);
+#pragma unroll
+            for (int j = 0; j < V; ++j) {
+              if (__builtin_fabs(tz[j]) <= 1.0) {
+                const double tx = LAYOUT == 1 && j > 0 ? __builtin_fma(ndxi, aq, vxs[0]) : __builtin_fma(ndxi, aq, vxs[j]);
+                const double xx = tx * tx;
+                const double s = __builtin_fma(tz[j], tz[j], __builtin_fma(ty, ty, xx));
+                if (s < best[j]) best[j] = s, brow[j] = row, bcol[j] = col;
+              }
+            }
+          }
+        }
+        ++p, ++col;
+        if (col == c1) {
+          col = c0, ++row, p += skip;
+          dyi = (double)row - cy;
+        }
+      }
+    }
+
+    // ---- d. the values, from the best pixel by the same sequence ----
+    acc_f4 o0, o1, o2;
+    acc_i4 on;
+#pragma unroll
+    for (int j = 0; j < V; ++j) {
+      const bool nearv = best[j] <= 1.0;
+      const int64_t at = nearv ? (int64_t)(brow[j] - top) * bw + (bcol[j] - left) : 0;
+      const double pd64 = (double)d[at];
+      const double aq = pd64 * kq;
+      const double tz = __builtin_fma(pd64, it, vzs[j]);
+      const double tx = __builtin_fma(-((double)bcol[j] - cx), aq, vxs[j]);
+      const double ty = __builtin_fma((double)brow[j] - cy, aq, vys);
+      const float sg = sv[j] < 0.0f ? -1.0f : 1.0f;              // a rejected voxel's ray meets no surface: positive
+      const float m0 = __builtin_fminf(__builtin_fabsf((float)tx), 1.0f);
+      const float m1 = __builtin_fminf(__builtin_fabsf((float)ty), 1.0f);
+      const float m2 = __builtin_fminf(__builtin_fabsf((float)tz), 1.0f);
+      o0[j] = nearv ? m0 * sg : sv[j];
+      o1[j] = nearv ? m1 * sg : sv[j];
+      o2[j] = nearv ? m2 * sg : sv[j];
+      on[j] = nearv ? (int)(uint32_t)(uint64_t)at : -1;
+    }
+    const int64_t e = ((int64_t)sl * R + y) * R + fv;   // o[c][slow][y][fast]
+    *reinterpret_cast<acc_f4 *>(out + e) = o0;
+    *reinterpret_cast<acc_f4 *>(out + R3 + e) = o1;
+    *reinterpret_cast<acc_f4 *>(out + 2 * R3 + e) = o2;
+    if (nearest) *reinterpret_cast<acc_i4 *>(nearest + e) = on;
+  }
+}
+
+}  // namespace
+
+extern "C" {
+
+int tsdf_accurate_version(void) { return TSDF_ACCURATE_VERSION; }
+
+int tsdf_voxelize_grid_accurate_hip(const float *d_depth, int64_t depth_len, const int64_t *d_offsets,
+                                    const int32_t *d_headers, int64_t n_src, const int64_t *d_index, int n, int R,
+                                    double focal, double cx, double cy, float invalid_eps, float trunc_voxels,
+                                    int layout, void *hip_stream, const float *d_grid, float *d_out_tsdf,
+                                    int32_t *d_out_nearest, int32_t *d_out_status) {
+  // arguments first, then the device, then the launch
+  if (n < 0) return TSDF_ERR_INVALID_ARG;
+  if (slab_bad_shape(R, layout)) return TSDF_ERR_INVALID_ARG;
+  if (n == 0) return TSDF_OK;
+  if (!d_depth || !d_offsets || !d_headers || !d_grid || !d_out_tsdf || depth_len < 0) return TSDF_ERR_INVALID_ARG;
+  if (n_src < 1 || (!d_index && n_src != n)) return TSDF_ERR_INVALID_ARG;
+  if (misaligned(d_out_tsdf, 15) || misaligned(d_out_nearest, 15)) return TSDF_ERR_INVALID_ARG;
+  const tsdf_cam cam = {focal, cx, cy, invalid_eps, trunc_voxels};   // by value in the ABI, one rule all the same
+  if (!cam_ok(&cam)) return TSDF_ERR_INVALID_ARG;
+  SlabPlan plan;
+  if (!slab_plan(n, R, V, plan)) return TSDF_ERR_INVALID_ARG;   // a launch holds fewer than 2^32 work-items
+  // slab_plan sizes a workgroup for a kernel that is bound by its stores.  This one is bound by its search, and a small
+  // batch is as long as its slowest workgroup: below kMinBlocks workgroups the slabs are halved (down to one slice).
+  // A voxel's result does not depend on the slab it is in.
+  while (plan.slab > 1 && plan.blocks < kMinBlocks) {
+    plan.slab = (plan.slab + 1) / 2;
+    plan.nslab = (R + plan.slab - 1) / plan.slab;
+    plan.blocks = (int64_t)n * plan.nslab;
+  }
+  const int rc = check_device(nullptr);
+  if (rc != TSDF_OK) return rc;
+  AccArgs a;
+  a.depth = d_depth;
+  a.depth_len = depth_len;
+  a.offsets = d_offsets;
+  a.headers = d_headers;
+  a.n_src = n_src;
+  a.index = d_index;
+  a.n = n;
+  a.R = R;
+  a.slab = plan.slab;
+  a.nslab = plan.nslab;
+  a.focal = focal;
+  a.cx = cx;
+  a.cy = cy;
+  a.inv_focal = 1.0 / focal;
+  a.eps = invalid_eps;
+  a.grid = d_grid;
+  a.out = d_out_tsdf;
+  a.nearest = d_out_nearest;
+  a.status = d_out_status;
+  hipStream_t s = static_cast<hipStream_t>(hip_stream);
+  if (layout == TSDF_LAYOUT_CZYX)
+    hipLaunchKernelGGL(tsdf_grid_accurate_kernel<0>, dim3((unsigned)plan.blocks), dim3(kSlabWG), 0, s, a);
+  else
+    hipLaunchKernelGGL(tsdf_grid_accurate_kernel<1>, dim3((unsigned)plan.blocks), dim3(kSlabWG), 0, s, a);
+  return launched();
+}
+
+}  // extern "C"

@@ -88,6 +88,20 @@ def _default_voxelize(pk: packing.PackedFrames, res: int, layout: str, device):
             out.status.cpu().numpy())
 
 
+def _default_voxelize_accurate(pk: packing.PackedFrames, res: int, layout: str, device):
+    """:func:`_default_voxelize` with the accurate directional TSDF (``voxelize.voxelize_accurate``): the same placement,
+    max_l, mid_p and status, the volumes by the nearest point among all valid pixels."""
+    import torch
+
+    from .voxelize import voxelize_accurate
+
+    depth, offsets, headers = pk.to_torch(device, pin=True, non_blocking=True)
+    out = voxelize_accurate(depth, offsets, headers, res=res, layout=layout)
+    torch.cuda.synchronize(depth.device)
+    return (out.tsdf.cpu().numpy(), out.max_l.cpu().numpy(), out.mid_p.cpu().numpy(),
+            out.status.cpu().numpy())
+
+
 def _default_voxelize_aug(pk: packing.PackedFrames, xforms: np.ndarray, gt: np.ndarray, res: int, layout: str, device):
     """Upload + one augmented launch with the labels: host arrays (tsdf, max_l, mid_p, status, gt_aug)."""
     import torch
@@ -114,6 +128,22 @@ def _default_voxelize_cloud(pk: packing.PackedFrames, cloud: np.ndarray, res: in
     pts = torch.from_numpy(np.ascontiguousarray(cloud, np.float64)).to(depth.device)
     cg = cloud_grids(pts, res=res)
     tsdf, st = voxelize_grid(depth, offsets, headers, cg.grid, res=res, layout=layout)
+    status = torch.where(cg.status != 0, cg.status, st)
+    torch.cuda.synchronize(depth.device)
+    return tsdf.cpu().numpy(), cg.max_l.cpu().numpy(), cg.mid_p.cpu().numpy(), status.cpu().numpy()
+
+
+def _default_voxelize_cloud_accurate(pk: packing.PackedFrames, cloud: np.ndarray, res: int, layout: str, device):
+    """:func:`_default_voxelize_cloud` with the accurate directional TSDF (``voxelize.voxelize_grid_accurate``) on the
+    cloud's placement."""
+    import torch
+
+    from .voxelize import cloud_grids, voxelize_grid_accurate
+
+    depth, offsets, headers = pk.to_torch(device, pin=True, non_blocking=True)
+    pts = torch.from_numpy(np.ascontiguousarray(cloud, np.float64)).to(depth.device)
+    cg = cloud_grids(pts, res=res)
+    tsdf, st = voxelize_grid_accurate(depth, offsets, headers, cg.grid, res=res, layout=layout)
     status = torch.where(cg.status != 0, cg.status, st)
     torch.cuda.synchronize(depth.device)
     return tsdf.cpu().numpy(), cg.max_l.cpu().numpy(), cg.mid_p.cpu().numpy(), status.cpu().numpy()
@@ -236,7 +266,7 @@ def preprocess_tree(db_dir: str, save_dir: str, *, res: int = 32, layout: str = 
                     aug_rng: Optional[np.random.Generator] = None,
                     voxelize_aug_fn: Optional[Callable] = None, placement: str = "pixels",
                     voxelize_cloud_fn: Optional[Callable] = None, aug_placement: str = "pixels",
-                    voxelize_aug_cloud_fn: Optional[Callable] = None) -> Dict[str, int]:
+                    voxelize_aug_cloud_fn: Optional[Callable] = None, tsdf: str = "projective") -> Dict[str, int]:
     """Replacement for ``read_MSRA.main()`` (pre/read_MSRA.py:37-140): voxelize a whole MSRA tree into ``save_dir`` in
     the reference's schema (with ``aug=True`` its AUG=True schema).  Returns ``{subject: frames}``.
 
@@ -261,6 +291,13 @@ def preprocess_tree(db_dir: str, save_dir: str, *, res: int = 32, layout: str = 
     ``point_clouds``: True / "host" (``resample_point_clouds`` on the host), "device" (``voxelize.point_clouds``) or
     False (no cloud files).  The draws of each are in the module docstring.
 
+    ``tsdf``: "projective" (default) or "accurate": the DEFAULT ``voxelize_fn`` / ``voxelize_cloud_fn`` write the accurate
+    directional TSDF — per voxel the nearest surface point among all valid pixels (``voxelize.voxelize_accurate``;
+    with ``placement="cloud"`` ``cloud_grids`` + ``voxelize_grid_accurate``) — into ``TSDF/<g>.npz``: the same schema, max_l,
+    mid_p and status, so the tree is read by the reference's own train.py unchanged.  Hooks the caller passes are called as
+    they are.  ``aug=True`` with ``tsdf="accurate"`` is a ``ValueError``: the accurate pass under a per-frame map is not
+    there yet.
+
     ``pca_dir``: also write the joint-PCA fits of the first nine subjects' leave-one-out folds there (``pca.JointPCA``
     files, ``<fold>.npz``, and with ``aug=True`` ``<fold>-aug.npz``): the labels are normalised with each frame's own
     max_l / mid_p (no clamp) and frames whose status is not OK are left out."""
@@ -277,9 +314,16 @@ def preprocess_tree(db_dir: str, save_dir: str, *, res: int = 32, layout: str = 
     if aug_placement == "cloud" and not (aug and point_clouds):
         raise ValueError('aug_placement="cloud" places the grid on the saved augmented cloud: it needs aug=True and '
                          'point_clouds="host" or "device"')
+    if tsdf not in ("projective", "accurate"):
+        raise ValueError('tsdf must be "projective" or "accurate"')
+    if tsdf == "accurate" and aug:
+        raise ValueError('tsdf="accurate" has no augmented twin yet (the accurate pass under a per-frame map): use aug=False')
     vox = voxelize_fn if voxelize_fn is not None else _default_voxelize
     vox_aug_cloud = voxelize_aug_cloud_fn if voxelize_aug_cloud_fn is not None else _default_voxelize_aug_cloud
     vox_cloud = voxelize_cloud_fn if voxelize_cloud_fn is not None else _default_voxelize_cloud
+    if tsdf == "accurate":
+        vox = voxelize_fn if voxelize_fn is not None else _default_voxelize_accurate
+        vox_cloud = voxelize_cloud_fn if voxelize_cloud_fn is not None else _default_voxelize_cloud_accurate
     vox_aug = voxelize_aug_fn if voxelize_aug_fn is not None else _default_voxelize_aug
     rng = rng if rng is not None else np.random.default_rng()
     if aug:

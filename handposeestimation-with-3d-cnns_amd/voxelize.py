@@ -1155,6 +1155,66 @@ def narrow_volumes(tsdf32: torch.Tensor, dtype: torch.dtype = torch.bfloat16,
     return out
 
 
+def voxelize_grid_accurate(depth: torch.Tensor, offsets: torch.Tensor, headers: torch.Tensor, grid: torch.Tensor,
+                           res: int = 32, layout: str = "czyx", cam: Optional[_lib.TsdfCam] = None,
+                           index: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None,
+                           nearest: bool = False):
+    """The ACCURATE directional TSDF on a caller-supplied grid (``tsdf_voxelize_grid_accurate_hip`` of
+    libtsdf_accurate.so; include/tsdf_accurate.h has the contract): per voxel the nearest surface point among ALL valid
+    pixels of the crop, where :func:`voxelize_grid` takes the one pixel the voxel projects to and rejects the voxel when
+    that pixel is empty.  A voxel within the truncation distance of some point gets ``min(|v - w| / trunc_dis, 1)`` per
+    channel with the plain pass's sign (positive where the plain pass rejects); every other voxel keeps the plain value.
+
+    depth / offsets / headers   the n_src source frames, as for :func:`voxelize`
+    grid    float32[n_src,8] on the GPU: vox_ori[3], voxel_len, trunc_dis, 3 pad words per SOURCE frame
+    cam     a :class:`TsdfCam` or None (the MSRA defaults); its five constants go to the entry by value
+    index   optional int64[n] on the GPU: batch position i voxelizes source frame index[i] (repeats allowed; an entry
+            outside [0, n_src) gives that position status 2 and a zero volume).  Without it the batch is the n_src frames
+    out     optional preallocated ``float32[n,3,R,R,R]`` (a contiguous view of a larger buffer will do) to write into
+    nearest True: also ``int32[n,R,R,R]``, per voxel the row-major crop index of its nearest pixel, -1 for a far voxel,
+            in the index order of one channel of the volume
+    Returns ``(tsdf float32[n,3,R,R,R], status int32[n])``, with ``nearest`` a third tensor.  A bad header (2) or an
+    unusable grid row (1: ``trunc_dis`` not positive, or anything non-finite) gives a zero volume; a frame without a valid
+    pixel gets a zero volume with status 0.  One launch on the current stream, no synchronisation.  A voxel within the
+    truncation distance of the camera plane is searched over the whole crop: keep such grids to small crops."""
+    A = _lib.load_accurate()
+    dev, n_src, R = _pack(_lib.load(), depth, offsets, headers, res, layout)
+    _shaped("grid", grid, (n_src, 8), torch.float32, dev)
+    n = n_src
+    if index is not None:
+        _dev_check("index", index, torch.int64, dev)
+        if index.dim() != 1:
+            raise ValueError("index must have shape [n]")
+        n = int(index.shape[0])
+        if n and not n_src:
+            raise ValueError("index needs at least one source frame")
+    tsdf = _out("out", out, (n, 3, R, R, R), torch.float32, dev)
+    st = _out("status", None, (n,), torch.int32, dev)
+    near = _out("nearest", None, (n, R, R, R), torch.int32, dev) if nearest else None
+    if n:
+        c = cam if cam is not None else _lib.default_cam()   # the entry takes the five constants by value
+        _call(dev, A.tsdf_voxelize_grid_accurate_hip,
+              [depth.data_ptr(), depth.numel(), offsets.data_ptr(), headers.data_ptr(), n_src, _ptr(index), n, R, c.focal, c.cx,
+               c.cy, c.invalid_eps, c.trunc_voxels, _lib.LAYOUTS[layout], None, grid.data_ptr(), tsdf.data_ptr(), _ptr(near),
+               st.data_ptr()], 14)
+    return (tsdf, st, near) if nearest else (tsdf, st)
+
+
+def _aabb_rows(ab: "AabbBatch") -> torch.Tensor:
+    """The grid rows (vox_ori[3], voxel_len, trunc_dis, 3 pad words) of :func:`aabb`'s placement, put together on the device."""
+    return torch.cat([ab.ori, ab.grid[:, 4:6], torch.zeros_like(ab.ori)], dim=1)
+
+
+def voxelize_accurate(depth: torch.Tensor, offsets: torch.Tensor, headers: torch.Tensor, res: int = 32,
+                      layout: str = "czyx", cam: Optional[_lib.TsdfCam] = None) -> TsdfBatch:
+    """:func:`voxelize` with the accurate directional TSDF: :func:`aabb` places the grid, the rows are put together on the
+    device and :func:`voxelize_grid_accurate` writes the volume.  Nothing runs on the host in between; it is two launches.
+    ``max_l`` / ``mid_p`` / ``status`` are :func:`aabb`'s, bit for bit those of :func:`voxelize`."""
+    ab = aabb(depth, offsets, headers, res=res, cam=cam)
+    tsdf, _ = voxelize_grid_accurate(depth, offsets, headers, _aabb_rows(ab), res=res, layout=layout, cam=cam)
+    return TsdfBatch(tsdf, ab.grid[:, 3].contiguous(), ab.grid[:, :3].contiguous(), ab.status)
+
+
 class MapGridBatch(NamedTuple):
     grid: torch.Tensor    # float32[n, 8]  vox_ori[3], voxel_len, trunc_dis, 0, 0, 0 (the ``grid`` of the voxel passes)
     max_l: torch.Tensor   # float32[n]     in the mapped frame
@@ -1492,7 +1552,7 @@ def locate_hands(frames: torch.Tensor, *, cube: float = 250.0, near: float = 100
 
 
 def voxelize_frames(frames: torch.Tensor, res: int = 32, *, placement: str = "aabb", dtype: Optional[torch.dtype] = None,
-                    gt: Optional[torch.Tensor] = None, layout: str = "czyx", **locate):
+                    gt: Optional[torch.Tensor] = None, layout: str = "czyx", tsdf: str = "projective", **locate):
     """Raw depth frames to volumes: :func:`locate_hands` chained into the existing voxelizers on one stream, nothing on
     the host in between.  Returns ``(TsdfBatch, HandCrops)``, or with ``gt`` (float32[n,3J] or [n,J,3] on the GPU, the
     joints of every batch position, camera frame) ``(TsdfBatch, HandCrops, gt_nor)``.
@@ -1504,6 +1564,9 @@ def voxelize_frames(frames: torch.Tensor, res: int = 32, *, placement: str = "aa
                 ``HandCrops.grid``; ``max_l`` / ``mid_p`` of the batch are the cube's (its edge and centre), so a frame's
                 scale does not move with a finger, and the labels are ``normalize_joints(gt, max_l, mid_p)``.
     dtype       None (float32 volumes), torch.float16 or torch.bfloat16
+    tsdf        "projective" (default: the entries above) or "accurate": the volumes are the accurate directional TSDF
+                (:func:`voxelize_grid_accurate`) on the same placement — the AABB's rows or the cube's —, followed by
+                :func:`narrow_volumes` with ``dtype``; ``max_l`` / ``mid_p`` / ``status`` and the labels do not change.
     **locate    :func:`locate_hands`' keywords (``cube``, ``near``, ``far``, ``seed_band``, ``refine``, ``cam``, ``shift``,
                 ``index``, ``out``); ``cam`` goes to the voxelizer as well."""
     if placement not in ("aabb", "cube"):
@@ -1512,13 +1575,26 @@ def voxelize_frames(frames: torch.Tensor, res: int = 32, *, placement: str = "aa
         raise ValueError("layout must be 'czyx' or 'cxyz'")
     if dtype is not None:
         _lowp_dtype(dtype)
+    if tsdf not in ("projective", "accurate"):
+        raise ValueError("tsdf must be 'projective' or 'accurate'")
     if "grid" in locate or "res" in locate:
         raise TypeError("voxelize_frames sets locate_hands' grid and res itself")
     cam = locate.get("cam")
     crops = locate_hands(frames, res=res, grid=placement == "cube", **locate)
     d, o, h = crops.depth, crops.offsets, crops.headers
     gt_nor = None
-    if placement == "aabb":
+    if tsdf == "accurate":
+        if placement == "aabb":
+            ab = aabb(d, o, h, res=res, cam=cam)
+            rows, max_l, mid_p, st = _aabb_rows(ab), ab.grid[:, 3].contiguous(), ab.grid[:, :3].contiguous(), ab.status
+            vol, _ = voxelize_grid_accurate(d, o, h, rows, res=res, layout=layout, cam=cam)
+        else:
+            max_l, mid_p = crops.max_l, crops.mid_p
+            vol, st = voxelize_grid_accurate(d, o, h, crops.grid, res=res, layout=layout, cam=cam)
+        if dtype is not None:
+            vol = narrow_volumes(vol, dtype=dtype)
+        batch = TsdfBatch(vol, max_l, mid_p, st)
+    elif placement == "aabb":
         if dtype is not None:
             batch = voxelize_lowp(d, o, h, res=res, layout=layout, dtype=dtype, cam=cam)
         elif gt is not None:
