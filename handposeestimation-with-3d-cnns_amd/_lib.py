@@ -152,9 +152,10 @@ class _Ext(NamedTuple):
 
 _vp, _i, _i64, _u64 = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_uint64
 
-# The nine extension libraries of csrc/Makefile's `EXTS :=` line, in its order: tests/test_ext_table_cpu.py pins this table
-# to exactly these and checks every row against its header and its binary.  A NEW library does not go here but into
-# _EXTS2 below.
+# The extension libraries of csrc/Makefile's `EXTS :=` line, in its order: tests/test_ext_table_cpu.py pins this table to
+# exactly these and checks every row against its header and its binary.  Adding one is a row here, a name on that line
+# (with what its tsdf_<name>.hip includes besides device.inc in <name>_DEPS), a one-line load_<name> below and a name in
+# that test's list.
 _EXTS = {
     "augment": _Ext(AUGMENT_LIB_PATH, "tsdf_augment_version", AUGMENT_VERSION, {
         # centres, n_src, index, n, key, counter0, stream, xforms, stretch, rot
@@ -214,12 +215,6 @@ _EXTS = {
                             ctypes.c_float, _i, _i, ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_float,
                             ctypes.c_float, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     }),
-}
-
-# The extension libraries added since, in the order of csrc/Makefile's `EXTS +=` lines.  Adding one is a row here, an
-# `EXTS += <name>` line there (with what its tsdf_<name>.hip includes besides device.inc in <name>_DEPS), a one-line
-# load_<name> below and a name in the list of tests/test_ext_table2_cpu.py, which makes the same checks over this table.
-_EXTS2 = {
     "accurate": _Ext(ACCURATE_LIB_PATH, "tsdf_accurate_version", ACCURATE_VERSION, {
         # depth, depth_len, offsets, headers, n_src, index, n, R, focal, cx, cy, invalid_eps, trunc_voxels (the camera by
         # value), layout, stream, grid, tsdf, nearest, status
@@ -324,7 +319,7 @@ def _load_ext(name: str):
     L = _ext_libs.get(name)
     if L is not None:
         return L
-    ext = _EXTS[name] if name in _EXTS else _EXTS2[name]
+    ext = _EXTS[name]
     if not os.path.exists(ext.path):
         raise ImportError(f"{ext.path} not found: build it with `make -C handposeestimation-with-3d-cnns_amd/csrc "
                           f"{name}` (__graft_entry__.build() does). There is no CPU fallback.")

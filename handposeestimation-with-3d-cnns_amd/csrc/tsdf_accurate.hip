@@ -69,16 +69,8 @@ constexpr int V = 4;   // voxels per lane and item: one 16-byte store per channe
 constexpr int64_t kMinBlocks = 1024;   // workgroups a launch aims for at least: four per CU of an MI355X
 
 struct AccArgs {
-  const float *depth;
-  int64_t depth_len;
-  const int64_t *offsets;   // [n_src + 1]
-  const int32_t *headers;   // [n_src][6]
-  int64_t n_src;
-  const int64_t *index;     // [n] or null
-  int n, R;
-  int slab;    // slices per workgroup
-  int nslab;   // workgroups per batch position
-  double focal, cx, cy, inv_focal;
+  SlabSrc src;
+  double inv_focal;
   float eps;
   const float *grid;        // [n_src][8]
   float *out;               // [n][3][R][R][R]
@@ -100,26 +92,18 @@ template <int LAYOUT>
 __global__ __launch_bounds__(kSlabWG) void tsdf_grid_accurate_kernel(AccArgs a) {
 #pragma clang fp contract(off)
   const int tid = threadIdx.x;
-  const int R = a.R, RV = R / V;
-  const Slab blk = slab_of_block(a.nslab, a.slab, R);
-  const int64_t i = blk.i;
+  const int R = a.src.R, RV = R / V;
+  const Slab blk = slab_of_block(a.src.nslab, a.src.slab, R);
   const int sb = blk.sb, se = blk.se;
   const int64_t R3 = (int64_t)R * R * R;
-  float *__restrict__ out = a.out + i * 3 * R3;
-  int32_t *__restrict__ nearest = a.nearest ? a.nearest + i * R3 : nullptr;
+  float *__restrict__ out = a.out + blk.i * 3 * R3;
+  int32_t *__restrict__ nearest = a.nearest ? a.nearest + blk.i * R3 : nullptr;
 
-  // the source frame; outside the tables it is a bad header and nothing of it is read
-  const int64_t g = a.index ? a.index[i] : i;
-  const bool src_ok = g >= 0 && g < a.n_src;
-  const int64_t gs = src_ok ? g : 0, depth_len = a.depth_len;
-  const SlabFrame fr = slab_frame(depth_len, a.offsets, a.headers, a.grid, gs, src_ok);
+  const SlabFrame fr = slab_head<true>(a.src, blk, a.grid);
   const int left = fr.left, top = fr.top, right = fr.right, bottom = fr.bottom;
   const int64_t bw = fr.bw;
-  if (blk.first() && tid == 0 && a.status) a.status[i] = fr.status;
-
-  if (fr.status != TSDF_FRAME_OK) {   // (uniform)
-    const int64_t per = (int64_t)(se - sb) * R * RV;   // 16-byte pieces of the slab, per channel
-    slab_zero_fill<acc_f4>(out, R, sb, per, tid);
+  const int64_t per = (int64_t)(se - sb) * R * RV;   // 16-byte pieces of the slab, per channel
+  if (slab_bad_frame<acc_f4>(fr, blk, a.status, out, R, per, tid)) {
     if (nearest) {
       const acc_i4 none = {-1, -1, -1, -1};
       acc_i4 *p = reinterpret_cast<acc_i4 *>(nearest + (int64_t)sb * R * R);
@@ -129,7 +113,7 @@ __global__ __launch_bounds__(kSlabWG) void tsdf_grid_accurate_kernel(AccArgs a) 
   }
 
   // per-frame constants, as tsdf_lowp.hip has them
-  const double F = a.focal, cx = a.cx, cy = a.cy;
+  const double F = a.src.focal, cx = a.src.cx, cy = a.src.cy;
   const double ox = (double)fr.ox, oy = (double)fr.oy, oz = (double)fr.oz, vl = (double)fr.vl;
   const double T = (double)fr.td;
   const double it = 1.0 / T;
@@ -137,7 +121,7 @@ __global__ __launch_bounds__(kSlabWG) void tsdf_grid_accurate_kernel(AccArgs a) 
   const double Tw = T * (1.0 + 0x1p-20);   // the window's truncation distance (see the head of this file)
   const float eps = a.eps;
   const double epsd = (double)eps;
-  const float *__restrict__ d = a.depth + fr.off0;
+  const float *__restrict__ d = a.src.depth + fr.off0;
 
   const int nit = (se - sb) * R * RV;
   for (int item = tid; item < nit; item += kSlabWG) {
@@ -280,13 +264,11 @@ int tsdf_voxelize_grid_accurate_hip(const float *d_depth, int64_t depth_len, con
   if (n < 0) return TSDF_ERR_INVALID_ARG;
   if (slab_bad_shape(R, layout)) return TSDF_ERR_INVALID_ARG;
   if (n == 0) return TSDF_OK;
-  if (!d_depth || !d_offsets || !d_headers || !d_grid || !d_out_tsdf || depth_len < 0) return TSDF_ERR_INVALID_ARG;
-  if (n_src < 1 || (!d_index && n_src != n)) return TSDF_ERR_INVALID_ARG;
-  if (misaligned(d_out_tsdf, 15) || misaligned(d_out_nearest, 15)) return TSDF_ERR_INVALID_ARG;
+  if (!d_grid || !d_out_tsdf || misaligned(d_out_tsdf, 15) || misaligned(d_out_nearest, 15)) return TSDF_ERR_INVALID_ARG;
   const tsdf_cam cam = {focal, cx, cy, invalid_eps, trunc_voxels};   // by value in the ABI, one rule all the same
-  if (!cam_ok(&cam)) return TSDF_ERR_INVALID_ARG;
   SlabPlan plan;
-  if (!slab_plan(n, R, V, plan)) return TSDF_ERR_INVALID_ARG;   // a launch holds fewer than 2^32 work-items
+  if (!slab_args_ok(d_depth, depth_len, d_offsets, d_headers, n_src, d_index, n, R, V, &cam, plan))
+    return TSDF_ERR_INVALID_ARG;
   // slab_plan sizes a workgroup for a kernel that is bound by its stores.  This one is bound by its search, and a small
   // batch is as long as its slowest workgroup: below kMinBlocks workgroups the slabs are halved (down to one slice).
   // A voxel's result does not depend on the slab it is in.
@@ -298,19 +280,7 @@ int tsdf_voxelize_grid_accurate_hip(const float *d_depth, int64_t depth_len, con
   const int rc = check_device(nullptr);
   if (rc != TSDF_OK) return rc;
   AccArgs a;
-  a.depth = d_depth;
-  a.depth_len = depth_len;
-  a.offsets = d_offsets;
-  a.headers = d_headers;
-  a.n_src = n_src;
-  a.index = d_index;
-  a.n = n;
-  a.R = R;
-  a.slab = plan.slab;
-  a.nslab = plan.nslab;
-  a.focal = focal;
-  a.cx = cx;
-  a.cy = cy;
+  a.src = slab_src(d_depth, depth_len, d_offsets, d_headers, n_src, d_index, n, R, cam, plan);
   a.inv_focal = 1.0 / focal;
   a.eps = invalid_eps;
   a.grid = d_grid;

@@ -3,22 +3,23 @@
 //
 // A translation unit and a library of its own, next to libtsdf_hip.so, libtsdf_augment.so and libtsdf_augstep.so (all
 // frozen).  It takes the status codes, tsdf_cam and the layout enum from include/tsdf.h and the host preamble every library
-// here has from device.inc, the device primitives from prim.inc and the slab scaffold it shares with tsdf_lowp.hip from
-// slab.inc; nothing else of the product's .inc files is included, and there is no device global: every launch is
-// self-contained.
+// here has from device.inc, the device primitives from prim.inc, the slab scaffold it shares with tsdf_lowp.hip,
+// tsdf_maplowp.hip and tsdf_accurate.hip from slab.inc and the voxel arithmetic under a map — the per-axis table, the
+// per-frame constants, the four-voxel chain — from mapvox.inc, which it shares with tsdf_maplowp.hip; nothing else of the
+// product's .inc files is included, and there is no device global: every launch is self-contained.
 //
 // tsdf_aug_grid_kernel: n x ceil(R / slab) workgroups of 256 threads; a workgroup owns `slab` consecutive slices (indices
 // of the slowest output axis) of one frame, so a batch of 16 frames at 32^3 is 256 workgroups.  It
-//   1. checks the frame's header and grid row (both uniform); a frame that is not OK has its slab zero-filled and
-//      workgroup 0 of the frame writes the status;
-//   2. tabulates, per axis and grid index, the three products of the inverse map with the voxel centre's coordinate (the z
-//      axis with b' added: the contract groups T^-1 as (A'_i0 x + A'_i1 y) + (A'_i2 z + b'_i), both brackets depend on grid
-//      indices only) and v' - b of the distance terms: 3 x R entries of 32 bytes in LDS (3 KiB at R = 32);
-//   3. walks its slab in items of 4 consecutive voxels of the fastest axis, one item per lane and pass: two additions
-//      per row of the map, the IEEE division, the unfused pixel index, a plain global load of the gathered pixel (a crop
-//      is at most 300 KB and is re-read by every slab of the frame: it is expected to be served by L2), the distance
-//      terms, and three 16-byte stores, one per channel (items are numbered in output order, so a wave writes one
-//      contiguous KiB per channel).
+//   1. checks the frame's header and grid row (both uniform; slab.inc, with no index: the ABI has none); a frame that is
+//      not OK has its slab zero-filled and workgroup 0 of the frame writes the status;
+//   2. tabulates, per axis and grid index, the three products of the inverse map with the voxel centre's coordinate and
+//      v' - b of the distance terms (mapvox.inc::map_fill_tab): 3 x R entries of 32 bytes in LDS (3 KiB at R = 32);
+//   3. walks its slab in items of 4 consecutive voxels of the fastest axis, one item per lane and pass
+//      (mapvox.inc::map_quad): two additions per row of the map, the IEEE division, the unfused pixel index and a plain
+//      global load of the gathered pixel for each of the four (always in bounds: a rejected voxel reads the crop's first
+//      pixel; a crop is at most 300 KB and is re-read by every slab of the frame: it is expected to be served by L2), then
+//      the distance terms, and three 16-byte stores, one per channel (items are numbered in output order, so a wave writes
+//      one contiguous KiB per channel).
 // No LDS staging of the crop, no work queue, no communication between workgroups, no atomics.
 // Arithmetic contract: include/tsdf_auggrid.h (== oracle/tsdf_oracle.c::tsdf_oracle_voxels_aug); compiled with
 // -ffp-contract=off, fma only where __builtin_fma is written.
@@ -36,19 +37,12 @@ namespace {
 #include "device.inc"   // check_device, launched, misaligned: the host preamble of every library here
 #include "prim.inc"     // kDefaultCam, trunc_i32, finite32, header_ok
 #include "slab.inc"     // workgroup <-> slab, the frame's header and grid row, zero-fill, host sizing
+#include "mapvox.inc"   // map_fill_tab, map_consts, map_quad: the mapped voxel arithmetic, shared with tsdf_maplowp.hip
 
 typedef float grid_f4 __attribute__((ext_vector_type(4)));
-typedef double grid_d4 __attribute__((ext_vector_type(4)));
 
 struct AugGridArgs {
-  const float *depth;
-  int64_t depth_len;
-  const int64_t *offsets;
-  const int32_t *headers;
-  int n, R;
-  int slab;    // slices per workgroup
-  int nslab;   // workgroups per frame
-  double focal, cx, cy;
+  SlabSrc src;            // no index in this ABI: index null, n_src = n
   float eps;
   const double *xforms;   // [n][24]
   const float *grid;      // [n][8]
@@ -59,57 +53,22 @@ struct AugGridArgs {
 template <int LAYOUT>
 __global__ __launch_bounds__(kSlabWG) void tsdf_aug_grid_kernel(AugGridArgs a) {
 #pragma clang fp contract(off)
-  // [axis][index] = {A'_0a v'_a, A'_1a v'_a, A'_2a v'_a, v'_a - b_a}; the z axis carries + b'_i in its first three
-  __shared__ grid_d4 s_tab[3][kSlabMaxR];
+  __shared__ map_d4 s_tab[3][kSlabMaxR];
 
   const int tid = threadIdx.x;
-  const int R = a.R, R4 = R >> 2;
-  const Slab blk = slab_of_block(a.nslab, a.slab, R);
-  const int64_t i = blk.i;
+  const int R = a.src.R, R4 = R >> 2;
+  const Slab blk = slab_of_block(a.src.nslab, a.src.slab, R);
   const int sb = blk.sb, se = blk.se;
   const int64_t R3 = (int64_t)R * R * R;
-  float *__restrict__ out = a.out + i * 3 * R3;
+  float *__restrict__ out = a.out + blk.i * 3 * R3;
 
-  const int64_t depth_len = a.depth_len;
-  const SlabFrame fr = slab_frame(depth_len, a.offsets, a.headers, a.grid, i, true);
-  const int left = fr.left, top = fr.top, right = fr.right, bottom = fr.bottom;
-  const int64_t bw = fr.bw;
-  const float ox = fr.ox, oy = fr.oy, oz = fr.oz, vl = fr.vl, td = fr.td;
-  if (blk.first() && tid == 0 && a.status) a.status[i] = fr.status;
+  const SlabFrame fr = slab_head<true>(a.src, blk, a.grid);
+  if (slab_bad_frame<grid_f4>(fr, blk, a.status, out, R, (int64_t)(se - sb) * R * R4, tid)) return;
 
-  if (fr.status != TSDF_FRAME_OK) {   // (uniform)
-    slab_zero_fill<grid_f4>(out, R, sb, (int64_t)(se - sb) * R * R4, tid);
-    return;
-  }
-
-  const double *__restrict__ xf = a.xforms + 24 * i;
-  for (int e = tid; e < 3 * R; e += kSlabWG) {
-    const int ax = e / R, idx = e - ax * R;
-    const float o = ax == 0 ? ox : ax == 1 ? oy : oz;
-    const double prod = (double)idx * (double)vl;
-    const double vp = (double)o + prod;                       // v'_a
-    grid_d4 t;
-    t.x = xf[12 + ax] * vp;                                   // A'_0a v'_a
-    t.y = xf[16 + ax] * vp;
-    t.z = xf[20 + ax] * vp;
-    if (ax == 2) {                                            // (A'_i2 z' + b'_i)
-      t.x = t.x + xf[15];
-      t.y = t.y + xf[19];
-      t.z = t.z + xf[23];
-    }
-    t.w = vp - xf[4 * ax + 3];                                // v'_a - b_a
-    s_tab[ax][idx] = t;
-  }
-
-  // per-frame constants of the distance terms
-  const double F = a.focal, cx = a.cx, cy = a.cy;
-  const double iF = 1.0 / F, it = 1.0 / (double)td;
-  const double p00 = xf[0] * iF, p10 = xf[4] * iF, p20 = xf[8] * iF;
-  const double g00 = -p00, g10 = -p10, g20 = -p20;                           // g_i0 = -(A_i0 * iF)
-  const double g01 = xf[1] * iF, g11 = xf[5] * iF, g21 = xf[9] * iF;         // g_i1 = A_i1 * iF
-  const double a02 = xf[2], a12 = xf[6], a22 = xf[10];
-  const float eps = a.eps;
-  const float *__restrict__ d = a.depth + fr.off0;
+  const double *__restrict__ xf = a.xforms + 24 * blk.i;
+  map_fill_tab(s_tab, xf, fr.ox, fr.oy, fr.oz, fr.vl, R, tid);
+  const MapK k = map_consts(xf, a.src, a.eps, fr);
+  const float *__restrict__ d = a.src.depth + fr.off0;
   __syncthreads();
 
   const int nit = (se - sb) * R * R4;
@@ -117,57 +76,14 @@ __global__ __launch_bounds__(kSlabWG) void tsdf_aug_grid_kernel(AugGridArgs a) {
     const int f4 = (item % R4) * 4;
     const int t1 = item / R4;
     const int y = t1 % R, sl = sb + t1 / R;
-    const grid_d4 ty = s_tab[1][y];
-    const grid_d4 ts = s_tab[LAYOUT == 0 ? 2 : 0][sl];     // the slice's axis: z (czyx) or x (cxyz)
-    grid_f4 o0 = {0.f, 0.f, 0.f, 0.f}, o1 = o0, o2 = o0;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const grid_d4 tf = s_tab[LAYOUT == 0 ? 0 : 2][f4 + j];   // the lane's own axis
-      const grid_d4 tx = LAYOUT == 0 ? tf : ts, tz = LAYOUT == 0 ? ts : tf;
-      // v = T^-1(v') = (A'_i0 x' + A'_i1 y') + (A'_i2 z' + b'_i)
-      const double s0 = tx.x + ty.x, s1 = tx.y + ty.y, s2 = tx.z + ty.z;
-      const double vx = s0 + tz.x, vy = s1 + tz.y, vz = s2 + tz.z;
-      const double q = -F / vz;
-      const double mx = vx * q, my = (-vy) * q;
-      const int px = trunc_i32(mx + cx), py = trunc_i32(my + cy);
-      float v0 = 0.f, v1 = 0.f, v2 = 0.f;
-      if (px >= left && px < right && py >= top && py < bottom) {
-        const float pd = d[(int64_t)(py - top) * bw + (px - left)];
-        if (__builtin_fabsf(pd) >= eps) {                     // NaN is invalid
-          const double dxi = (double)px - cx, dyi = (double)py - cy, pd64 = (double)pd;
-          const double c0 = __builtin_fma(g00, dxi, __builtin_fma(g01, dyi, a02));
-          const double c1 = __builtin_fma(g10, dxi, __builtin_fma(g11, dyi, a12));
-          const double c2 = __builtin_fma(g20, dxi, __builtin_fma(g21, dyi, a22));
-          const double u0 = __builtin_fma(pd64, c0, tx.w);    // v'_i - w'_i, mm
-          const double u1 = __builtin_fma(pd64, c1, ty.w);
-          const double u2 = __builtin_fma(pd64, c2, tz.w);
-          const double t0 = u0 * it, t1v = u1 * it, t2 = u2 * it;
-          const double xx = t0 * t0;
-          const double sq = __builtin_fma(t2, t2, __builtin_fma(t1v, t1v, xx));
-          const bool nearv = sq <= 1.0;
-          double m0 = __builtin_fabs(t0), m1 = __builtin_fabs(t1v), m2 = __builtin_fabs(t2);
-          if (!(m0 < 1.0)) m0 = 1.0;                          // min(|t|, 1); a NaN distance counts as far
-          if (!(m1 < 1.0)) m1 = 1.0;
-          if (!(m2 < 1.0)) m2 = 1.0;
-          if (!nearv) m0 = m1 = m2 = 1.0;
-          if (u2 < 0.0) {
-            m0 = -m0;
-            m1 = -m1;
-            m2 = -m2;
-          }
-          v0 = (float)m0;
-          v1 = (float)m1;
-          v2 = (float)m2;
-        }
-      }
-      o0[j] = v0;
-      o1[j] = v1;
-      o2[j] = v2;
-    }
+    const map_d4 ty = s_tab[1][y];
+    const map_d4 ts = s_tab[LAYOUT == 0 ? 2 : 0][sl];      // the slice's axis: z (czyx) or x (cxyz)
+    float v0[4], v1[4], v2[4];
+    map_quad<LAYOUT>(s_tab, k, d, ty, ts, f4, v0, v1, v2);
     const int64_t e = ((int64_t)sl * R + y) * R + f4;   // o[c][slow][y][fast]
-    *reinterpret_cast<grid_f4 *>(out + e) = o0;
-    *reinterpret_cast<grid_f4 *>(out + R3 + e) = o1;
-    *reinterpret_cast<grid_f4 *>(out + 2 * R3 + e) = o2;
+    *reinterpret_cast<grid_f4 *>(out + e) = grid_f4{v0[0], v0[1], v0[2], v0[3]};
+    *reinterpret_cast<grid_f4 *>(out + R3 + e) = grid_f4{v1[0], v1[1], v1[2], v1[3]};
+    *reinterpret_cast<grid_f4 *>(out + 2 * R3 + e) = grid_f4{v2[0], v2[1], v2[2], v2[3]};
   }
 }
 
@@ -205,27 +121,16 @@ int tsdf_voxelize_aug_grid_hip(const float *d_depth, int64_t depth_len, const in
   // arguments first, then the device, then the launch
   if (n < 0) return TSDF_ERR_INVALID_ARG;
   if (n == 0) return TSDF_OK;
-  if (!d_depth || !d_offsets || !d_headers || !d_xforms || !d_grid || !d_out_tsdf || depth_len < 0) return TSDF_ERR_INVALID_ARG;
-  if (slab_bad_shape(R, layout)) return TSDF_ERR_INVALID_ARG;
-  if (misaligned(d_xforms, 7) || misaligned(d_out_tsdf, 15)) return TSDF_ERR_INVALID_ARG;
-  if (!cam_ok(cam)) return TSDF_ERR_INVALID_ARG;
+  if (slab_bad_shape(R, layout)) return TSDF_ERR_INVALID_ARG;   // after n == 0, unlike the later libraries: frozen
+  if (!d_xforms || !d_grid || !d_out_tsdf || misaligned(d_xforms, 7) || misaligned(d_out_tsdf, 15))
+    return TSDF_ERR_INVALID_ARG;
   SlabPlan plan;
-  if (!slab_plan(n, R, 4, plan)) return TSDF_ERR_INVALID_ARG;   // a launch holds fewer than 2^32 work-items
+  if (!slab_args_ok(d_depth, depth_len, d_offsets, d_headers, n, nullptr, n, R, 4, cam, plan)) return TSDF_ERR_INVALID_ARG;
   const int rc = check_device(nullptr);
   if (rc != TSDF_OK) return rc;
   if (!cam) cam = &kDefaultCam;
   AugGridArgs a;
-  a.depth = d_depth;
-  a.depth_len = depth_len;
-  a.offsets = d_offsets;
-  a.headers = d_headers;
-  a.n = n;
-  a.R = R;
-  a.slab = plan.slab;
-  a.nslab = plan.nslab;
-  a.focal = cam->focal;
-  a.cx = cam->cx;
-  a.cy = cam->cy;
+  a.src = slab_src(d_depth, depth_len, d_offsets, d_headers, n, nullptr, n, R, *cam, plan);
   a.eps = cam->invalid_eps;
   a.xforms = d_xforms;
   a.grid = d_grid;

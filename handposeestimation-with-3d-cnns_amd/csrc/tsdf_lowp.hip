@@ -50,16 +50,8 @@ constexpr int kNarrowMaxBlocks = 1 << 16;   // the narrowing kernel strides over
 typedef float lowp_f4 __attribute__((ext_vector_type(4)));
 
 struct LowpArgs {
-  const float *depth;
-  int64_t depth_len;
-  const int64_t *offsets;   // [n_src + 1]
-  const int32_t *headers;   // [n_src][6]
-  int64_t n_src;
-  const int64_t *index;     // [n] or null
-  int n, R;
-  int slab;    // slices per workgroup
-  int nslab;   // workgroups per batch position
-  double focal, cx, cy, inv_focal;
+  SlabSrc src;
+  double inv_focal;
   float eps;
   const float *grid;        // [n_src][8]
   uint16_t *out;            // [n][3][R][R][R]
@@ -77,30 +69,21 @@ __global__ __launch_bounds__(kSlabWG) void tsdf_grid_lowp_kernel(LowpArgs a) {
   __shared__ float s_neg[kSlabMaxR];                       // f32_round_up(-v_z)
 
   const int tid = threadIdx.x;
-  const int R = a.R, RV = R / V;
-  const Slab blk = slab_of_block(a.nslab, a.slab, R);
-  const int64_t i = blk.i;
+  const int R = a.src.R, RV = R / V;
+  const Slab blk = slab_of_block(a.src.nslab, a.src.slab, R);
   const int sb = blk.sb, se = blk.se;
   const int64_t R3 = (int64_t)R * R * R;
-  uint16_t *__restrict__ out = a.out + i * 3 * R3;
+  uint16_t *__restrict__ out = a.out + blk.i * 3 * R3;
 
-  // the source frame; outside the tables it is a bad header and nothing of it is read
-  const int64_t g = a.index ? a.index[i] : i;
-  const bool src_ok = g >= 0 && g < a.n_src;
-  const int64_t gs = src_ok ? g : 0, depth_len = a.depth_len;
-  const SlabFrame fr = slab_frame(depth_len, a.offsets, a.headers, a.grid, gs, src_ok);
+  const SlabFrame fr = slab_head<true>(a.src, blk, a.grid);
   const int left = fr.left, top = fr.top, right = fr.right, bottom = fr.bottom;
   const int64_t bw = fr.bw;
   const float ox = fr.ox, oy = fr.oy, oz = fr.oz, vl = fr.vl, td = fr.td;
-  if (blk.first() && tid == 0 && a.status) a.status[i] = fr.status;
-
-  if (fr.status != TSDF_FRAME_OK) {   // (uniform)
-    slab_zero_fill<lowp_u4>(out, R, sb, (int64_t)(se - sb) * R * R / 8, tid);   // R * R is a multiple of 16
-    return;
-  }
+  // R * R is a multiple of 16
+  if (slab_bad_frame<lowp_u4>(fr, blk, a.status, out, R, (int64_t)(se - sb) * R * R / 8, tid)) return;
 
   // per-frame constants (frame.inc::make_voxk) and per-axis tables (frame.inc::fill_tables)
-  const double F = a.focal, cx = a.cx, cy = a.cy;
+  const double F = a.src.focal, cx = a.src.cx, cy = a.src.cy;
   const double it = 1.0 / (double)td;
   const double kq = a.inv_focal * it;
   for (int e = tid; e < 3 * R; e += kSlabWG) {
@@ -122,7 +105,7 @@ __global__ __launch_bounds__(kSlabWG) void tsdf_grid_lowp_kernel(LowpArgs a) {
     }
   }
   const float eps = a.eps;
-  const float *__restrict__ d = a.depth + fr.off0;
+  const float *__restrict__ d = a.src.depth + fr.off0;
   __syncthreads();
 
   const int nit = (se - sb) * R * RV;
@@ -227,7 +210,7 @@ __global__ __launch_bounds__(kSlabWG) void tsdf_lowp_narrow_kernel(NarrowArgs a)
 
 template <int LAYOUT, bool BF16>
 void launch_grid(const LowpArgs &a, int64_t blocks, hipStream_t s) {
-  if (a.R % 8 == 0)
+  if (a.src.R % 8 == 0)
     hipLaunchKernelGGL((tsdf_grid_lowp_kernel<LAYOUT, BF16, 8>), dim3((unsigned)blocks), dim3(kSlabWG), 0, s, a);
   else
     hipLaunchKernelGGL((tsdf_grid_lowp_kernel<LAYOUT, BF16, 4>), dim3((unsigned)blocks), dim3(kSlabWG), 0, s, a);
@@ -247,29 +230,15 @@ int tsdf_voxelize_grid_lowp_hip(const float *d_depth, int64_t depth_len, const i
   if (slab_bad_shape(R, layout)) return TSDF_ERR_INVALID_ARG;
   if (bad_dtype(dtype)) return TSDF_ERR_INVALID_ARG;
   if (n == 0) return TSDF_OK;
-  if (!d_depth || !d_offsets || !d_headers || !d_grid || !d_out_tsdf || depth_len < 0) return TSDF_ERR_INVALID_ARG;
-  if (n_src < 1 || (!d_index && n_src != n)) return TSDF_ERR_INVALID_ARG;
-  if (misaligned(d_out_tsdf, 15)) return TSDF_ERR_INVALID_ARG;
-  if (!cam_ok(cam)) return TSDF_ERR_INVALID_ARG;
+  if (!d_grid || !d_out_tsdf || misaligned(d_out_tsdf, 15)) return TSDF_ERR_INVALID_ARG;
   SlabPlan plan;
-  if (!slab_plan(n, R, R % 8 == 0 ? 8 : 4, plan)) return TSDF_ERR_INVALID_ARG;   // a launch holds fewer than 2^32 work-items
+  if (!slab_args_ok(d_depth, depth_len, d_offsets, d_headers, n_src, d_index, n, R, R % 8 == 0 ? 8 : 4, cam, plan))
+    return TSDF_ERR_INVALID_ARG;
   const int rc = check_device(nullptr);
   if (rc != TSDF_OK) return rc;
   if (!cam) cam = &kDefaultCam;
   LowpArgs a;
-  a.depth = d_depth;
-  a.depth_len = depth_len;
-  a.offsets = d_offsets;
-  a.headers = d_headers;
-  a.n_src = n_src;
-  a.index = d_index;
-  a.n = n;
-  a.R = R;
-  a.slab = plan.slab;
-  a.nslab = plan.nslab;
-  a.focal = cam->focal;
-  a.cx = cam->cx;
-  a.cy = cam->cy;
+  a.src = slab_src(d_depth, depth_len, d_offsets, d_headers, n_src, d_index, n, R, *cam, plan);
   a.inv_focal = 1.0 / cam->focal;
   a.eps = cam->invalid_eps;
   a.grid = d_grid;

@@ -6,9 +6,9 @@
 // host preamble every library here has from device.inc, the device primitives from prim.inc, the slab scaffold it shares
 // with tsdf_auggrid.hip and tsdf_lowp.hip from slab.inc, the store side it shares with tsdf_lowp.hip from narrow.inc and
 // the placement's arithmetic — the crop pass, the wave butterfly, the float32 glue and the degenerate rule — from
-// place.inc, which it shares with tsdf_mapstep.hip.  The augmented voxel arithmetic (tsdf_auggrid.hip::
-// tsdf_aug_grid_kernel) is RESTATED here operation for operation; nothing of the product's other .inc files is included,
-// and there is no device global: every launch is self-contained.
+// place.inc, which it shares with tsdf_mapstep.hip.  The augmented voxel arithmetic — the per-axis table, the per-frame
+// constants and the four-voxel chain — is mapvox.inc's, the text tsdf_auggrid.hip::tsdf_aug_grid_kernel runs too; nothing
+// of the product's other .inc files is included, and there is no device global: every launch is self-contained.
 //
 // tsdf_map_place_kernel: one workgroup of 1024 threads (16 wave64) per batch position, a grid-stride loop over positions
 // when n exceeds the grid — the shape of tsdf_obb_kernel.  Per position:
@@ -29,7 +29,7 @@
 // one batch position.  It
 //   1. resolves its source frame and checks the frame's header and the POSITION's grid row (all uniform); a position that
 //      is not OK has its slab zero-filled and workgroup 0 of the position writes the status;
-//   2. tabulates the per-axis terms of tsdf_aug_grid_kernel (3 x R entries of 32 bytes in LDS);
+//   2. tabulates the per-axis terms (mapvox.inc::map_fill_tab: 3 x R entries of 32 bytes in LDS);
 //   3. walks its slab in items of V consecutive voxels of the fastest axis (V = 8 when R % 8 == 0, else 4), one item per
 //      lane and pass, as V / 4 quads: a quad projects its four voxels and issues their four gathers (always in bounds: a
 //      rejected voxel reads the crop's first pixel) before the distance terms of the first one, then narrows its 3 x 4
@@ -53,12 +53,11 @@ namespace {
 #include "slab.inc"     // workgroup <-> slab, the frame's header and grid row, zero-fill, host sizing
 #include "narrow.inc"   // narrow2, store_vol, Piece, bad_dtype: the 2-byte store side
 #include "place.inc"    // place_crop, place_glue, Placed: the placement's arithmetic, shared with tsdf_mapstep.hip
+#include "mapvox.inc"   // map_fill_tab, map_consts, map_quad: the mapped voxel arithmetic, shared with tsdf_auggrid.hip
 
 constexpr int kPlaceWG = 1024;               // threads per workgroup of the placement
 constexpr int kPlaceWaves = kPlaceWG / 64;   // 16 wave64
 constexpr int kPlaceMaxBlocks = 1 << 16;     // positions beyond the grid are reached by the grid-stride loop
-
-typedef double map_d4 __attribute__((ext_vector_type(4)));
 
 struct PlaceArgs {
   const float *depth;
@@ -128,96 +127,13 @@ __global__ __launch_bounds__(kPlaceWG) void tsdf_map_place_kernel(PlaceArgs a) {
 }
 
 struct MapLowpArgs {
-  const float *depth;
-  int64_t depth_len;
-  const int64_t *offsets;   // [n_src + 1]
-  const int32_t *headers;   // [n_src][6]
-  int64_t n_src;
-  const int64_t *index;     // [n] or null
-  int n, R;
-  int slab;    // slices per workgroup
-  int nslab;   // workgroups per batch position
-  double focal, cx, cy;
+  SlabSrc src;
   float eps;
   const double *xforms;     // [n][24]
   const float *grid;        // [n][8]
   uint16_t *out;            // [n][3][R][R][R]
   int32_t *status;          // [n] or null
 };
-
-// the per-frame constants of the distance terms (tsdf_aug_grid_kernel's)
-struct MapK {
-  double F, cx, cy, it;
-  double g00, g10, g20, g01, g11, g21, a02, a12, a22;
-  float eps;
-  int left, top, right, bottom;
-  int64_t bw;
-};
-
-// Four consecutive voxels of the fastest axis starting at grid index f4, in the row y of slice sl: the float32 values
-// of tsdf_aug_grid_kernel, operation for operation.  s_tab: [axis][index] = {A'_0a v'_a, A'_1a v'_a, A'_2a v'_a,
-// v'_a - b_a}, the z axis with + b'_i in its first three.
-template <int LAYOUT>
-__device__ __forceinline__ void map_quad(const map_d4 (&s_tab)[3][kSlabMaxR], const MapK &k, const float *__restrict__ d,
-                                         const map_d4 &ty, const map_d4 &ts, int f4, float (&v0)[4], float (&v1)[4],
-                                         float (&v2)[4]) {
-#pragma clang fp contract(off)
-  // ---- project the four voxels and gather their depths ----
-  int px[4], py[4];
-  float pd[4];
-  bool inb[4];
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    const map_d4 tf = s_tab[LAYOUT == 0 ? 0 : 2][f4 + j];   // the lane's own axis
-    const map_d4 tx = LAYOUT == 0 ? tf : ts, tz = LAYOUT == 0 ? ts : tf;
-    // v = T^-1(v') = (A'_i0 x' + A'_i1 y') + (A'_i2 z' + b'_i)
-    const double s0 = tx.x + ty.x, s1 = tx.y + ty.y, s2 = tx.z + ty.z;
-    const double vx = s0 + tz.x, vy = s1 + tz.y, vz = s2 + tz.z;
-    const double q = -k.F / vz;                              // IEEE division
-    const double mx = vx * q, my = (-vy) * q;
-    px[j] = trunc_i32(mx + k.cx);
-    py[j] = trunc_i32(my + k.cy);
-    inb[j] = px[j] >= k.left && px[j] < k.right && py[j] >= k.top && py[j] < k.bottom;
-    const int64_t at = inb[j] ? (int64_t)(py[j] - k.top) * k.bw + (px[j] - k.left) : 0;   // the load is always in bounds
-    pd[j] = d[at];
-  }
-  // ---- the distance terms ----
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    const double wf = s_tab[LAYOUT == 0 ? 0 : 2][f4 + j].w;
-    const double wx = LAYOUT == 0 ? wf : ts.w, wz = LAYOUT == 0 ? ts.w : wf;
-    float r0 = 0.f, r1 = 0.f, r2 = 0.f;
-    if (inb[j] && __builtin_fabsf(pd[j]) >= k.eps) {         // NaN is invalid
-      const double dxi = (double)px[j] - k.cx, dyi = (double)py[j] - k.cy, pd64 = (double)pd[j];
-      const double c0 = __builtin_fma(k.g00, dxi, __builtin_fma(k.g01, dyi, k.a02));
-      const double c1 = __builtin_fma(k.g10, dxi, __builtin_fma(k.g11, dyi, k.a12));
-      const double c2 = __builtin_fma(k.g20, dxi, __builtin_fma(k.g21, dyi, k.a22));
-      const double u0 = __builtin_fma(pd64, c0, wx);         // v'_i - w'_i, mm
-      const double u1 = __builtin_fma(pd64, c1, ty.w);
-      const double u2 = __builtin_fma(pd64, c2, wz);
-      const double t0 = u0 * k.it, t1 = u1 * k.it, t2 = u2 * k.it;
-      const double xx = t0 * t0;
-      const double sq = __builtin_fma(t2, t2, __builtin_fma(t1, t1, xx));
-      const bool nearv = sq <= 1.0;
-      double m0 = __builtin_fabs(t0), m1 = __builtin_fabs(t1), m2 = __builtin_fabs(t2);
-      if (!(m0 < 1.0)) m0 = 1.0;                             // min(|t|, 1); a NaN distance counts as far
-      if (!(m1 < 1.0)) m1 = 1.0;
-      if (!(m2 < 1.0)) m2 = 1.0;
-      if (!nearv) m0 = m1 = m2 = 1.0;
-      if (u2 < 0.0) {
-        m0 = -m0;
-        m1 = -m1;
-        m2 = -m2;
-      }
-      r0 = (float)m0;
-      r1 = (float)m1;
-      r2 = (float)m2;
-    }
-    v0[j] = r0;
-    v1[j] = r1;
-    v2[j] = r2;
-  }
-}
 
 // V = voxels per lane and item (8: 16-byte stores, 4: 8-byte stores)
 template <int LAYOUT, bool BF16, int V>
@@ -227,58 +143,20 @@ __global__ __launch_bounds__(kSlabWG) void tsdf_map_grid_lowp_kernel(MapLowpArgs
   __shared__ map_d4 s_tab[3][kSlabMaxR];
 
   const int tid = threadIdx.x;
-  const int R = a.R, RV = R / V;
-  const Slab blk = slab_of_block(a.nslab, a.slab, R);
-  const int64_t i = blk.i;
+  const int R = a.src.R, RV = R / V;
+  const Slab blk = slab_of_block(a.src.nslab, a.src.slab, R);
   const int sb = blk.sb, se = blk.se;
   const int64_t R3 = (int64_t)R * R * R;
-  uint16_t *__restrict__ out = a.out + i * 3 * R3;
+  uint16_t *__restrict__ out = a.out + blk.i * 3 * R3;
 
-  // the source frame; outside the tables it is a bad header and nothing of it is read.  The grid row is the POSITION's.
-  const int64_t g = a.index ? a.index[i] : i;
-  const bool src_ok = g >= 0 && g < a.n_src;
-  const int64_t gs = src_ok ? g : 0, depth_len = a.depth_len;
-  const SlabFrame fr = slab_frame_row(depth_len, a.offsets, a.headers, a.grid + 8 * i, gs, src_ok);
-  const float ox = fr.ox, oy = fr.oy, oz = fr.oz, vl = fr.vl, td = fr.td;
-  if (blk.first() && tid == 0 && a.status) a.status[i] = fr.status;
+  const SlabFrame fr = slab_head<false>(a.src, blk, a.grid);   // the grid row is the POSITION's
+  // R * R is a multiple of 16
+  if (slab_bad_frame<lowp_u4>(fr, blk, a.status, out, R, (int64_t)(se - sb) * R * R / 8, tid)) return;
 
-  if (fr.status != TSDF_FRAME_OK) {   // (uniform)
-    slab_zero_fill<lowp_u4>(out, R, sb, (int64_t)(se - sb) * R * R / 8, tid);   // R * R is a multiple of 16
-    return;
-  }
-
-  const double *__restrict__ xf = a.xforms + 24 * i;
-  for (int e = tid; e < 3 * R; e += kSlabWG) {
-    const int ax = e / R, idx = e - ax * R;
-    const float o = ax == 0 ? ox : ax == 1 ? oy : oz;
-    const double prod = (double)idx * (double)vl;
-    const double vp = (double)o + prod;                       // v'_a
-    map_d4 t;
-    t.x = xf[12 + ax] * vp;                                   // A'_0a v'_a
-    t.y = xf[16 + ax] * vp;
-    t.z = xf[20 + ax] * vp;
-    if (ax == 2) {                                            // (A'_i2 z' + b'_i)
-      t.x = t.x + xf[15];
-      t.y = t.y + xf[19];
-      t.z = t.z + xf[23];
-    }
-    t.w = vp - xf[4 * ax + 3];                                // v'_a - b_a
-    s_tab[ax][idx] = t;
-  }
-
-  // per-frame constants of the distance terms
-  MapK k;
-  k.F = a.focal, k.cx = a.cx, k.cy = a.cy;
-  const double iF = 1.0 / k.F;
-  k.it = 1.0 / (double)td;
-  const double p00 = xf[0] * iF, p10 = xf[4] * iF, p20 = xf[8] * iF;
-  k.g00 = -p00, k.g10 = -p10, k.g20 = -p20;                   // g_i0 = -(A_i0 * iF)
-  k.g01 = xf[1] * iF, k.g11 = xf[5] * iF, k.g21 = xf[9] * iF; // g_i1 = A_i1 * iF
-  k.a02 = xf[2], k.a12 = xf[6], k.a22 = xf[10];
-  k.eps = a.eps;
-  k.left = fr.left, k.top = fr.top, k.right = fr.right, k.bottom = fr.bottom;
-  k.bw = fr.bw;
-  const float *__restrict__ d = a.depth + fr.off0;
+  const double *__restrict__ xf = a.xforms + 24 * blk.i;
+  map_fill_tab(s_tab, xf, fr.ox, fr.oy, fr.oz, fr.vl, R, tid);
+  const MapK k = map_consts(xf, a.src, a.eps, fr);
+  const float *__restrict__ d = a.src.depth + fr.off0;
   __syncthreads();
 
   const int nit = (se - sb) * R * RV;
@@ -309,7 +187,7 @@ __global__ __launch_bounds__(kSlabWG) void tsdf_map_grid_lowp_kernel(MapLowpArgs
 
 template <int LAYOUT, bool BF16>
 void launch_grid(const MapLowpArgs &a, int64_t blocks, hipStream_t s) {
-  if (a.R % 8 == 0)
+  if (a.src.R % 8 == 0)
     hipLaunchKernelGGL((tsdf_map_grid_lowp_kernel<LAYOUT, BF16, 8>), dim3((unsigned)blocks), dim3(kSlabWG), 0, s, a);
   else
     hipLaunchKernelGGL((tsdf_map_grid_lowp_kernel<LAYOUT, BF16, 4>), dim3((unsigned)blocks), dim3(kSlabWG), 0, s, a);
@@ -370,30 +248,16 @@ int tsdf_voxelize_map_grid_lowp_hip(const float *d_depth, int64_t depth_len, con
   if (slab_bad_shape(R, layout)) return TSDF_ERR_INVALID_ARG;
   if (bad_dtype(dtype)) return TSDF_ERR_INVALID_ARG;
   if (n == 0) return TSDF_OK;
-  if (!d_depth || !d_offsets || !d_headers || !d_xforms || !d_grid || !d_out_tsdf || depth_len < 0)
+  if (!d_xforms || !d_grid || !d_out_tsdf || misaligned(d_xforms, 7) || misaligned(d_out_tsdf, 15))
     return TSDF_ERR_INVALID_ARG;
-  if (n_src < 1 || (!d_index && n_src != n)) return TSDF_ERR_INVALID_ARG;
-  if (misaligned(d_xforms, 7) || misaligned(d_out_tsdf, 15)) return TSDF_ERR_INVALID_ARG;
-  if (!cam_ok(cam)) return TSDF_ERR_INVALID_ARG;
   SlabPlan plan;
-  if (!slab_plan(n, R, R % 8 == 0 ? 8 : 4, plan)) return TSDF_ERR_INVALID_ARG;   // a launch holds fewer than 2^32 work-items
+  if (!slab_args_ok(d_depth, depth_len, d_offsets, d_headers, n_src, d_index, n, R, R % 8 == 0 ? 8 : 4, cam, plan))
+    return TSDF_ERR_INVALID_ARG;
   const int rc = check_device(nullptr);
   if (rc != TSDF_OK) return rc;
   if (!cam) cam = &kDefaultCam;
   MapLowpArgs a;
-  a.depth = d_depth;
-  a.depth_len = depth_len;
-  a.offsets = d_offsets;
-  a.headers = d_headers;
-  a.n_src = n_src;
-  a.index = d_index;
-  a.n = n;
-  a.R = R;
-  a.slab = plan.slab;
-  a.nslab = plan.nslab;
-  a.focal = cam->focal;
-  a.cx = cam->cx;
-  a.cy = cam->cy;
+  a.src = slab_src(d_depth, depth_len, d_offsets, d_headers, n_src, d_index, n, R, *cam, plan);
   a.eps = cam->invalid_eps;
   a.xforms = d_xforms;
   a.grid = d_grid;

@@ -1077,6 +1077,26 @@ def invert_xforms(xforms: torch.Tensor) -> torch.Tensor:
     return torch.cat([xforms[:, 12:], xforms[:, :12]], dim=1)
 
 
+def _source(depth, offsets, headers, index, res, layout):
+    """The one validation of the source tables with an optional index (int64[n] on the GPU: batch position i takes source
+    frame index[i]; without it the batch is the n_src frames).  Returns (device, n_src, n, R)."""
+    dev, n_src, R = _pack(_lib.load(), depth, offsets, headers, res, layout)
+    n = n_src
+    if index is not None:
+        _dev_check("index", index, torch.int64, dev)
+        if index.dim() != 1:
+            raise ValueError("index must have shape [n]")
+        n = int(index.shape[0])
+        if n and not n_src:
+            raise ValueError("index needs at least one source frame")
+    return dev, n_src, n, R
+
+
+def _src_head(depth, offsets, headers, n_src, index, n, R) -> list:
+    """The eight arguments every indexed extension entry starts with."""
+    return [depth.data_ptr(), depth.numel(), offsets.data_ptr(), headers.data_ptr(), n_src, _ptr(index), n, R]
+
+
 _LOWP_DTYPES = {torch.float16: _lib.TSDF_LOWP_F16, torch.bfloat16: _lib.TSDF_LOWP_BF16}
 
 
@@ -1107,22 +1127,14 @@ def voxelize_grid_lowp(depth: torch.Tensor, offsets: torch.Tensor, headers: torc
     a zero volume with status 0.  One launch on the current stream, no synchronisation."""
     code = _lowp_dtype(dtype)
     P = _lib.load_lowp()
-    dev, n_src, R = _pack(_lib.load(), depth, offsets, headers, res, layout)
+    dev, n_src, n, R = _source(depth, offsets, headers, index, res, layout)
     _shaped("grid", grid, (n_src, 8), torch.float32, dev)
-    n = n_src
-    if index is not None:
-        _dev_check("index", index, torch.int64, dev)
-        if index.dim() != 1:
-            raise ValueError("index must have shape [n]")
-        n = int(index.shape[0])
-        if n and not n_src:
-            raise ValueError("index needs at least one source frame")
     tsdf = _out("out", out, (n, 3, R, R, R), dtype, dev)
     st = _out("status", None, (n,), torch.int32, dev)
     if n:
         _call(dev, P.tsdf_voxelize_grid_lowp_hip,
-              [depth.data_ptr(), depth.numel(), offsets.data_ptr(), headers.data_ptr(), n_src, _ptr(index), n, R, _cam(cam),
-               _lib.LAYOUTS[layout], code, None, grid.data_ptr(), tsdf.data_ptr(), st.data_ptr()], 11)
+              _src_head(depth, offsets, headers, n_src, index, n, R) +
+              [_cam(cam), _lib.LAYOUTS[layout], code, None, grid.data_ptr(), tsdf.data_ptr(), st.data_ptr()], 11)
     return tsdf, st
 
 
@@ -1134,8 +1146,7 @@ def voxelize_lowp(depth: torch.Tensor, offsets: torch.Tensor, headers: torch.Ten
     :func:`aabb`'s, bit for bit those of :func:`voxelize`; ``tsdf`` is ``dtype[n,3,R,R,R]``."""
     _lowp_dtype(dtype)
     ab = aabb(depth, offsets, headers, res=res, cam=cam)
-    rows = torch.cat([ab.ori, ab.grid[:, 4:6], torch.zeros_like(ab.ori)], dim=1)
-    tsdf, _ = voxelize_grid_lowp(depth, offsets, headers, rows, res=res, layout=layout, dtype=dtype, cam=cam)
+    tsdf, _ = voxelize_grid_lowp(depth, offsets, headers, _aabb_rows(ab), res=res, layout=layout, dtype=dtype, cam=cam)
     return TsdfBatch(tsdf, ab.grid[:, 3].contiguous(), ab.grid[:, :3].contiguous(), ab.status)
 
 
@@ -1178,25 +1189,17 @@ def voxelize_grid_accurate(depth: torch.Tensor, offsets: torch.Tensor, headers: 
     pixel gets a zero volume with status 0.  One launch on the current stream, no synchronisation.  A voxel within the
     truncation distance of the camera plane is searched over the whole crop: keep such grids to small crops."""
     A = _lib.load_accurate()
-    dev, n_src, R = _pack(_lib.load(), depth, offsets, headers, res, layout)
+    dev, n_src, n, R = _source(depth, offsets, headers, index, res, layout)
     _shaped("grid", grid, (n_src, 8), torch.float32, dev)
-    n = n_src
-    if index is not None:
-        _dev_check("index", index, torch.int64, dev)
-        if index.dim() != 1:
-            raise ValueError("index must have shape [n]")
-        n = int(index.shape[0])
-        if n and not n_src:
-            raise ValueError("index needs at least one source frame")
     tsdf = _out("out", out, (n, 3, R, R, R), torch.float32, dev)
     st = _out("status", None, (n,), torch.int32, dev)
     near = _out("nearest", None, (n, R, R, R), torch.int32, dev) if nearest else None
     if n:
         c = cam if cam is not None else _lib.default_cam()   # the entry takes the five constants by value
         _call(dev, A.tsdf_voxelize_grid_accurate_hip,
-              [depth.data_ptr(), depth.numel(), offsets.data_ptr(), headers.data_ptr(), n_src, _ptr(index), n, R, c.focal, c.cx,
-               c.cy, c.invalid_eps, c.trunc_voxels, _lib.LAYOUTS[layout], None, grid.data_ptr(), tsdf.data_ptr(), _ptr(near),
-               st.data_ptr()], 14)
+              _src_head(depth, offsets, headers, n_src, index, n, R) +
+              [c.focal, c.cx, c.cy, c.invalid_eps, c.trunc_voxels, _lib.LAYOUTS[layout], None, grid.data_ptr(),
+               tsdf.data_ptr(), _ptr(near), st.data_ptr()], 14)
     return (tsdf, st, near) if nearest else (tsdf, st)
 
 
@@ -1222,22 +1225,6 @@ class MapGridBatch(NamedTuple):
     status: torch.Tensor  # int32[n]  (_lib.TSDF_FRAME_*)
 
 
-def _mapped(depth, offsets, headers, xforms, res, layout, index):
-    """The one validation of the entries of libtsdf_maplowp.so: the source tables, the optional index and one map per
-    batch position.  Returns (device, n_src, n, R)."""
-    dev, n_src, R = _pack(_lib.load(), depth, offsets, headers, res, layout)
-    n = n_src
-    if index is not None:
-        _dev_check("index", index, torch.int64, dev)
-        if index.dim() != 1:
-            raise ValueError("index must have shape [n]")
-        n = int(index.shape[0])
-        if n and not n_src:
-            raise ValueError("index needs at least one source frame")
-    _shaped("xforms", xforms, (n, 24), torch.float64, dev)
-    return dev, n_src, n, R
-
-
 def map_grids(depth: torch.Tensor, offsets: torch.Tensor, headers: torch.Tensor, xforms: torch.Tensor, res: int = 32,
               cam: Optional[_lib.TsdfCam] = None, index: Optional[torch.Tensor] = None,
               out: Optional[MapGridBatch] = None) -> MapGridBatch:
@@ -1254,7 +1241,8 @@ def map_grids(depth: torch.Tensor, offsets: torch.Tensor, headers: torch.Tensor,
     A position that is not OK gets an all-zero grid row and ``max_l`` 0.  One launch on the current stream, no
     synchronisation."""
     M = _lib.load_maplowp()
-    dev, n_src, n, R = _mapped(depth, offsets, headers, xforms, res, "czyx", index)
+    dev, n_src, n, R = _source(depth, offsets, headers, index, res, "czyx")
+    _shaped("xforms", xforms, (n, 24), torch.float64, dev)
     fields = (("grid", (n, 8), torch.float32), ("max_l", (n,), torch.float32), ("mid_p", (n, 3), torch.float32),
               ("status", (n,), torch.int32))
     if out is None:
@@ -1264,8 +1252,8 @@ def map_grids(depth: torch.Tensor, offsets: torch.Tensor, headers: torch.Tensor,
             _shaped("out." + name, getattr(out, name), shape, dtype, dev)
     if n:
         _call(dev, M.tsdf_map_place_hip,
-              [depth.data_ptr(), depth.numel(), offsets.data_ptr(), headers.data_ptr(), n_src, _ptr(index), n, R, _cam(cam),
-               None, xforms.data_ptr(), out.grid.data_ptr(), out.max_l.data_ptr(), out.mid_p.data_ptr(),
+              _src_head(depth, offsets, headers, n_src, index, n, R) +
+              [_cam(cam), None, xforms.data_ptr(), out.grid.data_ptr(), out.max_l.data_ptr(), out.mid_p.data_ptr(),
                out.status.data_ptr()], 9)
     return out
 
@@ -1275,14 +1263,15 @@ def _map_grid_lowp(depth, offsets, headers, xforms, grid, res, layout, dtype, ca
     allocates nothing.  Returns (volume, status or None)."""
     code = _lowp_dtype(dtype)
     M = _lib.load_maplowp()
-    dev, n_src, n, R = _mapped(depth, offsets, headers, xforms, res, layout, index)
+    dev, n_src, n, R = _source(depth, offsets, headers, index, res, layout)
+    _shaped("xforms", xforms, (n, 24), torch.float64, dev)
     _shaped("grid", grid, (n, 8), torch.float32, dev)
     tsdf = _out("out", out, (n, 3, R, R, R), dtype, dev)
     status = _out("status", None, (n,), torch.int32, dev) if want_status else None
     if n:
         _call(dev, M.tsdf_voxelize_map_grid_lowp_hip,
-              [depth.data_ptr(), depth.numel(), offsets.data_ptr(), headers.data_ptr(), n_src, _ptr(index), n, R, _cam(cam),
-               _lib.LAYOUTS[layout], code, None, xforms.data_ptr(), grid.data_ptr(), tsdf.data_ptr(), _ptr(status)], 11)
+              _src_head(depth, offsets, headers, n_src, index, n, R) +
+              [_cam(cam), _lib.LAYOUTS[layout], code, None, xforms.data_ptr(), grid.data_ptr(), tsdf.data_ptr(), _ptr(status)], 11)
     return tsdf, status
 
 
@@ -1440,10 +1429,9 @@ def map_step_head(depth: torch.Tensor, offsets: torch.Tensor, headers: torch.Ten
     if n:
         c = cam if cam is not None else _lib.default_cam()   # the entry takes the five constants by value
         _call(dev, S.tsdf_map_step_head_hip,
-              [depth.data_ptr(), depth.numel(), offsets.data_ptr(), headers.data_ptr(), n_src, _ptr(index), n, R, c.focal, c.cx,
-               c.cy, c.invalid_eps, c.trunc_voxels, centres.data_ptr(), _ptr(base), state.data_ptr(), _ptr(counters), _ptr(gt), nj,
-               1 if clamp else 0, None,
-               xf.data_ptr(), _ptr(grid), _ptr(max_l), _ptr(mid_p), _ptr(status), _ptr(gt_aug), _ptr(gt_nor), _ptr(stretch),
+              _src_head(depth, offsets, headers, n_src, index, n, R) +
+              [c.focal, c.cx, c.cy, c.invalid_eps, c.trunc_voxels, centres.data_ptr(), _ptr(base), state.data_ptr(),
+               _ptr(counters), _ptr(gt), nj, 1 if clamp else 0, None, xf.data_ptr(), _ptr(grid), _ptr(max_l), _ptr(mid_p), _ptr(status), _ptr(gt_aug), _ptr(gt_nor), _ptr(stretch),
                _ptr(rot)], 20)
     batch = MapStepBatch(xf, grid, max_l, mid_p, status, gt_aug, gt_nor)
     return (batch, stretch, rot) if return_params else batch

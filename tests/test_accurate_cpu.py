@@ -1,5 +1,5 @@
 """CPU tier of the accurate directional TSDF (include/tsdf_accurate.h): libtsdf_accurate.so as far as it goes without a GPU —
-the build rule and its resource report, the binding through _lib._EXTS2, the version, every argument check before device
+the build rule and its resource report, the binding through _lib._EXTS, the version, every argument check before device
 work —, the public names, export.preprocess_tree(tsdf=...) through stubbed hooks, and the properties of the reference
 the GPU tier compares against (tests/accurate_ref.py) on the very inputs that tier uses.  Nothing here touches a GPU."""
 import ctypes
@@ -53,8 +53,8 @@ def test_make_rules_cross_compile_for_gfx950_without_scratch():
 
 # ---- binding ----
 def test_row_binds_exactly_its_header_with_types(pkg):
-    assert "accurate" not in pkg._lib._EXTS                     # the nine of tests/test_ext_table_cpu.py stay nine
-    ext = pkg._lib._EXTS2["accurate"]
+    assert not hasattr(pkg._lib, "_EXTS2")                      # one table: tests/test_ext_table_cpu.py pins all of it
+    ext = pkg._lib._EXTS["accurate"]
     assert isinstance(ext, pkg._lib._Ext)
     assert declared_functions("tsdf_accurate.h") == WANT == sorted([ext.version_symbol, *ext.entries])
     funcs, named = exported(pkg._lib.ACCURATE_LIB_PATH)
@@ -102,6 +102,7 @@ def test_argument_validation_happens_before_device_work(pkg):
         assert call(R=R) == INVALID, R
     for layout in (-1, 2):
         assert call(layout=layout) == INVALID
+    assert call(n=0, n_src=0, R=30) == INVALID and call(n=0, n_src=0, layout=2) == INVALID   # judged before n == 0
     assert call(out=odd) == INVALID and call(nearest=odd) == INVALID   # 8-byte, not 16-byte aligned
     assert call(out=ctypes.c_void_p(68)) == INVALID and call(nearest=ctypes.c_void_p(68)) == INVALID
     # the camera comes by value and goes through the camera rule of every entry (csrc/prim.inc::cam_ok)

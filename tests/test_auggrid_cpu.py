@@ -57,6 +57,7 @@ def test_argument_validation_happens_before_device_work(pkg):
     assert call(tsdf=odd16) == -1             # 8-byte aligned only
     # n == 0 is a no-op, whatever else is passed
     assert call(n=0) == 0
+    assert call(n=0, R=30) == 0 and call(n=0, layout=2) == 0   # before R and layout are looked at (the later libraries: after)
     assert vox(null, -5, null, null, 0, 31, None, 9, null, odd8, null, odd8, null) == 0
 
     tj = G.tsdf_transform_joints_hip          # gt, xforms, n, n_joints, stream, out

@@ -1,7 +1,7 @@
-"""CPU tier of the extension table (_lib._EXTS), and the only place that pins it: the table is csrc/Makefile's EXTS, every
-row binds exactly what its header declares and its binary exports, with the types declared — an entry added to a header
-without a row of argtypes would otherwise load with ctypes' defaults, int arguments and all —, every loader hands out one
-library object, and a library of another version or none at all is an ImportError that says what to do.  What is specific
+"""CPU tier of the extension table (_lib._EXTS), and the only place that pins it: the table is csrc/Makefile's one
+`EXTS :=` line (no `EXTS +=` line anywhere) and every name has its NAME_DEPS line there, every row binds exactly what
+its header declares and its binary exports, with the types declared — an entry added to a header without a row
+of argtypes would otherwise load with ctypes' defaults, int arguments and all —, every loader hands out one library object, and a library of another version or none at all is an ImportError that says what to do.  What is specific
 to one library (its literal names and argument types, its refusals) is in that library's own file.  Nothing here touches
 a GPU."""
 import ctypes
@@ -13,7 +13,7 @@ from abi_util import declared_functions, exported
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 # csrc/Makefile's EXTS, in its order: a new library is a name here, a name there and a row in _lib._EXTS
-EXTS = ["augment", "augstep", "auggrid", "depth16", "obb", "lowp", "maplowp", "mapstep", "locate"]
+EXTS = ["augment", "augstep", "auggrid", "depth16", "obb", "lowp", "maplowp", "mapstep", "locate", "accurate"]
 
 
 def test_the_table_has_a_row_and_a_loader_per_extension(pkg):
@@ -25,6 +25,17 @@ def test_the_table_has_a_row_and_a_loader_per_extension(pkg):
         assert isinstance(ext, pkg._lib._Ext)
         assert ext.path == getattr(pkg._lib, name.upper() + "_LIB_PATH")
         assert ext.version == getattr(pkg._lib, name.upper() + "_VERSION")
+
+
+def test_one_table_one_exts_line_and_a_deps_line_per_name(pkg):
+    assert not hasattr(pkg._lib, "_EXTS2")                                                 # one table
+    lines = open(os.path.join(ROOT, "handposeestimation-with-3d-cnns_amd", "csrc", "Makefile")).read().splitlines()
+    at = [k for k, ln in enumerate(lines) if re.match(r"^EXTS := ", ln)]
+    assert len(at) == 1 and lines[at[0]].split(":=")[1].split() == EXTS
+    assert not [ln for ln in lines if re.match(r"^\s*EXTS\s*\+=", ln)]                      # and one line that fills it
+    assert min(k for k, ln in enumerate(lines) if "$(EXTS)" in ln and not ln.startswith("#")) > at[0]
+    for name in EXTS:
+        assert any(re.match(rf"^{name}_DEPS := ", ln) for ln in lines), name
 
 
 @pytest.mark.parametrize("name", EXTS)

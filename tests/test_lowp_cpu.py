@@ -91,6 +91,9 @@ def test_argument_validation_happens_before_device_work(pkg):
     # n == 0 is a no-op
     assert call(n=0, n_src=0) == 0
     assert fn(null, 0, null, null, 0, null, 0, 32, None, 0, 1, null, null, null, null) == 0
+    # but R, layout and dtype are judged before n == 0: the order of the checks is what a caller sees
+    assert call(n=0, n_src=0, R=30) == INVALID and call(n=0, n_src=0, layout=2) == INVALID
+    assert call(n=0, n_src=0, dtype=3) == INVALID
 
     nar = L.tsdf_lowp_narrow_hip
     assert nar(one, -1, 2, null, one) == INVALID

@@ -92,6 +92,8 @@ def test_argument_validation_happens_before_device_work(pkg):
             assert call(R=R) == NO_DEVICE, R
         # n == 0 is a no-op
         assert call(n=0, n_src=0) == 0
+        assert call(n=0, n_src=0, R=30) == INVALID                         # but R (layout, dtype) is judged before n == 0
+    assert vox(n=0, n_src=0, layout=2) == INVALID and vox(n=0, n_src=0, dtype=3) == INVALID
     assert place(max_l=null, mid_p=null, status=null) == NO_DEVICE         # every scalar output is optional
     assert place(n=2 ** 31 - 1, n_src=2 ** 31 - 1) == NO_DEVICE            # the placement strides over any n
     assert L.tsdf_map_place_hip(null, 0, null, null, 0, null, 0, 32, None, null, null, null, null, null, null) == 0
