@@ -41,7 +41,8 @@ from . import _lib, augment, packing, shard
 from .pca import JointPCA, fit_joint_pca
 from .voxelize import (AugmentedStep, TsdfBatch, _get_raw_stream, aabb, aug_state, aug_xforms, aug_xforms_at,  # noqa: F401
                        denormalize_joints, empty_batch, normalize_joints, obb_xforms, project_joints, voxelize,
-                       voxelize_aug, voxelize_grid_lowp, voxelize_indexed, voxelize_labels, widen_depth16, _lowp_dtype)
+                       voxelize_aug, voxelize_grid_lowp, voxelize_indexed, voxelize_labels, widen_depth16, _lowp_dtype,
+                       _place_aabb)
 
 
 def _common_depth_shift(packs: Sequence[packing.PackedFrames]) -> Optional[int]:
@@ -625,9 +626,7 @@ class ResidentLoader(_BatchLoader):
             ob = obb_xforms(rp.depth, rp.offsets, rp.headers)
             self.obb, self.obb_status = ob.xforms, ob.status
         if self.volume_dtype is not None:   # every resident frame's grid placement, once: one AABB launch over the pack
-            ab = aabb(rp.depth, rp.offsets, rp.headers, res=self.res)
-            rows = torch.cat([ab.ori, ab.grid[:, 4:6], torch.zeros_like(ab.ori)], dim=1)
-            self._lowp = (rows, ab.grid[:, 3].contiguous(), ab.grid[:, :3].contiguous(), ab.status)
+            self._lowp = _place_aabb(rp.depth, rp.offsets, rp.headers, self.res)
         if self.augment:   # the centres the maps turn about: every frame's own grid centre, one AABB launch over the pack
             mid = aabb(rp.depth, rp.offsets, rp.headers, res=self.res).grid[:, :3]
             if self.device_draws:   # the centres stay where the launch left them; one map buffer per launch in flight
@@ -1083,19 +1082,18 @@ class MSRA_Dataset(data.Dataset):
         n, dev, us = self._n, self.device, []
         if self.resident:
             rp = self._resident_packs()
-            ab = aabb(rp.depth, rp.offsets, rp.headers)
+            pl = _place_aabb(rp.depth, rp.offsets, rp.headers, rows=False)
             fr = torch.from_numpy(rp.frame).to(dev)
-            grid, st, gt = ab.grid[fr], ab.status[fr], rp.gt[fr]
-            u = normalize_joints(gt.contiguous(), grid[:, 3].contiguous(), grid[:, :3].contiguous(), clamp=False)
-            us.append(u[st == 0].cpu().numpy())
+            u = normalize_joints(rp.gt[fr].contiguous(), pl.max_l[fr], pl.mid_p[fr], clamp=False)
+            us.append(u[pl.status[fr] == 0].cpu().numpy())
         else:
             for a in range(0, n, self.block):
                 pk = self.raw.take(np.arange(a, min(n, a + self.block)))
                 depth, offsets, headers = pk.to_torch(dev, pin=False, non_blocking=False)
-                ab = aabb(depth, offsets, headers)
+                pl = _place_aabb(depth, offsets, headers, rows=False)
                 gt = torch.from_numpy(np.ascontiguousarray(pk.gt)).to(dev)
-                u = normalize_joints(gt, ab.grid[:, 3].contiguous(), ab.grid[:, :3].contiguous(), clamp=False)
-                us.append(u[ab.status == 0].cpu().numpy())
+                u = normalize_joints(gt, pl.max_l, pl.mid_p, clamp=False)
+                us.append(u[pl.status == 0].cpu().numpy())
         for a in range(n, len(self), self.block):   # (the augmented items, where there are any)
             out, _, u, _ = self._voxelize_items(np.arange(a, min(len(self), a + self.block)), clamp=False)
             us.append(u[out.status == 0].cpu().numpy())

@@ -75,100 +75,79 @@ _SUBDIRS = ("Point_Cloud", "TSDF", "ground_truth", "num")
 _AUG_SUBDIRS = tuple(d + "_aug" for d in _SUBDIRS)
 
 
-def _default_voxelize(pk: packing.PackedFrames, res: int, layout: str, device):
-    """Upload + one launch; returns host arrays (tsdf, max_l, mid_p, status)."""
+def _voxelize_pack(pk: packing.PackedFrames, res: int, layout: str, device, *, cloud: Optional[np.ndarray] = None,
+                   xforms: Optional[np.ndarray] = None, gt: Optional[np.ndarray] = None, tsdf: str = "projective"):
+    """The one body of the default hooks below: upload the pack (and ``xforms`` / ``cloud`` / ``gt``), place the grid, run
+    the voxel pass, map the joints, combine the status, synchronise, copy to the host: ``(tsdf, max_l, mid_p, status)``,
+    with ``gt`` a fifth, the joints under ``xforms``.  With ``cloud`` (host float64[n, P, 3]) the grid is placed on it
+    (``voxelize.cloud_grids``), ``voxelize._grid_pass`` names the pass and ``status`` is the first non-zero of the two; without
+    it the grid is on all valid pixels: the fused ``voxelize`` / ``voxelize_aug``, or ``voxelize_accurate``."""
     import torch
 
-    from .voxelize import voxelize
+    from .voxelize import (TsdfBatch, _first_status, _grid_pass, cloud_grids, transform_joints, voxelize, voxelize_accurate,
+                           voxelize_aug)
 
+    if (xforms is None) != (gt is None) or (tsdf == "accurate" and xforms is not None):
+        raise ValueError('xforms and gt come together, and not with tsdf="accurate": that pass is not there yet')
     depth, offsets, headers = pk.to_torch(device, pin=True, non_blocking=True)
-    out = voxelize(depth, offsets, headers, res=res, layout=layout)
+
+    def up(a, dtype):
+        return None if a is None else torch.from_numpy(np.ascontiguousarray(a, dtype)).to(depth.device)
+    xf, pts = up(xforms, np.float64), up(cloud, np.float64)
+    g = up(None if gt is None else np.asarray(gt, np.float32).reshape(len(pk), -1), np.float32)
+    gt_aug = None
+    if pts is not None:
+        cg = cloud_grids(pts, res=res)
+        vol, st = _grid_pass(depth, offsets, headers, cg.grid, res=res, layout=layout, cam=None, xforms=xf, tsdf=tsdf)
+        gt_aug = transform_joints(g, xf) if g is not None else None
+        out = TsdfBatch(vol, cg.max_l, cg.mid_p, _first_status(cg.status, st))
+    elif xf is not None:
+        out, _, gt_aug = voxelize_aug(depth, offsets, headers, xf, res=res, layout=layout, gt=g)
+    elif tsdf == "accurate":
+        out = voxelize_accurate(depth, offsets, headers, res=res, layout=layout)
+    else:
+        out = voxelize(depth, offsets, headers, res=res, layout=layout)
     torch.cuda.synchronize(depth.device)
-    return (out.tsdf.cpu().numpy(), out.max_l.cpu().numpy(), out.mid_p.cpu().numpy(),
-            out.status.cpu().numpy())
+    return tuple(t.cpu().numpy() for t in (*out, gt_aug) if t is not None)
+
+
+def _default_voxelize(pk: packing.PackedFrames, res: int, layout: str, device):
+    """Upload + one launch; returns host arrays (tsdf, max_l, mid_p, status)."""
+    return _voxelize_pack(pk, res, layout, device)
 
 
 def _default_voxelize_accurate(pk: packing.PackedFrames, res: int, layout: str, device):
-    """:func:`_default_voxelize` with the accurate directional TSDF (``voxelize.voxelize_accurate``): the same placement,
-    max_l, mid_p and status, the volumes by the nearest point among all valid pixels."""
-    import torch
-
-    from .voxelize import voxelize_accurate
-
-    depth, offsets, headers = pk.to_torch(device, pin=True, non_blocking=True)
-    out = voxelize_accurate(depth, offsets, headers, res=res, layout=layout)
-    torch.cuda.synchronize(depth.device)
-    return (out.tsdf.cpu().numpy(), out.max_l.cpu().numpy(), out.mid_p.cpu().numpy(),
-            out.status.cpu().numpy())
+    """:func:`_default_voxelize` with the accurate directional TSDF (``voxelize.voxelize_accurate``): volumes alone differ."""
+    return _voxelize_pack(pk, res, layout, device, tsdf="accurate")
 
 
 def _default_voxelize_aug(pk: packing.PackedFrames, xforms: np.ndarray, gt: np.ndarray, res: int, layout: str, device):
     """Upload + one augmented launch with the labels: host arrays (tsdf, max_l, mid_p, status, gt_aug)."""
-    import torch
-
-    from .voxelize import voxelize_aug
-
-    depth, offsets, headers = pk.to_torch(device, pin=True, non_blocking=True)
-    xf = torch.from_numpy(np.ascontiguousarray(xforms, np.float64)).to(depth.device)
-    g = torch.from_numpy(np.ascontiguousarray(np.asarray(gt, np.float32).reshape(len(pk), -1))).to(depth.device)
-    out, _, gt_aug = voxelize_aug(depth, offsets, headers, xf, res=res, layout=layout, gt=g)
-    torch.cuda.synchronize(depth.device)
-    return (out.tsdf.cpu().numpy(), out.max_l.cpu().numpy(), out.mid_p.cpu().numpy(), out.status.cpu().numpy(),
-            gt_aug.cpu().numpy())
+    return _voxelize_pack(pk, res, layout, device, xforms=xforms, gt=gt)
 
 
 def _default_voxelize_cloud(pk: packing.PackedFrames, cloud: np.ndarray, res: int, layout: str, device):
     """Upload the pack and its clouds; grid placement from each cloud, then the volumes on that placement: host arrays
     (tsdf, max_l, mid_p, status), status being the first non-zero of the two stages."""
-    import torch
-
-    from .voxelize import cloud_grids, voxelize_grid
-
-    depth, offsets, headers = pk.to_torch(device, pin=True, non_blocking=True)
-    pts = torch.from_numpy(np.ascontiguousarray(cloud, np.float64)).to(depth.device)
-    cg = cloud_grids(pts, res=res)
-    tsdf, st = voxelize_grid(depth, offsets, headers, cg.grid, res=res, layout=layout)
-    status = torch.where(cg.status != 0, cg.status, st)
-    torch.cuda.synchronize(depth.device)
-    return tsdf.cpu().numpy(), cg.max_l.cpu().numpy(), cg.mid_p.cpu().numpy(), status.cpu().numpy()
+    return _voxelize_pack(pk, res, layout, device, cloud=cloud)
 
 
 def _default_voxelize_cloud_accurate(pk: packing.PackedFrames, cloud: np.ndarray, res: int, layout: str, device):
     """:func:`_default_voxelize_cloud` with the accurate directional TSDF (``voxelize.voxelize_grid_accurate``) on the
     cloud's placement."""
-    import torch
-
-    from .voxelize import cloud_grids, voxelize_grid_accurate
-
-    depth, offsets, headers = pk.to_torch(device, pin=True, non_blocking=True)
-    pts = torch.from_numpy(np.ascontiguousarray(cloud, np.float64)).to(depth.device)
-    cg = cloud_grids(pts, res=res)
-    tsdf, st = voxelize_grid_accurate(depth, offsets, headers, cg.grid, res=res, layout=layout)
-    status = torch.where(cg.status != 0, cg.status, st)
-    torch.cuda.synchronize(depth.device)
-    return tsdf.cpu().numpy(), cg.max_l.cpu().numpy(), cg.mid_p.cpu().numpy(), status.cpu().numpy()
+    return _voxelize_pack(pk, res, layout, device, cloud=cloud, tsdf="accurate")
 
 
 def _default_voxelize_aug_cloud(pk: packing.PackedFrames, xforms: np.ndarray, cloud_aug: np.ndarray, gt: np.ndarray,
                                 res: int, layout: str, device):
-    """Upload the pack, its maps and its augmented clouds; grid placement from each cloud, the augmented volumes on that
-    placement and the joints under the maps: host arrays (tsdf, max_l, mid_p, status, gt_aug), status being the first
-    non-zero of the two stages."""
-    import torch
+    """:func:`_default_voxelize_cloud` under the maps (``voxelize.voxelize_aug_grid`` on the augmented cloud's placement), and
+    the joints under them: host arrays (tsdf, max_l, mid_p, status, gt_aug)."""
+    return _voxelize_pack(pk, res, layout, device, cloud=cloud_aug, xforms=xforms, gt=gt)
 
-    from .voxelize import cloud_grids, transform_joints, voxelize_aug_grid
 
-    depth, offsets, headers = pk.to_torch(device, pin=True, non_blocking=True)
-    xf = torch.from_numpy(np.ascontiguousarray(xforms, np.float64)).to(depth.device)
-    pts = torch.from_numpy(np.ascontiguousarray(cloud_aug, np.float64)).to(depth.device)
-    g = torch.from_numpy(np.ascontiguousarray(np.asarray(gt, np.float32).reshape(len(pk), -1))).to(depth.device)
-    cg = cloud_grids(pts, res=res)
-    tsdf, st = voxelize_aug_grid(depth, offsets, headers, xf, cg.grid, res=res, layout=layout)
-    gt_aug = transform_joints(g, xf)
-    status = torch.where(cg.status != 0, cg.status, st)
-    torch.cuda.synchronize(depth.device)
-    return (tsdf.cpu().numpy(), cg.max_l.cpu().numpy(), cg.mid_p.cpu().numpy(), status.cpu().numpy(),
-            gt_aug.cpu().numpy())
+# the default plain hook of preprocess_tree by (tsdf, placement): module-level NAMES, resolved when it is called
+_PLAIN_HOOKS = {("projective", "pixels"): "_default_voxelize", ("accurate", "pixels"): "_default_voxelize_accurate",
+                ("projective", "cloud"): "_default_voxelize_cloud", ("accurate", "cloud"): "_default_voxelize_cloud_accurate"}
 
 
 def device_point_clouds(pk: packing.PackedFrames, points_num: int, seed: int, xforms: Optional[np.ndarray] = None,
@@ -318,13 +297,10 @@ def preprocess_tree(db_dir: str, save_dir: str, *, res: int = 32, layout: str = 
         raise ValueError('tsdf must be "projective" or "accurate"')
     if tsdf == "accurate" and aug:
         raise ValueError('tsdf="accurate" has no augmented twin yet (the accurate pass under a per-frame map): use aug=False')
-    vox = voxelize_fn if voxelize_fn is not None else _default_voxelize
-    vox_aug_cloud = voxelize_aug_cloud_fn if voxelize_aug_cloud_fn is not None else _default_voxelize_aug_cloud
-    vox_cloud = voxelize_cloud_fn if voxelize_cloud_fn is not None else _default_voxelize_cloud
-    if tsdf == "accurate":
-        vox = voxelize_fn if voxelize_fn is not None else _default_voxelize_accurate
-        vox_cloud = voxelize_cloud_fn if voxelize_cloud_fn is not None else _default_voxelize_cloud_accurate
+    vox = voxelize_fn if voxelize_fn is not None else globals()[_PLAIN_HOOKS[tsdf, "pixels"]]
+    vox_cloud = voxelize_cloud_fn if voxelize_cloud_fn is not None else globals()[_PLAIN_HOOKS[tsdf, "cloud"]]
     vox_aug = voxelize_aug_fn if voxelize_aug_fn is not None else _default_voxelize_aug
+    vox_aug_cloud = voxelize_aug_cloud_fn if voxelize_aug_cloud_fn is not None else _default_voxelize_aug_cloud
     rng = rng if rng is not None else np.random.default_rng()
     if aug:
         aug_rng = aug_rng if aug_rng is not None else np.random.default_rng()

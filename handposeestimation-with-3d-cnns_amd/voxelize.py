@@ -140,8 +140,28 @@ def _make_out(out, n, R, dev) -> "TsdfBatch":
     return out
 
 
+def _each(out, fields, dev) -> list:
+    """Every output of the table ``fields`` of (name, shape, dtype): ``out``'s, validated, or allocated where it has none."""
+    return [_out("out." + name, getattr(out, name, None), shape, dtype, dev) for name, shape, dtype in fields]
+
+
+def _outs(cls, out, fields, dev):
+    """An entry's outputs as the NamedTuple ``cls``: allocated from their table, or the caller's ``out``, every field validated."""
+    if out is None:
+        return cls(*[_out(name, None, shape, dtype, dev) for name, shape, dtype in fields])
+    for name, shape, dtype in fields:
+        _shaped("out." + name, getattr(out, name), shape, dtype, dev)
+    return out
+
+
 def _cam(cam):
     return ctypes.byref(cam) if cam is not None else None
+
+
+def _cam5(cam) -> list:
+    """The five camera constants by value, for the entries that take them so (``cam`` None: the MSRA defaults)."""
+    c = cam if cam is not None else _lib.default_cam()
+    return [c.focal, c.cx, c.cy, c.invalid_eps, c.trunc_voxels]
 
 
 def _ptr(t):
@@ -466,8 +486,8 @@ def aabb(depth: torch.Tensor, offsets: torch.Tensor, headers: torch.Tensor, res:
     """Phase 1 + glue only: min_max_kernel + host numpy of pre/tsdf_numba.py:75-116,135-147."""
     L = _lib.load()
     dev, n, R = _pack(L, depth, offsets, headers, res)
-    out = AabbBatch(_out("aabb", None, (n, 6), torch.float32, dev), _out("grid", None, (n, 8), torch.float32, dev),
-                    _out("ori", None, (n, 3), torch.float32, dev), _out("status", None, (n,), torch.int32, dev))
+    out = _outs(AabbBatch, None, (("aabb", (n, 6), torch.float32), ("grid", (n, 8), torch.float32),
+                                  ("ori", (n, 3), torch.float32), ("status", (n,), torch.int32)), dev)
     if n:
         _call(dev, L.tsdf_aabb_hip, [depth.data_ptr(), depth.numel(), offsets.data_ptr(), headers.data_ptr(), n, R, _cam(cam),
                                      None, out.aabb.data_ptr(), out.grid.data_ptr(), out.ori.data_ptr(),
@@ -814,12 +834,8 @@ def point_clouds(depth: torch.Tensor, offsets: torch.Tensor, headers: torch.Tens
         raise ValueError("frame_base must fit int64")
     if xforms is not None:
         _shaped("xforms", xforms, (n, 24), torch.float64, dev)
-    fields = (("points", (n, P, 3), torch.float64), ("count", (n,), torch.int32), ("status", (n,), torch.int32))
-    if out is None:
-        out = PointCloudBatch(*[_out(name, None, shape, dtype, dev) for name, shape, dtype in fields])
-    else:
-        for name, shape, dtype in fields:
-            _shaped("out." + name, getattr(out, name), shape, dtype, dev)
+    out = _outs(PointCloudBatch, out, (("points", (n, P, 3), torch.float64), ("count", (n,), torch.int32),
+                                       ("status", (n,), torch.int32)), dev)
     if n:
         _call(dev, L.tsdf_point_clouds_hip,
               [depth.data_ptr(), depth.numel(), offsets.data_ptr(), headers.data_ptr(), n, P, _cam(cam), seed, frame_base,
@@ -854,9 +870,9 @@ def cloud_grids(points: torch.Tensor, res: int = 32, cam: Optional[_lib.TsdfCam]
         raise ValueError("points must hold 1..2^31-1 points per frame")
     if not L.tsdf_resolution_supported(int(res)):
         raise ValueError(f"unsupported grid resolution {res} (multiple of 4 in 4..128)")
-    out = CloudGridBatch(_out("grid", None, (n, 8), torch.float32, dev), _out("max_l", None, (n,), torch.float32, dev),
-                         _out("mid_p", None, (n, 3), torch.float32, dev), _out("aabb", None, (n, 6), torch.float32, dev),
-                         _out("status", None, (n,), torch.int32, dev))
+    out = _outs(CloudGridBatch, None, (("grid", (n, 8), torch.float32), ("max_l", (n,), torch.float32),
+                                       ("mid_p", (n, 3), torch.float32), ("aabb", (n, 6), torch.float32),
+                                       ("status", (n,), torch.int32)), dev)
     if n:
         _call(dev, L.tsdf_cloud_grid_hip, [points.data_ptr(), n, P, int(res), _cam(cam), None, out.grid.data_ptr(),
                                            out.max_l.data_ptr(), out.mid_p.data_ptr(), out.aabb.data_ptr(),
@@ -887,16 +903,19 @@ def process_batch(depth: torch.Tensor, offsets: torch.Tensor, headers: torch.Ten
 
     ``dtype`` (torch.float16 / torch.bfloat16): the last stage is :func:`voxelize_grid_lowp` on the same rows and ``tsdf``
     has that type; every other field is unchanged."""
+    pc, cg, tsdf, status = _process_half(depth, offsets, headers, points, seed, frame_base, res, layout, cam, dtype)
+    return ProcessBatch(pc.points, tsdf, cg.max_l, cg.mid_p, status, pc.count)
+
+
+def _process_half(depth, offsets, headers, points, seed, frame_base, res, layout, cam, dtype, xforms=None):
+    """The three stages of ``process()`` — the resampled cloud (under ``xforms``), the grid on it, the volume on that grid
+    (:func:`_grid_pass`) —: ``(PointCloudBatch, CloudGridBatch, volume, first non-zero status of the three)``."""
     if dtype is not None:
         _lowp_dtype(dtype)
-    pc = point_clouds(depth, offsets, headers, points=points, seed=seed, frame_base=frame_base, cam=cam)
+    pc = point_clouds(depth, offsets, headers, points=points, seed=seed, frame_base=frame_base, xforms=xforms, cam=cam)
     cg = cloud_grids(pc.points, res=res, cam=cam)
-    if dtype is None:
-        tsdf, st = voxelize_grid(depth, offsets, headers, cg.grid, res=res, layout=layout, cam=cam)
-    else:
-        tsdf, st = voxelize_grid_lowp(depth, offsets, headers, cg.grid, res=res, layout=layout, dtype=dtype, cam=cam)
-    status = torch.where(pc.status != 0, pc.status, torch.where(cg.status != 0, cg.status, st))
-    return ProcessBatch(pc.points, tsdf, cg.max_l, cg.mid_p, status, pc.count)
+    vol, st = _grid_pass(depth, offsets, headers, cg.grid, res=res, layout=layout, cam=cam, xforms=xforms, dtype=dtype)
+    return pc, cg, vol, _first_status(pc.status, cg.status, st)
 
 
 def voxelize_aug_grid(depth: torch.Tensor, offsets: torch.Tensor, headers: torch.Tensor, xforms: torch.Tensor,
@@ -977,20 +996,12 @@ def process_batch_aug(depth: torch.Tensor, offsets: torch.Tensor, headers: torch
 
     ``dtype`` (torch.float16 / torch.bfloat16): ``tsdf`` comes from :func:`process_batch` ``(dtype=)`` and ``tsdf_aug`` from
     :func:`voxelize_map_grid_lowp` on the same rows, both of that type; every other field is unchanged bit for bit."""
-    if dtype is not None:
-        _lowp_dtype(dtype)
     pb = process_batch(depth, offsets, headers, points=points, seed=seed, frame_base=frame_base, res=res, layout=layout,
                        cam=cam, dtype=dtype)
     if xforms is None:
         xforms = aug_xforms(pb.mid_p, key=key, counter0=frame_base)
-    pa = point_clouds(depth, offsets, headers, points=points, seed=aug_seed, frame_base=frame_base, xforms=xforms, cam=cam)
-    cg = cloud_grids(pa.points, res=res, cam=cam)
-    if dtype is None:
-        tsdf_aug, st = voxelize_aug_grid(depth, offsets, headers, xforms, cg.grid, res=res, layout=layout, cam=cam)
-    else:
-        tsdf_aug, st = voxelize_map_grid_lowp(depth, offsets, headers, xforms, cg.grid, res=res, layout=layout, dtype=dtype,
-                                              cam=cam)
-    status_aug = torch.where(pa.status != 0, pa.status, torch.where(cg.status != 0, cg.status, st))
+    pa, cg, tsdf_aug, status_aug = _process_half(depth, offsets, headers, points, aug_seed, frame_base, res, layout, cam, dtype,
+                                                 xforms=xforms)
     gt_aug = transform_joints(gt, xforms) if gt is not None else None
     return ProcessAugBatch(pb.points, pb.tsdf, pb.max_l, pb.mid_p, pa.points, tsdf_aug, cg.max_l, cg.mid_p, gt_aug,
                            pb.status, status_aug, pb.count, xforms)
@@ -1081,15 +1092,19 @@ def _source(depth, offsets, headers, index, res, layout):
     """The one validation of the source tables with an optional index (int64[n] on the GPU: batch position i takes source
     frame index[i]; without it the batch is the n_src frames).  Returns (device, n_src, n, R)."""
     dev, n_src, R = _pack(_lib.load(), depth, offsets, headers, res, layout)
-    n = n_src
-    if index is not None:
-        _dev_check("index", index, torch.int64, dev)
-        if index.dim() != 1:
-            raise ValueError("index must have shape [n]")
-        n = int(index.shape[0])
-        if n and not n_src:
-            raise ValueError("index needs at least one source frame")
+    n = n_src if index is None else _indexed(index, n_src, dev, "index needs at least one source frame")
     return dev, n_src, n, R
+
+
+def _indexed(index, n_src, dev, nothing_to_index: str) -> int:
+    """The one check of an index into ``n_src`` frames (int64[n] on ``dev``); returns the batch's n."""
+    _dev_check("index", index, torch.int64, dev)
+    if index.dim() != 1:
+        raise ValueError("index must have shape [n]")
+    n = int(index.shape[0])
+    if n and not n_src:
+        raise ValueError(nothing_to_index)
+    return n
 
 
 def _src_head(depth, offsets, headers, n_src, index, n, R) -> list:
@@ -1145,9 +1160,8 @@ def voxelize_lowp(depth: torch.Tensor, offsets: torch.Tensor, headers: torch.Ten
     and the crop is read twice (the fused float32 entry reads it once).  ``max_l`` / ``mid_p`` / ``status`` are
     :func:`aabb`'s, bit for bit those of :func:`voxelize`; ``tsdf`` is ``dtype[n,3,R,R,R]``."""
     _lowp_dtype(dtype)
-    ab = aabb(depth, offsets, headers, res=res, cam=cam)
-    tsdf, _ = voxelize_grid_lowp(depth, offsets, headers, _aabb_rows(ab), res=res, layout=layout, dtype=dtype, cam=cam)
-    return TsdfBatch(tsdf, ab.grid[:, 3].contiguous(), ab.grid[:, :3].contiguous(), ab.status)
+    return _placed_pass(depth, offsets, headers, _place_aabb(depth, offsets, headers, res, cam), res=res, layout=layout,
+                        cam=cam, dtype=dtype)
 
 
 def narrow_volumes(tsdf32: torch.Tensor, dtype: torch.dtype = torch.bfloat16,
@@ -1195,17 +1209,73 @@ def voxelize_grid_accurate(depth: torch.Tensor, offsets: torch.Tensor, headers: 
     st = _out("status", None, (n,), torch.int32, dev)
     near = _out("nearest", None, (n, R, R, R), torch.int32, dev) if nearest else None
     if n:
-        c = cam if cam is not None else _lib.default_cam()   # the entry takes the five constants by value
         _call(dev, A.tsdf_voxelize_grid_accurate_hip,
-              _src_head(depth, offsets, headers, n_src, index, n, R) +
-              [c.focal, c.cx, c.cy, c.invalid_eps, c.trunc_voxels, _lib.LAYOUTS[layout], None, grid.data_ptr(),
-               tsdf.data_ptr(), _ptr(near), st.data_ptr()], 14)
+              _src_head(depth, offsets, headers, n_src, index, n, R) + _cam5(cam) +
+              [_lib.LAYOUTS[layout], None, grid.data_ptr(), tsdf.data_ptr(), _ptr(near), st.data_ptr()], 14)
     return (tsdf, st, near) if nearest else (tsdf, st)
 
 
-def _aabb_rows(ab: "AabbBatch") -> torch.Tensor:
-    """The grid rows (vox_ori[3], voxel_len, trunc_dis, 3 pad words) of :func:`aabb`'s placement, put together on the device."""
-    return torch.cat([ab.ori, ab.grid[:, 4:6], torch.zeros_like(ab.ori)], dim=1)
+class MapGridBatch(NamedTuple):
+    """A grid placement (:func:`map_grids`, :func:`_place_aabb`).  :class:`CloudGridBatch` and a :class:`HandCrops` with its
+    cube have the same four fields by name: ``grid`` goes to :func:`_grid_pass`, the rest into a composed entry's result."""
+    grid: torch.Tensor    # float32[n, 8]  vox_ori[3], voxel_len, trunc_dis, 0, 0, 0 (the ``grid`` of the voxel passes)
+    max_l: torch.Tensor   # float32[n]     in the mapped frame
+    mid_p: torch.Tensor   # float32[n, 3]
+    status: torch.Tensor  # int32[n]  (_lib.TSDF_FRAME_*)
+
+
+def _placement_fields(n):
+    return (("grid", (n, 8), torch.float32), ("max_l", (n,), torch.float32), ("mid_p", (n, 3), torch.float32),
+            ("status", (n,), torch.int32))
+
+
+def _place_aabb(depth, offsets, headers, res=32, cam=None, rows: bool = True) -> MapGridBatch:
+    """:func:`aabb`'s placement: the one place its columns (mid_p[3], max_l, voxel_len, trunc_dis; vox_ori apart) become the
+    passes' grid rows, put together on the device.  ``rows=False``: no ``grid``, for who wants the labels' frame alone."""
+    ab = aabb(depth, offsets, headers, res=res, cam=cam)
+    grid = torch.cat([ab.ori, ab.grid[:, 4:6], torch.zeros_like(ab.ori)], dim=1) if rows else None
+    return MapGridBatch(grid, ab.grid[:, 3].contiguous(), ab.grid[:, :3].contiguous(), ab.status)
+
+
+def _first_status(*stages: torch.Tensor) -> torch.Tensor:
+    """Per frame the first non-zero status of the stages, in their order."""
+    status = stages[-1]
+    for st in reversed(stages[:-1]):
+        status = torch.where(st != 0, st, status)
+    return status
+
+
+def _grid_pass(depth, offsets, headers, grid, *, res, layout, cam, xforms=None, dtype=None, tsdf="projective", index=None,
+               out=None):
+    """The voxel pass on the rows ``grid`` that (``xforms``, ``dtype``, ``tsdf``) name, ``(volume, status)`` — the one table
+    of the passes there are ("Placement, pass, status"):
+        projective   voxelize_grid | dtype: voxelize_grid_lowp | xforms: voxelize_aug_grid | both: voxelize_map_grid_lowp
+        accurate     voxelize_grid_accurate, with dtype then narrow_volumes; under xforms a ValueError: no such pass yet
+    ``index`` / ``out`` (with ``dtype``: the narrow volume) go to the entries whose ABI has them; the two float32 projective
+    entries have neither and refuse them.  Every refusal comes before the first launch."""
+    if dtype is not None:
+        _lowp_dtype(dtype)
+    if tsdf not in ("projective", "accurate"):
+        raise ValueError("tsdf must be 'projective' or 'accurate'")
+    pack = (depth, offsets, headers) if xforms is None else (depth, offsets, headers, xforms)
+    kw = dict(res=res, layout=layout, cam=cam)
+    if tsdf == "accurate":
+        if xforms is not None:
+            raise ValueError("tsdf='accurate' takes no xforms: the accurate pass under a per-frame map is not there yet")
+        vol, status = voxelize_grid_accurate(*pack, grid, index=index, out=out if dtype is None else None, **kw)
+        return (vol if dtype is None else narrow_volumes(vol, dtype=dtype, out=out)), status
+    if dtype is not None:
+        entry = voxelize_grid_lowp if xforms is None else voxelize_map_grid_lowp
+        return entry(*pack, grid, dtype=dtype, index=index, out=out, **kw)
+    if index is not None or out is not None:
+        raise ValueError(("voxelize_grid" if xforms is None else "voxelize_aug_grid") + " takes neither index nor out")
+    return (voxelize_grid if xforms is None else voxelize_aug_grid)(*pack, grid, **kw)
+
+
+def _placed_pass(depth, offsets, headers, place: MapGridBatch, **how) -> TsdfBatch:
+    """:func:`_grid_pass` on the rows of ``place``, as a batch with the PLACEMENT's ``max_l`` / ``mid_p`` / ``status``."""
+    vol, _ = _grid_pass(depth, offsets, headers, place.grid, **how)
+    return TsdfBatch(vol, place.max_l, place.mid_p, place.status)
 
 
 def voxelize_accurate(depth: torch.Tensor, offsets: torch.Tensor, headers: torch.Tensor, res: int = 32,
@@ -1213,16 +1283,8 @@ def voxelize_accurate(depth: torch.Tensor, offsets: torch.Tensor, headers: torch
     """:func:`voxelize` with the accurate directional TSDF: :func:`aabb` places the grid, the rows are put together on the
     device and :func:`voxelize_grid_accurate` writes the volume.  Nothing runs on the host in between; it is two launches.
     ``max_l`` / ``mid_p`` / ``status`` are :func:`aabb`'s, bit for bit those of :func:`voxelize`."""
-    ab = aabb(depth, offsets, headers, res=res, cam=cam)
-    tsdf, _ = voxelize_grid_accurate(depth, offsets, headers, _aabb_rows(ab), res=res, layout=layout, cam=cam)
-    return TsdfBatch(tsdf, ab.grid[:, 3].contiguous(), ab.grid[:, :3].contiguous(), ab.status)
-
-
-class MapGridBatch(NamedTuple):
-    grid: torch.Tensor    # float32[n, 8]  vox_ori[3], voxel_len, trunc_dis, 0, 0, 0 (the ``grid`` of the voxel passes)
-    max_l: torch.Tensor   # float32[n]     in the mapped frame
-    mid_p: torch.Tensor   # float32[n, 3]
-    status: torch.Tensor  # int32[n]  (_lib.TSDF_FRAME_*)
+    return _placed_pass(depth, offsets, headers, _place_aabb(depth, offsets, headers, res, cam), res=res, layout=layout,
+                        cam=cam, tsdf="accurate")
 
 
 def map_grids(depth: torch.Tensor, offsets: torch.Tensor, headers: torch.Tensor, xforms: torch.Tensor, res: int = 32,
@@ -1243,13 +1305,7 @@ def map_grids(depth: torch.Tensor, offsets: torch.Tensor, headers: torch.Tensor,
     M = _lib.load_maplowp()
     dev, n_src, n, R = _source(depth, offsets, headers, index, res, "czyx")
     _shaped("xforms", xforms, (n, 24), torch.float64, dev)
-    fields = (("grid", (n, 8), torch.float32), ("max_l", (n,), torch.float32), ("mid_p", (n, 3), torch.float32),
-              ("status", (n,), torch.int32))
-    if out is None:
-        out = MapGridBatch(*[_out(name, None, shape, dtype, dev) for name, shape, dtype in fields])
-    else:
-        for name, shape, dtype in fields:
-            _shaped("out." + name, getattr(out, name), shape, dtype, dev)
+    out = _outs(MapGridBatch, out, _placement_fields(n), dev)
     if n:
         _call(dev, M.tsdf_map_place_hip,
               _src_head(depth, offsets, headers, n_src, index, n, R) +
@@ -1412,10 +1468,7 @@ def map_step_head(depth: torch.Tensor, offsets: torch.Tensor, headers: torch.Ten
     grid = max_l = mid_p = status = gt_aug = gt_nor = None
     nj = 0
     if place:
-        fields = (("grid", (n, 8), torch.float32), ("max_l", (n,), torch.float32), ("mid_p", (n, 3), torch.float32),
-                  ("status", (n,), torch.int32))
-        grid, max_l, mid_p, status = (_out("out." + name, getattr(out, name) if out is not None else None, shape, dtype, dev)
-                                      for name, shape, dtype in fields)
+        grid, max_l, mid_p, status = _each(out, _placement_fields(n), dev)
     if gt is not None:
         if not place:
             raise ValueError("gt needs place=True (the labels are normalised in the placed grid)")
@@ -1427,11 +1480,10 @@ def map_step_head(depth: torch.Tensor, offsets: torch.Tensor, headers: torch.Ten
         gt_aug = _out("out.gt_aug", out.gt_aug if out is not None else None, shape, torch.float32, dev)
         gt_nor = _out("out.gt_nor", out.gt_nor if out is not None else None, shape, torch.float32, dev)
     if n:
-        c = cam if cam is not None else _lib.default_cam()   # the entry takes the five constants by value
         _call(dev, S.tsdf_map_step_head_hip,
-              _src_head(depth, offsets, headers, n_src, index, n, R) +
-              [c.focal, c.cx, c.cy, c.invalid_eps, c.trunc_voxels, centres.data_ptr(), _ptr(base), state.data_ptr(),
-               _ptr(counters), _ptr(gt), nj, 1 if clamp else 0, None, xf.data_ptr(), _ptr(grid), _ptr(max_l), _ptr(mid_p), _ptr(status), _ptr(gt_aug), _ptr(gt_nor), _ptr(stretch),
+              _src_head(depth, offsets, headers, n_src, index, n, R) + _cam5(cam) +
+              [centres.data_ptr(), _ptr(base), state.data_ptr(), _ptr(counters), _ptr(gt), nj, 1 if clamp else 0, None,
+               xf.data_ptr(), _ptr(grid), _ptr(max_l), _ptr(mid_p), _ptr(status), _ptr(gt_aug), _ptr(gt_nor), _ptr(stretch),
                _ptr(rot)], 20)
     batch = MapStepBatch(xf, grid, max_l, mid_p, status, gt_aug, gt_nor)
     return (batch, stretch, rot) if return_params else batch
@@ -1496,19 +1548,11 @@ def locate_hands(frames: torch.Tensor, *, cube: float = 250.0, near: float = 100
     _dev_check("frames", frames, frames.dtype)
     dev = frames.device
     n_src, H, W = (int(v) for v in frames.shape)
-    n = n_src
-    if index is not None:
-        _dev_check("index", index, torch.int64, dev)
-        if index.dim() != 1:
-            raise ValueError("index must have shape [n]")
-        n = int(index.shape[0])
-        if n and not n_src:
-            raise ValueError("index needs at least one frame")
-    c = cam if cam is not None else _lib.default_cam()   # the entry takes the five constants by value
+    n = n_src if index is None else _indexed(index, n_src, dev, "index needs at least one frame")
+    c5 = _cam5(cam)
     per = ctypes.c_int64(0)
-    _lib.check(K.tsdf_locate_capacity(H, W, cube, near, c.focal, ctypes.byref(per)), "tsdf_locate_capacity")
+    _lib.check(K.tsdf_locate_capacity(H, W, cube, near, c5[0], ctypes.byref(per)), "tsdf_locate_capacity")
     need = n * per.value
-    get = (lambda name: getattr(out, name)) if out is not None else (lambda name: None)
     if out is not None:
         _dev_check("out.depth", out.depth, torch.float32, dev)
         if out.depth.dim() != 1 or out.depth.numel() < need:
@@ -1520,22 +1564,16 @@ def locate_hands(frames: torch.Tensor, *, cube: float = 250.0, near: float = 100
         offsets = torch.zeros((1,), dtype=torch.int64, device=dev) if out is None else \
             _shaped("out.offsets", out.offsets, (1,), torch.int64, dev).zero_()
     else:
-        offsets = _out("out.offsets", get("offsets"), (n + 1,), torch.int64, dev)
-    headers = _out("out.headers", get("headers"), (n, 6), torch.int32, dev)
-    com = _out("out.com", get("com"), (n, 3), torch.float64, dev)
-    count = _out("out.count", get("count"), (n,), torch.int32, dev)
-    status = _out("out.status", get("status"), (n,), torch.int32, dev)
-    g = max_l = mid_p = None
-    if grid:
-        g = _out("out.grid", get("grid"), (n, 8), torch.float32, dev)
-        max_l = _out("out.max_l", get("max_l"), (n,), torch.float32, dev)
-        mid_p = _out("out.mid_p", get("mid_p"), (n, 3), torch.float32, dev)
+        offsets = _out("out.offsets", getattr(out, "offsets", None), (n + 1,), torch.int64, dev)
+    fields = (("headers", (n, 6), torch.int32), ("com", (n, 3), torch.float64), ("count", (n,), torch.int32),
+              ("status", (n,), torch.int32)) + (_placement_fields(n)[:3] if grid else ())
+    headers, com, count, status, *cube_rows = _each(out, fields, dev)
+    g, max_l, mid_p = cube_rows or (None, None, None)
     if n:
         _call(dev, K.tsdf_locate_hip,
               [frames.data_ptr(), _LOCATE_TYPES[frames.dtype], shift if u16 else 0, n_src, H, W, _ptr(index), n, near, far, cube,
-               seed_band, refine, int(res), c.focal, c.cx, c.cy, c.invalid_eps, c.trunc_voxels, depth.numel(), None,
-               depth.data_ptr(), offsets.data_ptr(), headers.data_ptr(), com.data_ptr(), count.data_ptr(), status.data_ptr(),
-               _ptr(g), _ptr(max_l), _ptr(mid_p)], 20)
+               seed_band, refine, int(res), *c5, depth.numel(), None, depth.data_ptr(), offsets.data_ptr(), headers.data_ptr(),
+               com.data_ptr(), count.data_ptr(), status.data_ptr(), _ptr(g), _ptr(max_l), _ptr(mid_p)], 20)
     return HandCrops(depth, offsets, headers, com, count, status, g, max_l, mid_p)
 
 
@@ -1571,30 +1609,16 @@ def voxelize_frames(frames: torch.Tensor, res: int = 32, *, placement: str = "aa
     crops = locate_hands(frames, res=res, grid=placement == "cube", **locate)
     d, o, h = crops.depth, crops.offsets, crops.headers
     gt_nor = None
-    if tsdf == "accurate":
-        if placement == "aabb":
-            ab = aabb(d, o, h, res=res, cam=cam)
-            rows, max_l, mid_p, st = _aabb_rows(ab), ab.grid[:, 3].contiguous(), ab.grid[:, :3].contiguous(), ab.status
-            vol, _ = voxelize_grid_accurate(d, o, h, rows, res=res, layout=layout, cam=cam)
-        else:
-            max_l, mid_p = crops.max_l, crops.mid_p
-            vol, st = voxelize_grid_accurate(d, o, h, crops.grid, res=res, layout=layout, cam=cam)
-        if dtype is not None:
-            vol = narrow_volumes(vol, dtype=dtype)
-        batch = TsdfBatch(vol, max_l, mid_p, st)
-    elif placement == "aabb":
-        if dtype is not None:
-            batch = voxelize_lowp(d, o, h, res=res, layout=layout, dtype=dtype, cam=cam)
-        elif gt is not None:
-            batch, gt_nor = voxelize_labels(d, o, h, gt, res=res, layout=layout, cam=cam)
-        else:
-            batch = voxelize(d, o, h, res=res, layout=layout, cam=cam)
+    how = dict(res=res, layout=layout, cam=cam)
+    if placement == "cube":     # the cube's rows, and the status the PASS gives them
+        vol, st = _grid_pass(d, o, h, crops.grid, dtype=dtype, tsdf=tsdf, **how)
+        batch = TsdfBatch(vol, crops.max_l, crops.mid_p, st)
+    elif dtype is not None or tsdf != "projective":
+        batch = _placed_pass(d, o, h, _place_aabb(d, o, h, res, cam), dtype=dtype, tsdf=tsdf, **how)
+    elif gt is not None:        # float32 projective on the AABB is the fused entry: one launch, not place plus pass
+        batch, gt_nor = voxelize_labels(d, o, h, gt, **how)
     else:
-        if dtype is not None:
-            tsdf, st = voxelize_grid_lowp(d, o, h, crops.grid, res=res, layout=layout, dtype=dtype, cam=cam)
-        else:
-            tsdf, st = voxelize_grid(d, o, h, crops.grid, res=res, layout=layout, cam=cam)
-        batch = TsdfBatch(tsdf, crops.max_l, crops.mid_p, st)
+        batch = voxelize(d, o, h, **how)
     if gt is None:
         return batch, crops
     if gt_nor is None:

@@ -315,3 +315,37 @@ def test_voxelize_frames_with_the_accurate_tsdf(pkg):
     b16, crops = pkg.voxelize_frames(t, R, placement="cube", dtype=torch.bfloat16, cam=hc, tsdf="accurate")
     f32, _ = pkg.voxelize_grid_accurate(crops.depth, crops.offsets, crops.headers, crops.grid, res=R, cam=hc)
     assert b16.tsdf.dtype is torch.bfloat16 and torch.equal(b16.tsdf, f32.to(torch.bfloat16))
+
+
+def test_preprocess_tree_accurate_through_the_default_hooks(pkg, synth, tmp_path):
+    """export's two accurate default hooks: ``TSDF/<g>.npz`` holds the volumes of the explicit chain on the same pack (and,
+    with placement="cloud", on the saved cloud) bit for bit, and nothing else moves against the projective tree."""
+    db, R, g = str(tmp_path / "db"), 8, "1"
+    synth.synth_msra_tree(db, n_sub=1, n_ges=1, n_frames=3, seed=8)
+    sub, = os.listdir(db)
+    pk = pkg.packing.pack_bin_files(pkg.packing.gesture_bin_paths(os.path.join(db, sub, g), 3))
+    td, to, th = pk.to_torch(dev())
+    npz = os.path.join(sub, "TSDF", g + ".npz")
+    for kw in (dict(), dict(placement="cloud", point_clouds="device")):
+        files = {}
+        for tsdf in ("projective", "accurate"):
+            out = str(tmp_path / (tsdf + "-" + kw.get("placement", "pixels")))
+            pkg.export.preprocess_tree(db, out, res=R, points_num=64, rng=np.random.default_rng(3), tsdf=tsdf, device=dev(), **kw)
+            files[tsdf] = {os.path.relpath(os.path.join(dp, f), out): os.path.join(dp, f) for dp, _, fs in os.walk(out) for f in fs}
+        fa, fp = files["accurate"], files["projective"]
+        assert sorted(fa) == sorted(fp) and npz in fa
+        za, zp = np.load(fa[npz]), np.load(fp[npz])
+        assert (za["tsdf"] != zp["tsdf"]).any()                       # the comparison below is not of equals
+        for k in fa:
+            if k != npz:
+                assert open(fa[k], "rb").read() == open(fp[k], "rb").read(), k
+        assert sorted(za.files) == sorted(zp.files) == ["max_l", "mid_p", "status", "tsdf"]
+        for f in ("max_l", "mid_p", "status"):
+            assert za[f].dtype == zp[f].dtype and za[f].tobytes() == zp[f].tobytes(), f
+        if kw:
+            pts, = up(np.load(fa[os.path.join(sub, "Point_Cloud", g + ".npy")]))
+            want, _ = pkg.voxelize_grid_accurate(td, to, th, pkg.cloud_grids(pts, res=R).grid, res=R, layout="cxyz")
+        else:
+            want = pkg.voxelize_accurate(td, to, th, res=R, layout="cxyz").tsdf
+        assert za["tsdf"].dtype == np.float32 and za["tsdf"].shape == (3, 3, R, R, R)
+        assert np.array_equal(za["tsdf"].view(np.uint32), want.cpu().numpy().view(np.uint32))
