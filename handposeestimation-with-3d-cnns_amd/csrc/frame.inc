@@ -97,6 +97,8 @@ struct GroupCtl {
   int cap_fail[kMaxGroups];  // a row of the group's current frame did not fit the pool
   FrameHdr hdr[kMaxGroups];  // mailbox: the group's first wave fetches the next frame for the others
   HelpReq help;
+  int row_next[kMaxGroups];  // the row stream's next block number (drawn deal: phase1.inc), reset with every header; last,
+                             // so that no other member moves (the block's size, rounded to 16 bytes, stays what it was)
 };
 
 // How a frame's pixels get into LDS for the voxel pass.
@@ -155,6 +157,7 @@ struct Lds {
     alignas(16) GroupCtl ctl;
   };
   static_assert(sizeof(Block) <= kLdsBytes, "LDS layout exceeds the CU");
+  static_assert(RT != 32 || AUG || GROUPS != 2 || kPoolFloats == 34968, "the headline's pool keeps its size");
 };
 
 template <class PG>

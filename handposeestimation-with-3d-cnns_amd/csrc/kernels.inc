@@ -21,6 +21,9 @@ __global__ __launch_bounds__(kWG) void tsdf_fused_kernel(const KArgs a, const fl
   constexpr int kGroups = GROUPS, kGW = kWG / GROUPS, kGWaves = kGW / 64;  // (shadow the file-scope defaults)
   using L = Lds<RT, AUG, GROUPS>;
   __shared__ typename L::Block lds;
+  // the two-group instantiations of a fixed resolution without augmentation draw row blocks (phase1.inc); the others
+  // keep the static deal (no paired A/B of their workloads says they would gain) and compile to what they were
+  constexpr int kDeal = (GROUPS == 2 && !AUG && RT != 0) ? kDealDrawn : kDealStatic;
 
   const int R = RT ? RT : a.R;
   const CamK &cam = a.cam;
@@ -79,6 +82,7 @@ __global__ __launch_bounds__(kWG) void tsdf_fused_kernel(const KArgs a, const fl
       if (lane == 0) {
         ctl.hdr[group] = m;
         ctl.cap_fail[group] = 0;
+        if constexpr (kDeal == kDealDrawn) ctl.row_next[group] = 0;   // the row stream's block counter (phase 1)
       }
     }
     gsync();
@@ -117,7 +121,8 @@ __global__ __launch_bounds__(kWG) void tsdf_fused_kernel(const KArgs a, const fl
         }
         gsync();
       };
-      phase1_extents<kGWaves, AUG, false>(f, cam, 0, f.bh, pg.red, fin, gwave, sync_ext, cap, kGroups * iter + group, xf);
+      phase1_extents<kGWaves, AUG, false, kDeal>(f, cam, 0, f.bh, pg.red, fin, gwave, sync_ext, cap,
+                                                 kGroups * iter + group, xf, &ctl.row_next[group]);
       holds_lock = want_vol;
       ab = aabb_from_extents(fin);
       TSDF_STAMP(kGroups * iter + group, 4);

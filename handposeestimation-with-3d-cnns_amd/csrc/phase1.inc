@@ -37,16 +37,32 @@ __device__ __forceinline__ unsigned row_pack(int off4, int first, int cnt) {
 }
 
 // ---- phase 1: extents of all valid back-projected pixels of rows [rbeg, rend) ----------------
-// NW waves cooperate (row = rbeg + wave + NW*i); the result is wave-uniform in every thread.
+// NW waves cooperate; the result is wave-uniform in every thread.
 // `wave` is the (scalar) index of this wave among the NW cooperating waves, `sync` their barrier.
+// DEAL: which rows a wave loads next (extents are min/max reductions: every deal gives the same bits).
+//   kDealStatic  row = rbeg + wave + NW*i, fixed at compile time; a register buffer holds kU rows NW apart.
+//   kDealDrawn   the rows are cut into blocks of kU adjacent rows (rowdeal.inc), a register buffer holds one block, and
+//                a wave draws the number of its next block from the LDS counter *row_ctr (0 when the waves enter: reset
+//                before the barrier in front of this call).  Block numbers go outside in, in runs of NW blocks: NW from
+//                the top, NW from the bottom, ... meeting in the middle.  Two effects, measured on 1024 full frames ->
+//                32^3 with the inputs in rotation (profiles/rowdeal/): a wave whose loads come back late no longer
+//                keeps its full share while seven wait — the spread between a group's first and last wave at the end
+//                of the stream falls from 2.9-3.6 us to 1.7-2.5 — and the rows read last are the middle ones, which
+//                the staging copy re-reads first and most (that re-read costs 3.0 % of the launch when the inputs
+//                are cold).  Drawn + top to bottom -1.4 % (crops -0.8 %), drawn + outside in block by block -2.8 %
+//                (crops +-0.2 %), in runs of NW the same on full frames and -0.7...+0.3 % on crops; static blocks
+//                outside in +0.5 % (crops +2.7 %); 4096 frames per launch pay +0.5 %.  docs/HISTORY.md has the table.
 // AUG: the extents are those of the affinely mapped cloud p' = A p + b (xf = 12 doubles), which needs
 // every valid pixel transformed (the monotone shortcut does not survive a rotation).
-template <int NW, bool AUG, bool CAP, typename SYNC>
+constexpr int kDealStatic = 0, kDealDrawn = 1;
+template <int NW, bool AUG, bool CAP, int DEAL = kDealStatic, typename SYNC>
 __device__ __forceinline__ void phase1_extents(const Frame &f, const CamK &k, int rbeg, int rend, float *red,
                                                float (&fin)[kExt], const int wave, SYNC sync, const Capture &cap,
-                                               int stamp_iter = 0, const double *xf = nullptr) {
+                                               int stamp_iter = 0, const double *xf = nullptr, int *row_ctr = nullptr) {
   (void)stamp_iter;
   constexpr int kWaves = NW;
+  constexpr int kRowStep = DEAL == kDealStatic ? NW : 1;   // distance between the rows of one register buffer
+  static_assert(DEAL == kDealStatic || !CAP, "the capture's per-wave pool regions assume the static deal");
   const int lane = threadIdx.x & 63;
   float xmn = TSDF_INF, xmx = -TSDF_INF, ymn = TSDF_INF, ymx = -TSDF_INF;
   float dmn = TSDF_INF, dmx = -TSDF_INF;
@@ -98,7 +114,7 @@ __device__ __forceinline__ void phase1_extents(const Frame &f, const CamK &k, in
     auto load_rows = [&](int row0, PixN<P> (&v)[kU]) {
 #pragma unroll
       for (int u = 0; u < kU; ++u) {
-        const int row = row0 + kWaves * u;
+        const int row = row0 + kRowStep * u;
         const int rc = row < rend ? row : rend - 1;  // scalar
         const float *rp = f.depth + (int64_t)rc * f.bw;
         if (ragged && rc == f.bh - 1) {  // scalar, last row of the frame only: nothing may be read past it
@@ -119,7 +135,7 @@ __device__ __forceinline__ void phase1_extents(const Frame &f, const CamK &k, in
       unsigned long long vm[kU];       // 0: nothing to do for the row
 #pragma unroll
       for (int u = 0; u < kU; ++u) {
-        const int row = row0 + kWaves * u;
+        const int row = row0 + kRowStep * u;
         float amax = __builtin_fabsf(v[u].d[0]);
 #pragma unroll
         for (int j = 1; j < P; ++j) amax = vmax(amax, __builtin_fabsf(v[u].d[j]));  // NaN operands are dropped
@@ -130,7 +146,7 @@ __device__ __forceinline__ void phase1_extents(const Frame &f, const CamK &k, in
       // ---- pass 2: the extents ----
 #pragma unroll
       for (int u = 0; u < kU; ++u) {
-        const int row = row0 + kWaves * u;
+        const int row = row0 + kRowStep * u;
         if (vm[u]) {
           bool ok[P];
 #pragma unroll
@@ -187,7 +203,7 @@ __device__ __forceinline__ void phase1_extents(const Frame &f, const CamK &k, in
       if (CAP && cap.on) {
 #pragma unroll
         for (int u = 0; u < kU; ++u) {
-          const int row = row0 + kWaves * u;
+          const int row = row0 + kRowStep * u;
           if (row >= rend) continue;  // scalar
           unsigned ent = kRowEmpty;
           if (vm[u]) {
@@ -214,12 +230,59 @@ __device__ __forceinline__ void phase1_extents(const Frame &f, const CamK &k, in
     };
 
     PixN<P> bufA[kU], bufB[kU];
-    load_rows(rbeg + wave, bufA);
-    for (int row0 = rbeg + wave; row0 < rend; row0 += 2 * kStep) {
-      load_rows(row0 + kStep, bufB);
-      reduce_rows(row0, bufA);
-      load_rows(row0 + 2 * kStep, bufA);
-      reduce_rows(row0 + kStep, bufB);
+    if constexpr (DEAL == kDealStatic) {
+      load_rows(rbeg + wave, bufA);
+      for (int row0 = rbeg + wave; row0 < rend; row0 += 2 * kStep) {
+        load_rows(row0 + kStep, bufB);
+        reduce_rows(row0, bufA);
+        load_rows(row0 + 2 * kStep, bufA);
+        reduce_rows(row0 + kStep, bufB);
+      }
+    } else {
+      // Blocks.  The number of the block after the one being loaded is on its way while a buffer is reduced (an LDS
+      // atomic with return is 3-7 us per frame on the critical path, see above: here its latency is behind kU rows'
+      // arithmetic).  A number past the last block maps to rend: such a buffer loads clamped rows and reduces nothing,
+      // like the static deal's rows past the band.  Numbers only grow, wave by wave, so a wave whose buffer A is past
+      // the end has nothing in B either.  The counter serves ONE pass: a frame wider than a column pass takes its later
+      // passes on fixed block numbers (wave + NW*i).
+      constexpr int kOrder = kWaves;         // outside in, in runs of NW blocks (rowdeal.inc)
+      const bool drawn = cbase == 0;         // scalar
+      int held = wave + kWaves;              // fixed numbers: the last one taken
+      auto next_block = [&]() -> int {
+        if (drawn) {
+          int t = 0;
+          if (lane == 0) t = __hip_atomic_fetch_add(row_ctr, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+          return __builtin_amdgcn_readfirstlane(t);
+        }
+        held += kWaves;
+        return held;
+      };
+      auto block_row = [&](int blk) -> int {
+        int n;
+        return rbeg + rowdeal_block(blk, rend - rbeg, kU, kOrder, n);
+      };
+      int rowA, rowB;
+      if (drawn) {
+        int t = 0;
+        if (lane == 0) t = __hip_atomic_fetch_add(row_ctr, 2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        t = __builtin_amdgcn_readfirstlane(t);
+        rowA = block_row(t);
+        rowB = block_row(t + 1);
+      } else {
+        rowA = block_row(wave);
+        rowB = block_row(wave + kWaves);
+      }
+      load_rows(rowA, bufA);
+      while (rowA < rend) {
+        load_rows(rowB, bufB);
+        int nb = next_block();
+        reduce_rows(rowA, bufA);
+        rowA = block_row(nb);
+        load_rows(rowA, bufA);
+        nb = next_block();
+        reduce_rows(rowB, bufB);
+        rowB = block_row(nb);
+      }
     }
     if constexpr (!AUG) {
       // column extremes of this wave's rows -> x extent; depth extremes -> z extent
@@ -252,6 +315,7 @@ __device__ __forceinline__ void phase1_extents(const Frame &f, const CamK &k, in
     }
   }
   TSDF_STAMP(stamp_iter, 1);
+  if constexpr (!AUG) TSDF_WSTAMP(stamp_iter, 0);   // per wave: rows done (the augmented voxel pass stamps these itself)
   flush_rows();
   TSDF_STAMP(stamp_iter, 2);
 

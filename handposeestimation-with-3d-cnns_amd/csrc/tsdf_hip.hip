@@ -48,6 +48,7 @@
 //   device.inc   host preamble shared with the extension libraries: check_device, device_cus, launched, misaligned
 //   prim.inc     device primitives shared with the extension libraries: default camera, truncation, the header rule
 //   common.inc   constants, types, VALU / DPP / float64 helpers
+//   rowdeal.inc  the row stream's block deal: block number -> rows (plain C++, also compiled on the host by its test)
 //   phase1.inc   row stream -> extents (AABB) -> grid placement
 //   phase2.inc   the voxel pass, plain and augmented; gather sources, projection tables, volume stores
 //   frame.inc    kernel arguments, LDS layout, group barrier, per-frame helpers, LDS-DMA staging, table fill
@@ -85,6 +86,7 @@ namespace {
 #include "device.inc"    // host preamble: device check, launch status, alignment test (every library here has it)
 #include "prim.inc"      // kDefaultCam, trunc_i32, finite32, f32_round_up, header_ok (shared with the extension libraries)
 #include "common.inc"    // constants, types, VALU / DPP / float64 helpers
+#include "rowdeal.inc"   // block number -> rows of the row stream (host + device)
 #include "phase1.inc"    // row stream -> extents -> grid placement
 #include "phase2.inc"    // the voxel pass, plain and augmented
 #include "frame.inc"     // kernel arguments, LDS layout, per-frame helpers, staging, tables
