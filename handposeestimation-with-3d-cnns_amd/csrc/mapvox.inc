@@ -1,5 +1,6 @@
 // mapvox.inc — the voxel arithmetic under a per-frame map, stated once: tsdf_auggrid.hip (float32 voxels) and
-// tsdf_maplowp.hip (float16 / bfloat16 voxels) include it after slab.inc, inside their anonymous namespace.  The contract
+// tsdf_maplowp.hip (float16 / bfloat16 voxels) include it after slab.inc, inside their anonymous namespace;
+// tsdf_mapaccurate.hip takes the table and the constants from it and evaluates the terms per candidate pixel.  The contract
 // is include/tsdf_auggrid.h (== oracle/tsdf_oracle.c::tsdf_oracle_voxels_aug); both kernels compute the same float32
 // values by the same operations and differ in how they store them.
 //   map_d4        four float64: one entry of the per-axis table

@@ -1,6 +1,6 @@
 // slab.inc — the scaffold of a kernel that voxelizes on a grid row the caller supplies: tsdf_auggrid.hip, tsdf_lowp.hip,
-// tsdf_maplowp.hip and tsdf_accurate.hip include it (after prim.inc, inside their anonymous namespace); the product does
-// not.  Such a kernel is launched as n x ceil(R / slab) workgroups of kSlabWG threads, and a workgroup owns `slab`
+// tsdf_maplowp.hip, tsdf_accurate.hip and tsdf_mapaccurate.hip include it (after prim.inc, inside their anonymous
+// namespace); the product does not.  Such a kernel is launched as n x ceil(R / slab) workgroups of kSlabWG threads, and a workgroup owns `slab`
 // consecutive slices (indices of the slowest output axis) of one batch position.  What is the same for all of them is here:
 //   SlabSrc          the members every such kernel's argument struct opens with: source tables, index, plan, camera
 //   slab_of_block    workgroup -> (batch position, slab index, slices [sb, se))
@@ -59,7 +59,7 @@ struct SlabFrame {
 // The head of a kernel (all uniform): the block's source frame — through the index, if any; outside the tables it is a
 // bad header and nothing of it is read, a bad frame's depth neither — on its grid row.  ROWS_OF_SOURCES: `grid` holds a
 // row per source frame (tsdf_auggrid.hip, tsdf_lowp.hip, tsdf_accurate.hip); otherwise a row per batch position
-// (tsdf_maplowp.hip).  (depth_len and src_ok reach header_ok by reference, from locals: see there.)
+// (tsdf_maplowp.hip, tsdf_mapaccurate.hip).  (depth_len and src_ok reach header_ok by reference, from locals: see there.)
 template <bool ROWS_OF_SOURCES>
 __device__ __forceinline__ SlabFrame slab_head(const SlabSrc &s, const Slab &blk, const float *grid) {
   const int64_t gi = s.index ? s.index[blk.i] : blk.i;

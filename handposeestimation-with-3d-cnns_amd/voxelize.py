@@ -678,12 +678,21 @@ class AugmentedStep:
     (``place=False``) and then :func:`voxelize_indexed`; with ``dtype`` the whole head — maps, placement and labels in one
     launch — and then :func:`voxelize_map_grid_lowp`, two launches in all.  ``step`` leaves the composed maps in
     ``self.xforms``.  ``fused_head=True`` takes that two-launch form without a ``base`` as well; its results are those of
-    the default step bit for bit.  The defaults ``base=None, fused_head=False`` issue exactly the launches listed above."""
+    the default step bit for bit.  The defaults ``base=None, fused_head=False`` issue exactly the launches listed above.
+
+    ``tsdf="accurate"``: the volume is the accurate directional TSDF.  The step is the draw (:func:`aug_xforms_at`) and
+    :func:`map_grids` — or, with ``base`` / ``fused_head``, the whole head in one launch —, then
+    :func:`voxelize_map_grid_accurate` into a static float32 buffer, with ``dtype`` :func:`narrow_volumes` into the 2-byte
+    volume, and without the head the labels as in the ``dtype`` step (``gt`` on the GPU, covering the pack).  One linear
+    graph on one stream over static buffers again; ``max_l`` / ``mid_p`` / ``status``, ``xforms`` and the labels are the
+    projective step's bit for bit."""
 
     def __init__(self, depth: torch.Tensor, offsets: torch.Tensor, headers: torch.Tensor, n: int,
                  gt: Optional[torch.Tensor] = None, centres: Optional[torch.Tensor] = None, res: int = 32,
                  layout: str = "czyx", clamp: bool = True, cam: Optional[_lib.TsdfCam] = None, graph: bool = True,
-                 dtype: Optional[torch.dtype] = None, base: Optional[torch.Tensor] = None, fused_head: bool = False):
+                 dtype: Optional[torch.dtype] = None, base: Optional[torch.Tensor] = None, fused_head: bool = False,
+                 tsdf: str = "projective"):
+        self.accurate = _tsdf_kind(tsdf)
         if graph not in (False, True):
             raise ValueError(f"graph must be False or True, got {graph!r}")
         if fused_head not in (False, True):
@@ -717,21 +726,26 @@ class AugmentedStep:
         self._turn = 0
         self.xforms = torch.empty((n, 24), dtype=torch.float64, device=dev)
         self.out = empty_batch(n, R, dev)
-        if dtype is not None:   # the 2-byte volume, and the grid rows the placement hands to the voxel pass
+        # the placed form of the step: a placement writes grid rows and a voxel pass runs on them (dtype, accurate)
+        placed = self._placed = dtype is not None or self.accurate
+        if self.accurate and dtype is not None:   # the accurate pass writes float32: narrow_volumes fills the 2-byte volume
+            self._vol32 = self.out.tsdf
+        if dtype is not None:   # the 2-byte volume
             self.out = self.out._replace(tsdf=torch.empty((n, 3, R, R, R), dtype=dtype, device=dev))
+        if placed:   # the grid rows the placement hands to the voxel pass
             self._grid = MapGridBatch(torch.empty((n, 8), dtype=torch.float32, device=dev), *self.out[1:])
         self.gt_nor = self.gt_aug = None
         if gt is not None:
-            _dev_check("gt", gt, torch.float32, dev, host_ok=dtype is None)
-            if dtype is not None and gt.shape[0] != n_pack:
+            _dev_check("gt", gt, torch.float32, dev, host_ok=not placed)
+            if placed and gt.shape[0] != n_pack:
                 raise ValueError("gt must hold the labels of every frame of the pack: [N, 3*J] or [N, J, 3]")
             shape = (n,) + tuple(gt.shape[1:])
             self.gt_nor = torch.empty(shape, dtype=torch.float32, device=dev)
             self.gt_aug = torch.empty(shape, dtype=torch.float32, device=dev)
-            if dtype is not None and not self._head:   # the batch's frame numbers kept inside the pack, and its joints before the map
+            if placed and not self._head:   # the batch's frame numbers kept inside the pack, and its joints before the map
                 self._sel = (torch.empty(n, dtype=torch.int64, device=dev), torch.empty(shape, dtype=torch.float32, device=dev))
         if self._head:   # what map_step_head writes into: the object's own buffers
-            g = self._grid if dtype is not None else MapGridBatch(None, None, None, None)
+            g = self._grid if placed else MapGridBatch(None, None, None, None)
             self._head_out = MapStepBatch(self.xforms, g.grid, g.max_l, g.mid_p, g.status, self.gt_aug, self.gt_nor)
         self.graph = None
         self._run()                      # eagerly once: argument checks, library loads and the device check happen here
@@ -743,29 +757,39 @@ class AugmentedStep:
                 self._run()
             self.graph = g
 
+    def _voxel_pass(self):
+        """The voxel pass of the placed form on ``self._grid``'s rows, into the object's volume."""
+        d, o, h = self._pack_args
+        if not self.accurate:
+            _map_grid_lowp(d, o, h, self.xforms, self._grid.grid, self.res, self.layout, self.dtype, self.cam, self.index,
+                           self.out.tsdf, False)
+            return
+        vol32 = self.out.tsdf if self.dtype is None else self._vol32
+        _map_grid_accurate(d, o, h, self.xforms, self._grid.grid, self.res, self.layout, self.cam, self.index, vol32, False)
+        if self.dtype is not None:
+            narrow_volumes(vol32, dtype=self.dtype, out=self.out.tsdf)
+
     def _run(self):
         d, o, h = self._pack_args
         if self._head:
-            lowp = self.dtype is not None
+            placed = self._placed
             map_step_head(d, o, h, self.centres, self.state, base=self.base, index=self.index,
-                          gt=self._gt if lowp else None, res=self.res, cam=self.cam, clamp=self.clamp, place=lowp,
+                          gt=self._gt if placed else None, res=self.res, cam=self.cam, clamp=self.clamp, place=placed,
                           out=self._head_out)
-            if lowp:
-                _map_grid_lowp(d, o, h, self.xforms, self._grid.grid, self.res, self.layout, self.dtype, self.cam, self.index,
-                               self.out.tsdf, False)
+            if placed:
+                self._voxel_pass()
             else:
                 voxelize_indexed(d, o, h, self.index, self._gt, res=self.res, layout=self.layout, cam=self.cam,
                                  clamp=self.clamp, out=self.out, xforms=self.xforms, out_gt_nor=self.gt_nor,
                                  out_gt=self.gt_aug)
             return
         aug_xforms_at(self.centres, self.state, index=self.index, out=self.xforms)
-        if self.dtype is None:
+        if not self._placed:
             voxelize_indexed(d, o, h, self.index, self._gt, res=self.res, layout=self.layout, cam=self.cam, clamp=self.clamp,
                              out=self.out, xforms=self.xforms, out_gt_nor=self.gt_nor, out_gt=self.gt_aug)
             return
         map_grids(d, o, h, self.xforms, res=self.res, cam=self.cam, index=self.index, out=self._grid)
-        _map_grid_lowp(d, o, h, self.xforms, self._grid.grid, self.res, self.layout, self.dtype, self.cam, self.index,
-                       self.out.tsdf, False)
+        self._voxel_pass()
         if self._gt is not None:
             _batch_labels(self._gt, self.index, h.shape[0], self.xforms, self.out.max_l, self.out.mid_p, self.clamp,
                           sel=self._sel, out_aug=self.gt_aug, out_nor=self.gt_nor)
@@ -1058,7 +1082,7 @@ def obb_xforms(depth: torch.Tensor, offsets: torch.Tensor, headers: torch.Tensor
 
 def voxelize_obb(depth: torch.Tensor, offsets: torch.Tensor, headers: torch.Tensor, res: int = 32, layout: str = "czyx",
                  cam: Optional[_lib.TsdfCam] = None, gt: Optional[torch.Tensor] = None, clamp: bool = True,
-                 dtype: Optional[torch.dtype] = None):
+                 dtype: Optional[torch.dtype] = None, tsdf: str = "projective"):
     """Volumes cut in every cloud's own principal axes: :func:`obb_xforms` followed by :func:`voxelize_aug` on the same
     stream, nothing on the host in between.  Returns ``(TsdfBatch, xforms)``, or with ``gt`` (float32[n,3J] on the GPU)
     ``(TsdfBatch, gt_nor, gt_obb, xforms)``: ``gt_obb`` are the joints in the mapped frame, ``gt_nor`` their labels;
@@ -1066,11 +1090,18 @@ def voxelize_obb(depth: torch.Tensor, offsets: torch.Tensor, headers: torch.Tens
     with ``transform_joints(pred, invert_xforms(xforms))``.
 
     ``dtype`` (torch.float16 / torch.bfloat16): :func:`voxelize_aug_lowp` takes :func:`voxelize_aug`'s place and ``tsdf``
-    has that type; everything else is unchanged bit for bit."""
+    has that type; everything else is unchanged bit for bit.
+
+    ``tsdf="accurate"``: the accurate directional TSDF, :func:`voxelize_aug_accurate` in the voxelizer's place (with
+    ``dtype``: narrowed afterwards); every other field is unchanged bit for bit."""
+    accurate = _tsdf_kind(tsdf)
     if dtype is not None:
         _lowp_dtype(dtype)
     xf = obb_xforms(depth, offsets, headers, cam=cam).xforms
-    if dtype is None:
+    if accurate:
+        r = voxelize_aug_accurate(depth, offsets, headers, xf, res=res, layout=layout, dtype=dtype, cam=cam, gt=gt,
+                                  clamp=clamp)
+    elif dtype is None:
         r = voxelize_aug(depth, offsets, headers, xf, res=res, layout=layout, cam=cam, gt=gt, clamp=clamp)
     else:
         r = voxelize_aug_lowp(depth, offsets, headers, xf, res=res, layout=layout, dtype=dtype, cam=cam, gt=gt, clamp=clamp)
@@ -1250,7 +1281,9 @@ def _grid_pass(depth, offsets, headers, grid, *, res, layout, cam, xforms=None, 
     """The voxel pass on the rows ``grid`` that (``xforms``, ``dtype``, ``tsdf``) name, ``(volume, status)`` — the one table
     of the passes there are ("Placement, pass, status"):
         projective   voxelize_grid | dtype: voxelize_grid_lowp | xforms: voxelize_aug_grid | both: voxelize_map_grid_lowp
-        accurate     voxelize_grid_accurate, with dtype then narrow_volumes; under xforms a ValueError: no such pass yet
+        accurate     voxelize_grid_accurate, with dtype then narrow_volumes; under xforms a ValueError: the mapped accurate
+                     pass is voxelize_map_grid_accurate, reached by the entries listed there (voxelize_aug_accurate,
+                     voxelize_obb and AugmentedStep with tsdf="accurate"), not through this table
     ``index`` / ``out`` (with ``dtype``: the narrow volume) go to the entries whose ABI has them; the two float32 projective
     entries have neither and refuse them.  Every refusal comes before the first launch."""
     if dtype is not None:
@@ -1380,6 +1413,89 @@ def voxelize_aug_lowp(depth: torch.Tensor, offsets: torch.Tensor, headers: torch
     _lowp_dtype(dtype)
     mg = map_grids(depth, offsets, headers, xforms, res=res, cam=cam, index=index)
     tsdf, _ = _map_grid_lowp(depth, offsets, headers, xforms, mg.grid, res, layout, dtype, cam, index, None, False)
+    batch = TsdfBatch(tsdf, mg.max_l, mg.mid_p, mg.status)
+    if gt is None:
+        return batch
+    _dev_check("gt", gt, torch.float32, depth.device)
+    gt_nor, gt_aug = _batch_labels(gt, index, headers.shape[0], xforms, mg.max_l, mg.mid_p, clamp)
+    return batch, gt_nor, gt_aug
+
+
+_TSDF_KINDS = ("projective", "accurate")
+
+
+def _tsdf_kind(tsdf) -> bool:
+    """``tsdf=`` of a composed entry: True for the accurate volume; anything but the two names is a ValueError."""
+    if tsdf not in _TSDF_KINDS:
+        raise ValueError("tsdf must be 'projective' or 'accurate'")
+    return tsdf == "accurate"
+
+
+def _map_grid_accurate(depth, offsets, headers, xforms, grid, res, layout, cam, index, out, want_status, nearest=False):
+    """:func:`voxelize_map_grid_accurate`; without ``want_status`` the launch writes no status and, given ``out`` (and no
+    ``nearest``), the call allocates nothing.  Returns (volume, status or None, nearest or None)."""
+    A = _lib.load_mapaccurate()
+    dev, n_src, n, R = _source(depth, offsets, headers, index, res, layout)
+    _shaped("xforms", xforms, (n, 24), torch.float64, dev)
+    _shaped("grid", grid, (n, 8), torch.float32, dev)
+    tsdf = _out("out", out, (n, 3, R, R, R), torch.float32, dev)
+    status = _out("status", None, (n,), torch.int32, dev) if want_status else None
+    near = _out("nearest", None, (n, R, R, R), torch.int32, dev) if nearest else None
+    if n:
+        _call(dev, A.tsdf_voxelize_map_grid_accurate_hip,
+              _src_head(depth, offsets, headers, n_src, index, n, R) + _cam5(cam) +
+              [_lib.LAYOUTS[layout], None, xforms.data_ptr(), grid.data_ptr(), tsdf.data_ptr(), _ptr(near), _ptr(status)], 14)
+    return tsdf, status, near
+
+
+def voxelize_map_grid_accurate(depth: torch.Tensor, offsets: torch.Tensor, headers: torch.Tensor, xforms: torch.Tensor,
+                               grid: torch.Tensor, res: int = 32, layout: str = "czyx",
+                               cam: Optional[_lib.TsdfCam] = None, index: Optional[torch.Tensor] = None,
+                               out: Optional[torch.Tensor] = None, nearest: bool = False):
+    """The ACCURATE directional TSDF under per-frame maps, on a caller-supplied grid (``tsdf_voxelize_map_grid_accurate_hip``
+    of libtsdf_mapaccurate.so; include/tsdf_mapaccurate.h has the contract): per voxel the nearest MAPPED surface point
+    among ALL valid pixels of the crop, where :func:`voxelize_aug_grid` takes the one pixel the voxel projects to and
+    rejects the voxel when that pixel is empty.  It is :func:`voxelize_grid_accurate`'s search on
+    :func:`voxelize_aug_grid`'s arithmetic: a voxel whose nearest pixel is its projected one has the projective pass's bits,
+    a voxel with no mapped point within the truncation distance keeps the projective value.
+
+    depth / offsets / headers   the n_src source frames, as for :func:`voxelize`
+    xforms  float64[n,24] on the GPU  }  per BATCH POSITION: position i voxelizes its source frame under map i on row i
+    grid    float32[n,8] on the GPU   }  (vox_ori[3], voxel_len, trunc_dis, 3 pad words: what :func:`map_grids` returns)
+    cam     a :class:`TsdfCam` or None (the MSRA defaults); its five constants go to the entry by value
+    index   optional int64[n] on the GPU: batch position i voxelizes source frame index[i] (repeats allowed; an entry
+            outside [0, n_src) gives that position status 2 and a zero volume).  Without it the batch is the n_src frames
+    out     optional preallocated ``float32[n,3,R,R,R]`` (a contiguous view of a larger buffer will do) to write into
+    nearest True: also ``int32[n,R,R,R]``, per voxel the row-major crop index of its nearest pixel, -1 for a far voxel,
+            in the index order of one channel of the volume
+    Returns ``(tsdf float32[n,3,R,R,R], status int32[n])``, with ``nearest`` a third tensor.  A bad header (2) or an
+    unusable grid row (1) gives a zero volume; a frame without a valid pixel gets a zero volume with status 0.  Only the
+    forward rows of a map enter the distances and the search window; the inverse rows serve the projection that gives the
+    sign.  One launch on the current stream, no synchronisation.  Float32 only: :func:`narrow_volumes` follows where
+    2-byte voxels are wanted (the pass is bound by its search, not by its stores)."""
+    tsdf, status, near = _map_grid_accurate(depth, offsets, headers, xforms, grid, res, layout, cam, index, out, True, nearest)
+    return (tsdf, status, near) if nearest else (tsdf, status)
+
+
+def voxelize_aug_accurate(depth: torch.Tensor, offsets: torch.Tensor, headers: torch.Tensor, xforms: torch.Tensor,
+                          res: int = 32, layout: str = "czyx", dtype: Optional[torch.dtype] = None,
+                          cam: Optional[_lib.TsdfCam] = None, gt: Optional[torch.Tensor] = None, clamp: bool = True,
+                          index: Optional[torch.Tensor] = None):
+    """:func:`voxelize_aug` with the accurate directional TSDF: :func:`map_grids` places the grid under the maps and
+    :func:`voxelize_map_grid_accurate` writes the volume on its rows, on one stream with nothing on the host in between;
+    with ``dtype`` (torch.float16 / torch.bfloat16) :func:`narrow_volumes` follows and ``tsdf`` has that type.
+    ``max_l`` / ``mid_p`` / ``status`` are the placement's, bit for bit those of :func:`voxelize_aug`.
+
+    xforms  float64[n,24] on the GPU, one map per batch position; ``index`` (int64[n] on the GPU) draws the batch from the
+            source frames as for :func:`voxelize_map_grid_accurate`
+    gt      optional float32[n_src,3J] (or [n_src,J,3]) on the GPU: returns ``(TsdfBatch, gt_nor, gt_aug)`` as
+            :func:`voxelize_aug_lowp` does, the values the fused projective entry writes."""
+    if dtype is not None:
+        _lowp_dtype(dtype)
+    mg = map_grids(depth, offsets, headers, xforms, res=res, cam=cam, index=index)
+    tsdf, _, _ = _map_grid_accurate(depth, offsets, headers, xforms, mg.grid, res, layout, cam, index, None, False)
+    if dtype is not None:
+        tsdf = narrow_volumes(tsdf, dtype=dtype)
     batch = TsdfBatch(tsdf, mg.max_l, mg.mid_p, mg.status)
     if gt is None:
         return batch
