@@ -2,7 +2,8 @@
 what it reaches, tests/test_resolutions_gpu.py runs it).  Test infrastructure only.
 
 Restated from the host code: ``split_plan`` (csrc/launch.inc), ``slab_plan`` (csrc/slab.inc), the predicates of the voxel
-pass (csrc/phase2.inc: the lane mapping, the dynamic units; csrc/kernels.inc: ``use_tab``; csrc/common.inc: ``groups_for``)
+pass (csrc/phase2.inc: the lane mapping, the dynamic units; csrc/kernels.inc: ``use_tab``; csrc/common.inc: ``groups_for``),
+the halving loop of the two accurate entries (csrc/tsdf_accurate.hip, csrc/tsdf_mapaccurate.hip: ``accurate_plan``)
 and the string of ``tsdf_describe_launch`` (csrc/abi.inc).  Nothing here is read from the library."""
 import functools
 import importlib
@@ -96,6 +97,45 @@ def slab_ragged(R, V):
 def lowp_items(R):
     """V of the 16-bit slab kernels."""
     return 8 if R % 8 == 0 else 4
+
+
+# ---- csrc/tsdf_accurate.hip, csrc/tsdf_mapaccurate.hip: slab_plan, then the halving loop ----
+K_MIN_BLOCKS = 1024    # workgroups an accurate launch aims for at least (kMinBlocks)
+
+
+def accurate_plan(n, R):
+    """(slab, nslab, halvings) of the two accurate entries: slab.inc's plan at V = 4, the slab halved (rounding up) while
+    it holds more than one slice and the launch fewer than kMinBlocks workgroups."""
+    slab, nslab = slab_plan(R, 4)
+    halvings = 0
+    while slab > 1 and n * nslab < K_MIN_BLOCKS:
+        slab = (slab + 1) // 2
+        nslab = (R + slab - 1) // slab
+        halvings += 1
+    return slab, nslab, halvings
+
+
+def accurate_batch_sizes(R):
+    """[(n, regime)] the accurate entries are launched at:
+    'one'      n = 1, the slab halved as often as the loop ever halves it at R (not at all from R = 48 on, where
+               slab_plan's slab is one slice already);
+    'partway'  the smallest n at which the slab is halved exactly once less than at n = 1 and still at least once: the
+               loop stops partway.  A resolution has this state only if n = 1 halves twice or more (R <= 28); at the
+               others the size is left out;
+    'whole'    the smallest n at which nothing is halved: n * nslab >= kMinBlocks with slab_plan's own slab."""
+    h1 = accurate_plan(1, R)[2]
+    _, nslab0 = slab_plan(R, 4)
+    out = [(1, "one")]
+    if h1 >= 2:
+        out.append((next(n for n in range(1, K_MIN_BLOCKS + 1) if accurate_plan(n, R)[2] == h1 - 1), "partway"))
+    out.append(((K_MIN_BLOCKS + nslab0 - 1) // nslab0, "whole"))
+    return out
+
+
+def accurate_last_slab(n, R):
+    """Slices of the last slab of a position (== slab unless it is ragged)."""
+    slab, nslab, _ = accurate_plan(n, R)
+    return R - (nslab - 1) * slab
 
 
 # ---- csrc/abi.inc::tsdf_describe_launch ----

@@ -253,6 +253,8 @@ def test_preprocess_tree_tsdf_through_stubbed_hooks(pkg, synth, tmp_path, monkey
 
 
 # ---- the reference, on the inputs of the GPU tier ----
+# (the dense ones; the sparse frames of tests/sparse_ref.py, whose grids and cameras are their own, have their reference's
+# properties and both lists' search windows checked in tests/test_window_cpu.py)
 CASES = ar.all_cases()
 
 

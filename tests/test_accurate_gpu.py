@@ -1,7 +1,8 @@
 """GPU tier of the accurate directional TSDF (include/tsdf_accurate.h): tsdf_grid_accurate_kernel against the brute-force
 float64 reference of tests/accurate_ref.py under that file's comparison rules — outside the fragile set ``nearest`` is
 equal, far voxels are bit-exact, near values lie within 1e-5; the fragile set may hold at most 1e-4 of a case's voxels (it is
-empty on every input here: tests/test_accurate_cpu.py) —, then the batch behaviour, bad inputs, another camera, graph
+empty on every input here: tests/test_accurate_cpu.py, tests/test_window_cpu.py) —, the sparse frames that reach the
+edges of the search window (tests/sparse_ref.py), then the batch behaviour, bad inputs, another camera, graph
 capture and the consumers.  The references are computed once per case, shared and never modified."""
 import os
 import sys
@@ -13,6 +14,7 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import accurate_ref as ar  # noqa: E402
 import locate_ref as lr  # noqa: E402
+import sparse_ref as sp  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -72,6 +74,18 @@ def test_shifted_grid_most_voxels_far(pkg, layout):
     assert c["ref"]["near"].mean() < 0.5
     tsdf, nn = run_case(pkg, c, 12, layout, "synth1 R=12 shifted")
     assert bool((nn == -1).any()) and bool((nn >= 0).any())
+
+
+# ---- the search window ----
+@pytest.mark.parametrize("layout", LAYOUTS)
+@pytest.mark.parametrize("name", list(sp.PLAIN))
+def test_sparse_frames_reach_the_search_windows_edges(pkg, name, layout):
+    """The sparse frames of tests/sparse_ref.py, under their own cameras: inputs on which a search window that is slightly
+    too small loses the nearest pixel (tests/test_window_cpu.py counts what each mistake would lose on them) — a frame of
+    negative depths, a grid that reaches within T of the camera plane (items with no finite rectangle next to windowed ones),
+    a crop box whose four sides cut windows."""
+    c = sp.plain_case(name)
+    run_case(pkg, c, c["R"], layout, f"sparse {name}", cam=None if c["cam"] is None else pkg.TsdfCam(*c["cam"]))
 
 
 # ---- batch behaviour ----

@@ -2,8 +2,11 @@
 
 The smallest shape at which a 32-bit index can fail is 2^31 elements, so the buffers here are that size and no larger:
  (a) a 7-frame pack whose crops sit at element offsets around 2^30 (byte 2^32) and 2^31, every entry that reads a pack
-     against the same entry on a compact pack of the same crops, bit for bit;
- (b) 344 volumes at 128^3 (8.65 GB of float32, 4.3 GB of 16-bit voxels), every position against the oracle;
+     (``ENTRIES`` and voxelize_indexed; the two accurate entries voxelize_grid_accurate and voxelize_map_grid_accurate
+     among them, with their ``nearest``) against the same entry on a compact pack of the same crops, bit for bit;
+ (b) 344 volumes at 128^3 (8.65 GB of float32, 4.3 GB of 16-bit voxels) from voxelize, voxelize_aug, voxelize_aug_grid,
+     voxelize_grid_lowp and voxelize_map_grid_lowp, every position against the oracle; and 513 volumes at 128^3 with
+     their ``nearest`` (17.3 GiB) from each accurate entry, on sparse frames, against the brute-force reference;
  (c) widen_depth16 and narrow_volumes over 2^31 + 4099 elements against torch's own arithmetic;
  (d) locate_hands on 699,060 frames of 64 x 48 (more than 2^31 pixels), uint16 and float32, against a compact tensor.
 Each test states its need of device memory, asks the device first and skips (with both figures) if that plus 2 GiB is not
@@ -13,6 +16,7 @@ import functools
 import importlib
 import os
 import sys
+import time
 import types
 
 import numpy as np
@@ -22,11 +26,13 @@ import torch
 import oracle
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import accurate_ref as acr  # noqa: E402
 import auggrid_ref as ar  # noqa: E402
 import locate_ref as lr  # noqa: E402
 import plan_ref as pr  # noqa: E402
+import sparse_ref as sp  # noqa: E402
 from test_lowp_gpu import in_band  # noqa: E402
-from test_resolutions_gpu import cu_count, cycle, dev, up, worst_error  # noqa: E402
+from test_resolutions_gpu import accurate_launch, accurate_sources, cu_count, cycle, dev, up, worst_error  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -228,6 +234,17 @@ def _map_grids_and_lowp(pkg, P, A, idx):
     return out
 
 
+def _voxelize_grid_accurate(pkg, P, A, idx):
+    tsdf, st, nn = pkg.voxelize_grid_accurate(P.d, P.o, P.h, A.rows, res=R_A, index=idx, nearest=True)     # rows of SOURCES
+    return dict(tsdf=tsdf, status=st, nearest=nn)
+
+
+def _voxelize_map_grid_accurate(pkg, P, A, idx):
+    xf, arows = (A.xf, A.arows) if idx is None else (A.xf.index_select(0, idx), A.arows.index_select(0, idx))
+    tsdf, st, nn = pkg.voxelize_map_grid_accurate(P.d, P.o, P.h, xf, arows, res=R_A, index=idx, nearest=True)
+    return dict(tsdf=tsdf, status=st, nearest=nn)
+
+
 def _map_step_head(pkg, P, A, idx):
     # (position i draws from counter0 + i: the 4-frame pack's frames are given the table positions as their counters)
     counters = A.pos if idx is None else None
@@ -252,6 +269,8 @@ ENTRIES = {
     "voxelize_aug_grid": (_voxelize_aug_grid, False, ("tsdf",)),
     "voxelize_grid_lowp": (_voxelize_grid_lowp, True, ("tsdf_bf16", "tsdf_f16")),
     "map_grids_and_voxelize_map_grid_lowp": (_map_grids_and_lowp, True, ("grid", "tsdf_bf16", "tsdf_f16")),
+    "voxelize_grid_accurate": (_voxelize_grid_accurate, True, ("tsdf",)),
+    "voxelize_map_grid_accurate": (_voxelize_map_grid_accurate, True, ("tsdf",)),
     "map_step_head": (_map_step_head, True, ("grid",)),
     "process_batch": (_process_batch, False, ("points", "tsdf")),
 }
@@ -284,6 +303,8 @@ def test_pack_offsets_beyond_2_31(pkg, packs, entry):
     for k in zero:
         assert not bool(big[k][fl].float().abs().sum() != 0) and not bool(torch.isnan(big[k].float()).any()), (entry, k)
         assert all(bool((big[k][p] != 0).any()) for p in ks), (entry, k)
+    if "nearest" in big:       # the accurate entries: a filler names no pixel, every crop has near voxels
+        assert bool((big["nearest"][fl] == -1).all()) and all(bool((big["nearest"][p] >= 0).any()) for p in ks), entry
     if entry == "voxelize":    # once: the big pack's volumes against the oracle itself
         depth, off, hdr = _crops()
         ref = oracle.voxelize(depth, off, hdr, R=R_A, n_threads=4)
@@ -308,7 +329,7 @@ def test_pack_offsets_beyond_2_31_through_an_index(pkg, packs, entry):
     for k in _status_keys(big):
         assert big[k].tolist() == [0] * 5, (entry, k)
     for k in big:
-        if k.startswith("tsdf") or k == "grid":
+        if k.startswith("tsdf") or k in ("grid", "nearest"):
             assert all(bool((big[k][p] != 0).any()) for p in range(5)), (entry, k)
             # positions 1 and 4 are both K3 (under the same map; the step head draws a map per position)
             assert same(big[k][1], big[k][4]) == (entry != "map_step_head") and not same(big[k][0], big[k][1]), (entry, k)
@@ -442,6 +463,43 @@ def test_volume_outputs_beyond_2_31(pkg, big_batch, record_property, entry):
         record_property("copies_identical", ident)
     report_peak(entry)
     del results
+    torch.cuda.empty_cache()
+
+
+N_ACC = 513                            # positions of the accurate entries' case: 171 cycles of the three sparse sources
+
+
+@pytest.mark.parametrize("kind,layout", [("plain", "czyx"), ("mapped", "cxyz")], ids=["voxelize_grid_accurate", "voxelize_map_grid_accurate"])
+def test_accurate_outputs_beyond_2_31(pkg, record_property, kind, layout):
+    """(b) The two accurate entries at 128^3 with 513 positions cycling over the three sparse sources of
+    tests/sparse_ref.py (a dense crop puts their brute-force reference out of reach at this R): the volume holds 3.2e9
+    elements — position 170 crosses byte 2^32, position 341 element 2^31 — and ``nearest`` 4.30e9 bytes: its last position
+    begins at byte 2^32.  Positions 0..2 against the reference under accurate_ref.compare, every later position equal to
+    position i % 3 bit for bit, in chunks on the device.  One layout each: the in-volume index is the same int64 expression
+    in both kernels.  Needs 17.3 GiB of outputs (12.9 GiB of volumes, 4.3 GiB of ``nearest``) and 0.7 GiB to compare."""
+    need_memory(18)
+    k, R3 = sp.K_RES, R_B ** 3
+    cycles = N_ACC // k
+    assert N_ACC == cycles * k and N_ACC * VOL > P31 and 170 * VOL * 4 < (1 << 32) < 171 * VOL * 4 and 341 * VOL < P31 < 342 * VOL
+    assert (N_ACC - 1) * R3 * 4 == 1 << 32 and pr.accurate_plan(N_ACC, R_B) == (1, R_B, 0)
+    t0 = time.perf_counter()
+    a = accurate_sources(kind, R_B)
+    t1 = time.perf_counter()
+    tsdf, st, nn = accurate_launch(pkg, a, N_ACC, layout)
+    torch.cuda.synchronize()
+    t2 = time.perf_counter()
+    assert tsdf.shape == (N_ACC, 3, R_B, R_B, R_B) and nn.shape == (N_ACC, R_B, R_B, R_B) and not bool(st.any())
+    wv, wn, wf = sp.res_in_layout(a.ref, layout)
+    acr.compare(tsdf[:k].cpu().numpy(), nn[:k].cpu().numpy(), wv, wn, wf, f"{kind} R={R_B} {layout} n={N_ACC}")
+    v, q = tsdf.view(cycles, k * VOL).view(torch.int32), nn.view(cycles, k * R3)
+    for c0 in range(1, cycles, 8):
+        assert bool((v[c0:c0 + 8] == v[0]).all()), (kind, "volume", c0)
+        assert bool((q[c0:c0 + 8] == q[0]).all()), (kind, "nearest", c0)
+    t3 = time.perf_counter()
+    print(f"{kind} {N_ACC} x {R_B}^3: reference {t1 - t0:.2f} s, launch {t2 - t1:.2f} s, comparison {t3 - t2:.2f} s")
+    record_property("launch_seconds", t2 - t1)
+    report_peak(f"accurate {kind}")
+    del a, tsdf, st, nn, v, q
     torch.cuda.empty_cache()
 
 

@@ -419,6 +419,8 @@ def test_augmented_step_accurate_chain(V, rec, pack, monkeypatch, head, dtype, w
 
 
 # ---- the reference, on the inputs of the GPU tier ----
+# (the dense ones; the sparse frames of tests/sparse_ref.py, whose grids and cameras are their own, have their reference's
+# properties and both lists' search windows checked in tests/test_window_cpu.py)
 CASES = mr.all_cases()
 
 

@@ -2,7 +2,8 @@
 tsdf_map_grid_accurate_kernel against the brute-force float64 reference of tests/mapaccurate_ref.py under
 ``accurate_ref.compare`` — outside the fragile set ``nearest`` is equal, far voxels are bit-exact, near values lie within
 1e-5; the fragile set may hold at most 1e-4 of a case's voxels (it is empty on every input here:
-tests/test_mapaccurate_cpu.py) —, then the batch behaviour, bad inputs, another camera, graph capture, the relation to the
+tests/test_mapaccurate_cpu.py, tests/test_window_cpu.py) —, the sparse frames that reach the edges of the search window
+(tests/sparse_ref.py), then the batch behaviour, bad inputs, another camera, graph capture, the relation to the
 plain accurate pass and the consumers.  The references are computed once per case, shared and never modified."""
 import os
 import sys
@@ -15,6 +16,7 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import accurate_ref as ar  # noqa: E402
 import map_geom_ref as mg  # noqa: E402
 import mapaccurate_ref as mr  # noqa: E402
+import sparse_ref as sp  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -118,6 +120,24 @@ def test_broken_forward_parts_among_good_positions(pkg):
         tsdf, nn = run(pkg, keys, 12, layout, "broken")
         assert bool((nn[1] >= 0).any())                                # diag(1, 1, 0): just arithmetic, some voxels near
         assert bool((nn[3] == -1).all()) and not bool(torch.isnan(tsdf[3]).any())    # a NaN s wins no comparison
+
+
+# ---- the search window ----
+@pytest.mark.parametrize("layout", LAYOUTS)
+@pytest.mark.parametrize("name", list(sp.MAPPED))
+def test_sparse_frames_reach_the_search_windows_edges(pkg, name, layout):
+    """The sparse frames of tests/sparse_ref.py under shear / aniso / general / rx100 and their own cameras: inputs on which
+    a search window that is slightly too small loses the nearest pixel (tests/test_window_cpu.py counts what each mistake
+    would lose on them) — a frame of negative depths, a grid that reaches within the window's depth half-extent of the
+    camera plane (items with no finite rectangle next to windowed ones), a crop box whose four sides cut windows."""
+    c = sp.mapped_case(name)
+    R = c["R"]
+    td, to, th, tx, tg = up(c["depth"], c["off"], c["hdr"], c["xf"], c["grid"])
+    tsdf, st, nn = pkg.voxelize_map_grid_accurate(td, to, th, tx, tg, res=R, layout=layout, nearest=True,
+                                                  cam=None if c["cam"] is None else pkg.TsdfCam(*c["cam"]))
+    torch.cuda.synchronize()
+    assert tsdf.shape == (1, 3, R, R, R) and nn.shape == (1, R, R, R) and st.tolist() == [0]
+    check(tsdf, nn, [c], layout, f"sparse {name}")
 
 
 # ---- batch behaviour ----

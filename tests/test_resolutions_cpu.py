@@ -1,5 +1,5 @@
-"""CPU tier of the resolution tests: what the case list of tests/plan_ref.py reaches, shown on the restated launch plans,
-and the conditions on the oracle's volumes of the six source frames at all 32 resolutions — so that the GPU tier
+"""CPU tier of the resolution tests: what the case list of tests/plan_ref.py reaches, shown on the restated launch plans
+(those of the two accurate entries included: slab_plan followed by their halving loop), and the conditions on the oracle's volumes of the six source frames at all 32 resolutions — so that the GPU tier
 (tests/test_resolutions_gpu.py) compares volumes that hold rejected voxels and voxels near the surface everywhere."""
 import os
 import sys
@@ -78,6 +78,49 @@ def test_the_case_list_reaches_every_class(cus):
         assert {pr.slab_ragged(R, V) for R in pr.RES if pr.lowp_items(R) == V} == {True, False}, V
     # one position per workgroup and several workgroups per position
     assert {pr.slab_plan(R, pr.lowp_items(R))[1] == 1 for R in pr.RES} == {True, False}
+
+
+def test_the_accurate_plan_on_known_values():
+    """The figures the accurate entries' comments and their GPU tests state."""
+    assert pr.accurate_plan(1, 4) == (1, 4, 2) and pr.accurate_plan(1024, 4) == (4, 1, 0)
+    assert pr.accurate_plan(2, 20) == (1, 20, 3) and pr.accurate_plan(300, 20) == (6, 4, 0)       # 6 slices, the last slab 2
+    assert pr.accurate_plan(1100, 8) == (8, 1, 0) and pr.accurate_plan(1, 64) == (1, 64, 0)
+    assert pr.accurate_plan(1100, 12) == (12, 1, 0) and pr.accurate_plan(3, 12) == (1, 12, 4)     # 12 -> 6 -> 3 -> 2 -> 1
+    assert pr.accurate_batch_sizes(4) == [(1, "one"), (512, "partway"), (1024, "whole")]
+    assert pr.accurate_batch_sizes(128) == [(1, "one"), (8, "whole")]
+    assert pr.accurate_plan(512, 4) == (2, 2, 1) and pr.accurate_plan(511, 4) == (1, 4, 2)
+    assert pr.accurate_plan(103, 20) == (2, 10, 2) and pr.accurate_plan(102, 20) == (1, 20, 3)
+
+
+def test_the_accurate_case_list_reaches_every_plan():
+    """What tests/test_resolutions_gpu.py launches the two accurate entries at: every R, and among the final plans slabs of
+    one slice, slabs of several that divide R, slabs that leave a ragged last slab, and all three batch regimes."""
+    final = {(R, kind): (n, *pr.accurate_plan(n, R)) for R in pr.RES for n, kind in pr.accurate_batch_sizes(R)}
+    assert {R for R, _ in final} == set(pr.RES)
+    for R in pr.RES:
+        n1, slab, nslab, h1 = final[R, "one"]
+        assert (n1, slab, nslab) == (1, 1, R)                                 # n = 1: always one slice per workgroup
+        nw, slab, nslab, hw = final[R, "whole"]
+        assert hw == 0 and (slab, nslab) == pr.slab_plan(R, 4) and nw * nslab >= pr.K_MIN_BLOCKS > (nw - 1) * nslab
+        assert ((R, "partway") in final) == (h1 >= 2) == (R <= 28), R
+        if (R, "partway") in final:
+            n, slab, nslab, h = final[R, "partway"]
+            assert 1 <= h == h1 - 1 and 1 < slab < pr.slab_plan(R, 4)[0] and 1 < n < nw
+            assert n * nslab >= pr.K_MIN_BLOCKS and pr.accurate_plan(n - 1, R)[2] == h1      # the smallest such n
+        else:                                                                 # no partway state: the loop runs out or never runs
+            assert h1 <= 1 and {pr.accurate_plan(n, R)[2] for n in range(1, nw + 1)} == {h1, 0}
+    assert final[4, "whole"][0] == 1024 and final[128, "whole"][0] == 8
+    # from R = 48 on slab_plan's slab is one slice: 'one' and 'whole' differ in the batch only
+    assert [R for R in pr.RES if final[R, "one"][3] == 0] == list(range(48, 129, 4))
+    several = {(R, kind): v for (R, kind), v in final.items() if v[1] > 1}
+    divides = sorted({R for (R, _), v in several.items() if R % v[1] == 0})
+    ragged = sorted({R for (R, _), v in several.items() if R % v[1] != 0})
+    assert ragged == [20, 28] and len(divides) >= 8, (ragged, divides)        # (V = 4 has no other ragged slab_plan: below)
+    assert ragged == [R for R in pr.RES if pr.slab_ragged(R, 4)]
+    assert {pr.accurate_last_slab(final[R, "whole"][0], R) for R in ragged} == {1, 2}
+    # a slab that holds the whole position, and a halved slab of several slices, at several resolutions each
+    assert sorted(R for (R, kind), v in several.items() if v[2] == 1) == [4, 8, 12]
+    assert sorted(R for (R, kind), v in several.items() if kind == "partway") == [4, 8, 12, 16, 20, 24, 28]
 
 
 def test_the_sources():

@@ -5,10 +5,18 @@ tests/plan_ref.py, whose CPU tier (tests/test_resolutions_cpu.py) shows which br
 of slab_plan the list reaches and that every oracle volume used here holds rejected voxels and voxels near the surface.
 Every position of every batch is compared (on the device) with the oracle's result for its source: volumes within the
 contract's 1e-5 (include/tsdf.h), max_l / mid_p / status bit for bit, pixel maps equal, 16-bit volumes by the in_band rule
-of tests/test_lowp_gpu.py, grid rows bit for bit with their restatements."""
+of tests/test_lowp_gpu.py, grid rows bit for bit with their restatements.
+
+The entries, each called below: voxelize, voxelize_aug (the product kernels), voxel_pixels, voxelize_grid,
+voxelize_aug_grid, voxelize_grid_lowp, voxelize_map_grid_lowp, map_grids, map_step_head, cloud_grids, locate_hands(res=R),
+and the two accurate entries voxelize_grid_accurate and voxelize_map_grid_accurate.  The accurate ones have a reference of
+their own, brute force over (voxel, valid pixel) pairs, which a dense crop puts out of reach at R = 128: they run on the
+three sparse sources of tests/sparse_ref.py, one parametrized case per (R, kernel), at the batch sizes of
+``plan_ref.accurate_batch_sizes`` (their halving loop's regimes), under ``accurate_ref.compare``."""
 import ctypes
 import os
 import sys
+import time
 import types
 
 import numpy as np
@@ -18,10 +26,12 @@ import torch
 import oracle
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import accurate_ref as acr  # noqa: E402
 import auggrid_ref as ar  # noqa: E402
 import cloud_grid_ref as cg  # noqa: E402
 import locate_ref as lr  # noqa: E402
 import plan_ref as pr  # noqa: E402
+import sparse_ref as sp  # noqa: E402
 from test_lowp_gpu import in_band  # noqa: E402
 
 pytestmark = pytest.mark.gpu
@@ -260,3 +270,56 @@ def test_grid_rows_equal_their_restatements(pkg, src, case):
         assert np.array_equal(grid[i].view(np.uint32), wg.view(np.uint32)), (R, "locate_hands", i)
         assert max_l[i].view(np.uint32) == np.float32(wl).view(np.uint32), (R, "locate_hands", i)
         assert np.array_equal(mid_p[i].view(np.uint32), wm.view(np.uint32)), (R, "locate_hands", i)
+
+
+# ---- the two accurate entries ----
+def accurate_sources(kind, R):
+    """The three sparse sources of tests/sparse_ref.py on the device with their rows (and maps) at R, and their brute-force
+    references (numpy, indexed [z][y][x])."""
+    s = sp.res_sources(kind, R)
+    depth, off, hdr = sp.res_pack()
+    t = up(depth, off, hdr, s["grid"], sp.res_xforms())
+    return types.SimpleNamespace(kind=kind, R=R, ref=s, depth=t[0], off=t[1], hdr=t[2], grid=t[3], xf=t[4])
+
+
+def accurate_launch(pkg, a, n, layout):
+    """n positions cycling over the three sources (position i holds source i % 3) -> (tsdf, status, nearest)."""
+    idx = torch.arange(n, dtype=torch.int64, device=dev()) % sp.K_RES
+    if a.kind == "plain":       # rows of SOURCES
+        return pkg.voxelize_grid_accurate(a.depth, a.off, a.hdr, a.grid, res=a.R, layout=layout, index=idx, nearest=True)
+    return pkg.voxelize_map_grid_accurate(a.depth, a.off, a.hdr, cycle(a.xf, n), cycle(a.grid, n), res=a.R, layout=layout,
+                                          index=idx, nearest=True)      # maps and rows of POSITIONS
+
+
+@pytest.mark.parametrize("kind", ["plain", "mapped"])
+@pytest.mark.parametrize("R", pr.RES, ids=lambda R: "R%d" % R)
+def test_accurate_entries_at_every_resolution(pkg, R, kind):
+    """voxelize_grid_accurate / voxelize_map_grid_accurate (three maps, one of them ``general``) at n = 1, at the smallest n
+    at which their slab is halved once less than at n = 1 (where R has such a state: R <= 28) and at the smallest n at which
+    it is not halved at all, both layouts.  Positions 0..2 against the brute-force reference under accurate_ref.compare; every
+    later position equal to position i % 3 bit for bit in volume, ``nearest`` and status, and position 0 the same bits in
+    every launch: a voxel's bits depend on neither its slab nor its batch position."""
+    t0 = time.perf_counter()
+    a = accurate_sources(kind, R)
+    t_ref = time.perf_counter() - t0
+    k = sp.K_RES
+    for layout in LAYOUTS:
+        wv, wn, wf = sp.res_in_layout(a.ref, layout)
+        first = None
+        for n, regime in pr.accurate_batch_sizes(R):
+            tsdf, st, nn = accurate_launch(pkg, a, n, layout)
+            torch.cuda.synchronize()
+            what = (kind, R, layout, n, regime, pr.accurate_plan(n, R))
+            assert tsdf.shape == (n, 3, R, R, R) and nn.shape == (n, R, R, R) and not bool(st.any()), what
+            m = min(n, k)
+            acr.compare(tsdf[:m].cpu().numpy(), nn[:m].cpu().numpy(), wv[:m], wn[:m], wf[:m],
+                        f"{kind} R={R} {layout} n={n} ({regime}: slab {what[5][0]})")
+            if n > k:
+                assert torch.equal(fbits(tsdf), fbits(cycle(tsdf[:k], n))) and torch.equal(nn, cycle(nn[:k], n)), what
+            if first is None:
+                first = (tsdf[0].clone(), nn[0].clone())
+            else:
+                assert torch.equal(fbits(tsdf[0]), fbits(first[0])) and torch.equal(nn[0], first[1]), what
+            del tsdf, st, nn
+    print(f"{kind} R={R}: {time.perf_counter() - t0:.2f} s in all, {t_ref:.2f} s of it the reference")
+    torch.cuda.empty_cache()
