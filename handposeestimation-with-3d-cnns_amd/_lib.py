@@ -226,19 +226,14 @@ _EXTS = {
         "tsdf_voxelize_grid_accurate_hip": [_vp, _i64, _vp, _vp, _i64, _vp, _i, _i, ctypes.c_double, ctypes.c_double,
                                             ctypes.c_double, ctypes.c_float, ctypes.c_float, _i, _vp, _vp, _vp, _vp, _vp],
     }),
+    "mapaccurate": _Ext(MAPACCURATE_LIB_PATH, "tsdf_mapaccurate_version", MAPACCURATE_VERSION, {
+        # depth, depth_len, offsets, headers, n_src, index, n, R, focal, cx, cy, invalid_eps, trunc_voxels (the camera by
+        # value), layout, stream, xforms, grid, tsdf, nearest, status
+        "tsdf_voxelize_map_grid_accurate_hip": [_vp, _i64, _vp, _vp, _i64, _vp, _i, _i, ctypes.c_double, ctypes.c_double,
+                                                ctypes.c_double, ctypes.c_float, ctypes.c_float, _i, _vp, _vp, _vp, _vp, _vp,
+                                                _vp],
+    }),
 }
-
-# libtsdf_mapaccurate.so's row stands OUTSIDE the table, as its build rule stands outside the `EXTS :=` line:
-# tests/test_ext_table_cpu.py pins both to exactly the ten libraries above, and adding a library does not edit an existing
-# test.  It is the same kind of row, loaded by the same code (_load_row); moving it in is this row under the key
-# "mapaccurate", a name on that line and a name in that test's list.
-_MAPACCURATE = _Ext(MAPACCURATE_LIB_PATH, "tsdf_mapaccurate_version", MAPACCURATE_VERSION, {
-    # depth, depth_len, offsets, headers, n_src, index, n, R, focal, cx, cy, invalid_eps, trunc_voxels (the camera by
-    # value), layout, stream, xforms, grid, tsdf, nearest, status
-    "tsdf_voxelize_map_grid_accurate_hip": [_vp, _i64, _vp, _vp, _i64, _vp, _i, _i, ctypes.c_double, ctypes.c_double,
-                                            ctypes.c_double, ctypes.c_float, ctypes.c_float, _i, _vp, _vp, _vp, _vp, _vp,
-                                            _vp],
-})
 
 _lib = None
 _debug_lib = None
@@ -332,14 +327,12 @@ def load_debug():
 
 
 def _load_ext(name: str):
-    """Load libtsdf_<name>.so, a row of the table, once and declare its entry points; raise loudly if it is not there."""
+    """Load libtsdf_<name>.so, a row of the table, once: the file must exist, its entry points are declared, its version
+    must be the row's, and the library is kept in ``_ext_libs`` under ``name``; raise loudly if it is not there."""
     L = _ext_libs.get(name)
-    return L if L is not None else _load_row(name, _EXTS[name])
-
-
-def _load_row(name: str, ext: _Ext):
-    """What loading any row is: the file must exist, its entry points are declared, its version must be the row's, and the
-    library is kept in ``_ext_libs`` under ``name``."""
+    if L is not None:
+        return L
+    ext = _EXTS[name]
     if not os.path.exists(ext.path):
         raise ImportError(f"{ext.path} not found: build it with `make -C handposeestimation-with-3d-cnns_amd/csrc "
                           f"{name}` (__graft_entry__.build() does). There is no CPU fallback.")
@@ -403,9 +396,8 @@ def load_accurate():
 
 
 def load_mapaccurate():
-    """libtsdf_mapaccurate.so, the library of include/tsdf_mapaccurate.h (its row: _MAPACCURATE, read at call time)."""
-    L = _ext_libs.get("mapaccurate")
-    return L if L is not None else _load_row("mapaccurate", _MAPACCURATE)
+    """libtsdf_mapaccurate.so, the library of include/tsdf_mapaccurate.h."""
+    return _load_ext("mapaccurate")
 
 
 @contextlib.contextmanager

@@ -10,7 +10,8 @@
 //   slab_bad_shape   host: the R / layout test of an entry (device.inc::bad_res and the layout enum)
 //   slab_args_ok     host: the argument checks every entry makes between `n == 0` and the device, with the plan
 //   slab_src         host: a SlabSrc from an entry's arguments, its camera and its plan
-// The voxel arithmetic of each kernel and the tail of its argument struct stay in its own file.
+// The voxel arithmetic of each kernel and the tail of its argument struct stay in its own file; what the two accurate
+// kernels share beyond this (their search rectangle, bad-frame tail, store and launch) is in search.inc.
 
 constexpr int kSlabWG = 256;       // threads per workgroup (4 wave64)
 constexpr int kSlabMaxR = 128;     // largest resolution (device.inc::bad_res)

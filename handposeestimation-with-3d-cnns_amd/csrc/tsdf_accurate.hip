@@ -3,18 +3,19 @@
 //
 // A translation unit and a library of its own, next to libtsdf_hip.so and the other extension libraries (all frozen).  It
 // takes the status codes and the layout enum from include/tsdf.h, the host preamble every library here has from
-// device.inc, the device primitives from prim.inc and the slab scaffold it shares with tsdf_auggrid.hip, tsdf_lowp.hip and
-// tsdf_maplowp.hip from slab.inc; the plain contract's projection and sign rule are RESTATED here operation for operation
+// device.inc, the device primitives from prim.inc, the slab scaffold it shares with tsdf_auggrid.hip, tsdf_lowp.hip and
+// tsdf_maplowp.hip from slab.inc and what it shares with tsdf_mapaccurate.hip alone — the search rectangle, the bad-frame
+// tail, the item's store, the host's halving and launch — from search.inc; the plain contract's projection and sign rule are RESTATED here operation for operation
 // as tsdf_lowp.hip has them, and there is no device global: every launch is self-contained.
 //
 // tsdf_grid_accurate_kernel: n x ceil(R / slab) workgroups of 256 threads; a workgroup owns `slab` consecutive slices
 // (indices of the slowest output axis) of one batch position — slab.inc's slab, halved while the launch would hold fewer
-// than kMinBlocks workgroups.  It
+// than kMinBlocks workgroups (search.inc).  It
 //   1. resolves its source frame (the index, if any) and checks the frame's header and grid row (all uniform); a position
 //      that is not OK has its slab filled with zeros (nearest: -1) and workgroup 0 of the position writes the status;
 //   2. walks its slab in items of 4 consecutive voxels of the fastest axis, one item per lane and pass.  Per item:
 //      a. the plain contract's projection, gather and sign rule for each of the 4 voxels (`sv`: 0 rejected, else +-1);
-//      b. the SEARCH REGION of the item, a pixel rectangle (below);
+//      b. the SEARCH REGION of the item, a pixel rectangle (below; search.inc::search_rect);
 //      c. one row-major walk of that rectangle: per valid pixel the z term of each voxel first (one per item in layout
 //         czyx, where the 4 voxels share z) and, where some |tz| <= 1, the float64 evaluation of s for those voxels;
 //         (best s, row, column) is kept with a strict <, so ties stay with the lowest index;
@@ -23,30 +24,16 @@
 // No LDS, no work queue, no communication between workgroups, no atomics.  Compiled with -ffp-contract=off, fma only where
 // __builtin_fma is written.
 //
-// WHAT MAY BE DISCARDED BEFORE s IS EVALUATED.  The contract allows only candidates that provably have
-// s > min(1, best so far).  A candidate with s > 1 never decides anything: if the true minimum is <= 1 the minimiser and
-// every pixel that ties with it have s <= 1, and if it is > 1 the voxel is far and names no pixel.  Two tests use that:
-//   The z term.  The kernel's s is fma(tz, tz, fma(ty, ty, tx * tx)) with tz = fma(d, it, vs_z).  For a float64 |tz| > 1,
-//     tz^2 >= (1 + 2^-52)^2 > 1 + 2^-52, the inner fma is the rounding of a non-negative real and so >= 0, and rounding is
-//     monotone: the evaluated s would be >= 1 + 2^-52 > 1.  Skipping on !(|tz| <= 1) therefore skips exactly candidates
-//     whose EVALUATED s exceeds 1 (or is a NaN, which wins no comparison): no margin is needed.
-//   The rectangle.  |v - w| <= T (T = trunc_dis) bounds each coordinate: |w_z - v_z| <= T puts the depth d = -w_z into
-//     [-v_z - T, -v_z + T], and |w_x - v_x| <= T with w_x = (col - cx) * d / F gives col = cx + F * w_x / d, a quotient that
-//     is monotone in w_x and in d separately while d keeps one sign — so over the box [v_x - T, v_x + T] x [d_lo, d_hi] its
-//     extremes are at the four corners (likewise row = cy - F * w_y / d).  The kernel uses T' = T * (1 + 2^-20) and, for
-//     the 4 voxels of an item, the union of their coordinate ranges; it rounds the corner values outwards by floor - 1 /
-//     ceil + 1 and clips to the crop.  A pixel outside has a real |t_c| > 1 + 2^-20 in some coordinate, a real
-//     s > 1 + 2^-19, and with the contract's evaluation error of 2^-40 (relative beyond s = 2) an evaluated s > 1.  The
-//     corner values carry a few roundings of relative 2^-53 on pixel coordinates that matter only inside the crop, i.e.
-//     below 2^31: far less than the one pixel added; a NaN bound (cx or cy is not judged) selects the whole side.
-//     A valid pixel has |d| >= eps.  When the depth interval does not stay on one side of zero by eps — the voxel lies
-//     within T' (+ eps) of the camera plane — the quotient is unbounded: there is NO finite rectangle and the whole crop is
-//     walked.
+// THE SEARCH REGION.  search.inc has the argument for what may be discarded before s is evaluated (the z term, the
+// corner-quotient rectangle) and the rectangle itself; what is this file's is why its six arguments bound a point w within
+// T' of a voxel v.  Here the voxel and the points live in ONE frame, the camera's, so |v - w| <= T' bounds each coordinate
+// by itself: w_x in [v_x - T', v_x + T'], w_y likewise, and |w_z - v_z| <= T' puts the depth d = -w_z into
+// [-v_z - T', -v_z + T'].  Over the 4 voxels of an item the ranges are united: [xlo - T', xhi + T'] along the fastest axis
+// of layout czyx (cxyz: the z range), one y.  The depth interval meets zero by eps where the item lies within T' (+ eps)
+// of the camera plane: then the whole crop is walked.
 // Tried and not kept ("Accurate directional TSDF"): a per-tile (min, max) depth cull in LDS — on hand crops a
 // tile's depth range meets most voxels' interval, and the tile walk cost twice the time of this one.  Not tried: a float32
 // screen, the slab's union window staged in LDS, several pixels per loop trip.
-//
-// The stores: plain 16-byte vector stores, as in tsdf_auggrid.hip; the kernel is bound by its search, not by its stores.
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -61,12 +48,7 @@ namespace {
 #include "device.inc"   // check_device, launched, misaligned: the host preamble of every library here
 #include "prim.inc"     // cam_ok, trunc_i32, finite32, f32_round_up, header_ok
 #include "slab.inc"     // workgroup <-> slab, the frame's header and grid row, zero-fill, host sizing
-
-typedef float acc_f4 __attribute__((ext_vector_type(4)));
-typedef int acc_i4 __attribute__((ext_vector_type(4)));
-
-constexpr int V = 4;   // voxels per lane and item: one 16-byte store per channel
-constexpr int64_t kMinBlocks = 1024;   // workgroups a launch aims for at least: four per CU of an MI355X
+#include "search.inc"   // the item, the search rectangle, the bad-frame tail, the item's store, the host's halving and launch
 
 struct AccArgs {
   SlabSrc src;
@@ -77,16 +59,6 @@ struct AccArgs {
   int32_t *nearest;         // [n][R][R][R] or null
   int32_t *status;          // [n] or null
 };
-
-// lower clip of a window bound: max(lo, min(hi, b)) as an int; a NaN gives lo (the whole side)
-__device__ __forceinline__ int clip_lo(double b, int lo, int hi) {
-  return !(b > (double)lo) ? lo : (b < (double)hi ? trunc_i32(b) : hi);
-}
-
-// upper clip: min(hi, max(lo, b)); a NaN gives hi
-__device__ __forceinline__ int clip_hi(double b, int lo, int hi) {
-  return !(b < (double)hi) ? hi : (b > (double)lo ? trunc_i32(b) : lo);
-}
 
 template <int LAYOUT>
 __global__ __launch_bounds__(kSlabWG) void tsdf_grid_accurate_kernel(AccArgs a) {
@@ -103,14 +75,7 @@ __global__ __launch_bounds__(kSlabWG) void tsdf_grid_accurate_kernel(AccArgs a) 
   const int left = fr.left, top = fr.top, right = fr.right, bottom = fr.bottom;
   const int64_t bw = fr.bw;
   const int64_t per = (int64_t)(se - sb) * R * RV;   // 16-byte pieces of the slab, per channel
-  if (slab_bad_frame<acc_f4>(fr, blk, a.status, out, R, per, tid)) {
-    if (nearest) {
-      const acc_i4 none = {-1, -1, -1, -1};
-      acc_i4 *p = reinterpret_cast<acc_i4 *>(nearest + (int64_t)sb * R * R);
-      for (int64_t q = tid; q < per; q += kSlabWG) p[q] = none;
-    }
-    return;
-  }
+  if (search_bad_frame(fr, blk, a.status, out, nearest, R, per, tid)) return;
 
   // per-frame constants, as tsdf_lowp.hip has them
   const double F = a.src.focal, cx = a.src.cx, cy = a.src.cy;
@@ -118,7 +83,7 @@ __global__ __launch_bounds__(kSlabWG) void tsdf_grid_accurate_kernel(AccArgs a) 
   const double T = (double)fr.td;
   const double it = 1.0 / T;
   const double kq = a.inv_focal * it;
-  const double Tw = T * (1.0 + 0x1p-20);   // the window's truncation distance (see the head of this file)
+  const double Tw = T * (1.0 + 0x1p-20);   // the window's truncation distance T' (search.inc)
   const float eps = a.eps;
   const double epsd = (double)eps;
   const float *__restrict__ d = a.src.depth + fr.off0;
@@ -156,25 +121,9 @@ __global__ __launch_bounds__(kSlabWG) void tsdf_grid_accurate_kernel(AccArgs a) 
     }
 
     // ---- b. the item's search rectangle [c0, c1) x [r0, r1), image coordinates ----
-    int c0 = left, c1 = right, r0 = top, r1 = bottom;
-    {
-      const double dlo = -zhi - Tw, dhi = -zlo + Tw;             // depths of points within T' along z
-      if (dlo >= epsd || dhi <= -epsd) {                         // one sign, away from zero: a finite rectangle
-        const double i0 = 1.0 / dlo, i1 = 1.0 / dhi;
-        const double xa = xlo - Tw, xb = xhi + Tw, ya = vy - Tw, yb = vy + Tw;
-        const double x00 = xa * i0, x01 = xa * i1, x10 = xb * i0, x11 = xb * i1;
-        const double y00 = ya * i0, y01 = ya * i1, y10 = yb * i0, y11 = yb * i1;
-        const double qxlo = __builtin_fmin(__builtin_fmin(x00, x01), __builtin_fmin(x10, x11));
-        const double qxhi = __builtin_fmax(__builtin_fmax(x00, x01), __builtin_fmax(x10, x11));
-        const double qylo = __builtin_fmin(__builtin_fmin(y00, y01), __builtin_fmin(y10, y11));
-        const double qyhi = __builtin_fmax(__builtin_fmax(y00, y01), __builtin_fmax(y10, y11));
-        // col = cx + F * (w_x / d), row = cy - F * (w_y / d); outwards by one pixel beyond floor / ceil
-        c0 = clip_lo(__builtin_floor(cx + F * qxlo) - 1.0, left, right);
-        c1 = clip_hi(__builtin_ceil(cx + F * qxhi) + 2.0, left, right);
-        r0 = clip_lo(__builtin_floor(cy - F * qyhi) - 1.0, top, bottom);
-        r1 = clip_hi(__builtin_ceil(cy - F * qylo) + 2.0, top, bottom);
-      }
-    }
+    const SearchRect w = search_rect(xlo - Tw, xhi + Tw, vy - Tw, vy + Tw, -zhi - Tw, -zlo + Tw, epsd, F, cx, cy, left, top,
+                                     right, bottom);
+    const int c0 = w.c0, c1 = w.c1, r0 = w.r0, r1 = w.r1;
 
     // ---- c. the walk ----
     double best[V];
@@ -242,10 +191,7 @@ __global__ __launch_bounds__(kSlabWG) void tsdf_grid_accurate_kernel(AccArgs a) 
       on[j] = nearv ? (int)(uint32_t)(uint64_t)at : -1;
     }
     const int64_t e = ((int64_t)sl * R + y) * R + fv;   // o[c][slow][y][fast]
-    *reinterpret_cast<acc_f4 *>(out + e) = o0;
-    *reinterpret_cast<acc_f4 *>(out + R3 + e) = o1;
-    *reinterpret_cast<acc_f4 *>(out + 2 * R3 + e) = o2;
-    if (nearest) *reinterpret_cast<acc_i4 *>(nearest + e) = on;
+    search_store(out, nearest, R3, e, o0, o1, o2, on);
   }
 }
 
@@ -269,14 +215,7 @@ int tsdf_voxelize_grid_accurate_hip(const float *d_depth, int64_t depth_len, con
   SlabPlan plan;
   if (!slab_args_ok(d_depth, depth_len, d_offsets, d_headers, n_src, d_index, n, R, V, &cam, plan))
     return TSDF_ERR_INVALID_ARG;
-  // slab_plan sizes a workgroup for a kernel that is bound by its stores.  This one is bound by its search, and a small
-  // batch is as long as its slowest workgroup: below kMinBlocks workgroups the slabs are halved (down to one slice).
-  // A voxel's result does not depend on the slab it is in.
-  while (plan.slab > 1 && plan.blocks < kMinBlocks) {
-    plan.slab = (plan.slab + 1) / 2;
-    plan.nslab = (R + plan.slab - 1) / plan.slab;
-    plan.blocks = (int64_t)n * plan.nslab;
-  }
+  search_halve(plan, n, R);   // bound by its search: below kMinBlocks workgroups the slabs are halved
   const int rc = check_device(nullptr);
   if (rc != TSDF_OK) return rc;
   AccArgs a;
@@ -287,12 +226,7 @@ int tsdf_voxelize_grid_accurate_hip(const float *d_depth, int64_t depth_len, con
   a.out = d_out_tsdf;
   a.nearest = d_out_nearest;
   a.status = d_out_status;
-  hipStream_t s = static_cast<hipStream_t>(hip_stream);
-  if (layout == TSDF_LAYOUT_CZYX)
-    hipLaunchKernelGGL(tsdf_grid_accurate_kernel<0>, dim3((unsigned)plan.blocks), dim3(kSlabWG), 0, s, a);
-  else
-    hipLaunchKernelGGL(tsdf_grid_accurate_kernel<1>, dim3((unsigned)plan.blocks), dim3(kSlabWG), 0, s, a);
-  return launched();
+  return search_launch(tsdf_grid_accurate_kernel<0>, tsdf_grid_accurate_kernel<1>, layout, plan, hip_stream, a);
 }
 
 }  // extern "C"

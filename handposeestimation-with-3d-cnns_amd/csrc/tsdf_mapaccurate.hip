@@ -4,14 +4,16 @@
 //
 // A translation unit and a library of its own, next to libtsdf_hip.so and the other extension libraries (all frozen).  It
 // takes the status codes and the layout enum from include/tsdf.h, the host preamble every library here has from
-// device.inc, the device primitives from prim.inc, the slab scaffold from slab.inc and, from mapvox.inc, the per-axis
+// device.inc, the device primitives from prim.inc, the slab scaffold from slab.inc, what the two accurate kernels share
+// beyond it (the search rectangle, the bad-frame tail, the item's store, the host's halving and launch) from search.inc
+// and, from mapvox.inc, the per-axis
 // table and the per-frame constants of the mapped arithmetic (map_fill_tab, map_consts) — the text tsdf_auggrid.hip and
 // tsdf_maplowp.hip run.  The projection and the distance terms are restated here operation for operation as
 // mapvox.inc::map_quad has them, because here the terms are evaluated per CANDIDATE pixel.  No device global: every launch
 // is self-contained.
 //
 // tsdf_map_grid_accurate_kernel: n x ceil(R / slab) workgroups of 256 threads; a workgroup owns `slab` consecutive slices
-// of one batch position — slab.inc's slab, halved while the launch would hold fewer than kMinBlocks workgroups.  It
+// of one batch position — slab.inc's slab, halved while the launch would hold fewer than kMinBlocks workgroups (search.inc).  It
 //   1. resolves its source frame (the index, if any) and checks the frame's header and the POSITION's grid row (all
 //      uniform); a position that is not OK has its slab filled with zeros (nearest: -1) and workgroup 0 of the position
 //      writes the status;
@@ -21,7 +23,7 @@
 //   3. walks its slab in items of 4 consecutive voxels of the fastest axis, one item per lane and pass.  Per item:
 //      a. per voxel the mapped contract's projection (the INVERSE rows), gather and sign (`sv`: 0 rejected, else +-1 by
 //         the projected pixel's u_z), and the voxel's camera-frame centre B (v' - b), B the kernel's own inverse;
-//      b. the SEARCH REGION of the item, a pixel rectangle (below);
+//      b. the SEARCH REGION of the item, a pixel rectangle (below; search.inc::search_rect);
 //      c. one row-major walk of that rectangle.  The c_i depend on the pixel only and their fma(g_i1, dyi, A_i2) on the
 //         row only; u_i differs between the 4 voxels only in its addend, and only along the fastest axis: in layout czyx
 //         the item has ONE t_z and ONE t_y and four t_x, in cxyz one t_x, one t_y and four t_z.  Per valid pixel the z
@@ -32,25 +34,20 @@
 // No work queue, no communication between workgroups, no atomics.  Compiled with -ffp-contract=off, fma only where
 // __builtin_fma is written.
 //
-// WHAT MAY BE DISCARDED BEFORE s IS EVALUATED.  Only candidates whose evaluated s provably exceeds min(1, best so far).  A
-// candidate with s > 1 never decides anything (tsdf_accurate.hip has the sentence).  Two tests use that:
-//   The z term.  s = fma(tz, tz, fma(ty, ty, tx * tx)) with tz = u_z * it.  tsdf_accurate.hip's argument does not look at
-//     how tz came about: for a float64 |tz| > 1, tz^2 >= (1 + 2^-52)^2, the inner fma is the rounding of a non-negative
-//     real, rounding is monotone, so the evaluated s exceeds 1.  Skipping on !(|tz| <= 1) skips exactly candidates whose
-//     EVALUATED s exceeds 1 or is a NaN.  No margin.
-//   The rectangle.  Over the reals u = (v' - b) - A w for the point w of a pixel.  Let B be ANY 3x3 (the kernel's computed
-//     inverse, exact as the float64 numbers it holds), Res = B A - I, c = B (v' - b).  Then B u = c - w - Res w, so
+// THE SEARCH REGION.  search.inc has the argument for what may be discarded before s is evaluated (the z term — here
+// tz = u_z * it, and the argument does not look at how tz came about — and the corner-quotient rectangle) and the
+// rectangle itself; what is this file's is why its six arguments bound, in the CAMERA frame, a point w whose mapped image
+// is within T of the voxel.  Over the reals u = (v' - b) - A w for the point w of a pixel.  Let B be ANY 3x3 (the kernel's
+// computed inverse, exact as the float64 numbers it holds), Res = B A - I, c = B (v' - b).  Then B u = c - w - Res w, so
 //         |w_a - c_a| <= ||row a of B||_2 |u|_2 + rho |w|_2,   rho = ||Res||_F,
 //     and from |w| <= |c| + |w - c| and |w - c| <= ||B||_F |u| + rho |w|:  for rho <= 1/4 and |u| <= T
 //         |w_a - c_a| <= T h_a + 2 rho (|c|_1 + ||B||_F T),     h_a = ||row a of B||_2.
 //     That bounds each CAMERA coordinate of a point within T of the voxel by the half-extent H_a around c_a, whatever B
-//     is — a poor inverse only has a large rho.  The plain kernel's corner-quotient rectangle follows with c as the
-//     centre: depth d = -w_z in [-c_z - H_z, -c_z + H_z], col = cx + F w_x / d and row = cy - F w_y / d monotone in each
-//     argument while d keeps one sign, extremes at the four corners, union over the item's 4 voxels, rounded outwards by
-//     floor - 1 / ceil + 1, clipped to the crop.  The kernel uses T' = T (1 + 2^-20) for T and rho' = rho + 2^-30 for rho:
-//     a pixel outside has a real |u| > T', a real s > 1 + 2^-19, and with the evaluation error of the sequence (2^-40 for
-//     s <= 2 under the magnitudes below) an evaluated s > 1; 2^-30 covers the float64 roundings of Res, h_a (a square
-//     root of three products) and c (relative 2^-50 ||B|| ||A|| each) under the conditions below.
+//     is — a poor inverse only has a large rho.  So w_x is in [c_x - H_x, c_x + H_x], w_y likewise and the depth d = -w_z
+//     in [-c_z - H_z, -c_z + H_z]; over the item's 4 voxels the ranges of c are united (clo, chi).  The kernel uses
+//     T' = T (1 + 2^-20) for T and rho' = rho + 2^-30 for rho: a pixel outside has a real |u| > T'; 2^-30 covers the
+//     float64 roundings of Res, h_a (a square root of three products) and c (relative 2^-50 ||B|| ||A|| each) under the
+//     conditions below, and under their magnitudes the sequence's evaluation error is the 2^-40 search.inc counts on.
 //     The rectangle is used only where the inverse can be TRUSTED: ||A||_F and ||B||_F both <= 2^20, ||A||_F ||B||_F <=
 //     2^16 and rho <= 2^-24, each written so that a NaN fails (a zero or non-finite determinant gives a non-finite B or a
 //     rho of sqrt 3).  Otherwise, and where the depth interval does not stay on one side of zero by invalid_eps, there is
@@ -77,13 +74,8 @@ namespace {
 #include "device.inc"   // check_device, launched, misaligned: the host preamble of every library here
 #include "prim.inc"     // cam_ok, trunc_i32, finite32, header_ok
 #include "slab.inc"     // workgroup <-> slab, the frame's header and grid row, zero-fill, host sizing
+#include "search.inc"   // the item, the search rectangle, the bad-frame tail, the item's store, the host's halving and launch
 #include "mapvox.inc"   // map_fill_tab, MapK, map_consts: the mapped arithmetic's table and constants
-
-typedef float acc_f4 __attribute__((ext_vector_type(4)));
-typedef int acc_i4 __attribute__((ext_vector_type(4)));
-
-constexpr int V = 4;   // voxels per lane and item: one 16-byte store per channel
-constexpr int64_t kMinBlocks = 1024;   // workgroups a launch aims for at least: four per CU of an MI355X
 
 struct MapAccArgs {
   SlabSrc src;
@@ -94,16 +86,6 @@ struct MapAccArgs {
   int32_t *nearest;         // [n][R][R][R] or null
   int32_t *status;          // [n] or null
 };
-
-// lower clip of a window bound: max(lo, min(hi, b)) as an int; a NaN gives lo (the whole side)
-__device__ __forceinline__ int clip_lo(double b, int lo, int hi) {
-  return !(b > (double)lo) ? lo : (b < (double)hi ? trunc_i32(b) : hi);
-}
-
-// upper clip: min(hi, max(lo, b)); a NaN gives hi
-__device__ __forceinline__ int clip_hi(double b, int lo, int hi) {
-  return !(b < (double)hi) ? hi : (b > (double)lo ? trunc_i32(b) : lo);
-}
 
 // A float64 every lane holds the same value of (computed from uniform inputs by the same operations), moved into scalar
 // registers: v_fma_f64 and its kin take one scalar operand, and the per-frame constants then cost no vector registers.
@@ -163,14 +145,7 @@ __global__ __launch_bounds__(kSlabWG) void tsdf_map_grid_accurate_kernel(MapAccA
 
   const SlabFrame fr = slab_head<false>(a.src, blk, a.grid);   // the grid row is the POSITION's
   const int64_t per = (int64_t)(se - sb) * R * RV;   // 16-byte pieces of the slab, per channel
-  if (slab_bad_frame<acc_f4>(fr, blk, a.status, out, R, per, tid)) {
-    if (nearest) {
-      const acc_i4 none = {-1, -1, -1, -1};
-      acc_i4 *p = reinterpret_cast<acc_i4 *>(nearest + (int64_t)sb * R * R);
-      for (int64_t q = tid; q < per; q += kSlabWG) p[q] = none;
-    }
-    return;
-  }
+  if (search_bad_frame(fr, blk, a.status, out, nearest, R, per, tid)) return;
 
   const double *__restrict__ xf = a.xforms + 24 * blk.i;
   map_fill_tab(s_tab, xf, fr.ox, fr.oy, fr.oz, fr.vl, R, tid);
@@ -183,7 +158,7 @@ __global__ __launch_bounds__(kSlabWG) void tsdf_map_grid_accurate_kernel(MapAccA
   const int64_t bw = k.bw;
   const float eps = k.eps;
   const double epsd = (double)eps;
-  const double Tw = uniform64((double)fr.td * (1.0 + 0x1p-20));   // the window's truncation distance (see the head of this file)
+  const double Tw = uniform64((double)fr.td * (1.0 + 0x1p-20));   // the window's truncation distance T' (search.inc)
   const float *__restrict__ d = a.src.depth + fr.off0;
   __syncthreads();
   double B[9], hB[3];                                  // the window's constants, out of LDS once
@@ -238,7 +213,7 @@ __global__ __launch_bounds__(kSlabWG) void tsdf_map_grid_accurate_kernel(MapAccA
     }
 
     // ---- b. the item's search rectangle [c0, c1) x [r0, r1), image coordinates ----
-    int c0 = left, c1 = right, r0 = top, r1 = bottom;
+    SearchRect w = {left, right, top, bottom};               // an inverse that is not trusted: the whole crop
     if (windowed) {
       double c1n = 0.0;                                        // the largest |c|_1 of the four
 #pragma unroll
@@ -246,23 +221,10 @@ __global__ __launch_bounds__(kSlabWG) void tsdf_map_grid_accurate_kernel(MapAccA
       const double slack = __builtin_fma(rho2, c1n, slack0);   // 2 rho' (|c|_1 + ||B||_F T')
       const double Hx = __builtin_fma(Tw, hB[0], slack), Hy = __builtin_fma(Tw, hB[1], slack),
                    Hz = __builtin_fma(Tw, hB[2], slack);
-      const double dlo = -chi[2] - Hz, dhi = -clo[2] + Hz;     // depths of points within T' of the item
-      if (dlo >= epsd || dhi <= -epsd) {                       // one sign, away from zero: a finite rectangle
-        const double i0 = 1.0 / dlo, i1 = 1.0 / dhi;
-        const double xa = clo[0] - Hx, xb = chi[0] + Hx, ya = clo[1] - Hy, yb = chi[1] + Hy;
-        const double x00 = xa * i0, x01 = xa * i1, x10 = xb * i0, x11 = xb * i1;
-        const double y00 = ya * i0, y01 = ya * i1, y10 = yb * i0, y11 = yb * i1;
-        const double qxlo = __builtin_fmin(__builtin_fmin(x00, x01), __builtin_fmin(x10, x11));
-        const double qxhi = __builtin_fmax(__builtin_fmax(x00, x01), __builtin_fmax(x10, x11));
-        const double qylo = __builtin_fmin(__builtin_fmin(y00, y01), __builtin_fmin(y10, y11));
-        const double qyhi = __builtin_fmax(__builtin_fmax(y00, y01), __builtin_fmax(y10, y11));
-        // col = cx + F * (w_x / d), row = cy - F * (w_y / d); outwards by one pixel beyond floor / ceil
-        c0 = clip_lo(__builtin_floor(k.cx + k.F * qxlo) - 1.0, left, right);
-        c1 = clip_hi(__builtin_ceil(k.cx + k.F * qxhi) + 2.0, left, right);
-        r0 = clip_lo(__builtin_floor(k.cy - k.F * qyhi) - 1.0, top, bottom);
-        r1 = clip_hi(__builtin_ceil(k.cy - k.F * qylo) + 2.0, top, bottom);
-      }
+      w = search_rect(clo[0] - Hx, chi[0] + Hx, clo[1] - Hy, chi[1] + Hy, -chi[2] - Hz, -clo[2] + Hz, epsd, k.F, k.cx, k.cy,
+                      left, top, right, bottom);
     }
+    const int c0 = w.c0, c1 = w.c1, r0 = w.r0, r1 = w.r1;
 
     // ---- c. the walk ----
     double best[V];
@@ -343,10 +305,7 @@ __global__ __launch_bounds__(kSlabWG) void tsdf_map_grid_accurate_kernel(MapAccA
       on[j] = nearv ? (int)(uint32_t)(uint64_t)at : -1;
     }
     const int64_t e = ((int64_t)sl * R + y) * R + fv;   // o[c][slow][y][fast]
-    *reinterpret_cast<acc_f4 *>(out + e) = o0;
-    *reinterpret_cast<acc_f4 *>(out + R3 + e) = o1;
-    *reinterpret_cast<acc_f4 *>(out + 2 * R3 + e) = o2;
-    if (nearest) *reinterpret_cast<acc_i4 *>(nearest + e) = on;
+    search_store(out, nearest, R3, e, o0, o1, o2, on);
   }
 }
 
@@ -372,13 +331,7 @@ int tsdf_voxelize_map_grid_accurate_hip(const float *d_depth, int64_t depth_len,
   SlabPlan plan;
   if (!slab_args_ok(d_depth, depth_len, d_offsets, d_headers, n_src, d_index, n, R, V, &cam, plan))
     return TSDF_ERR_INVALID_ARG;
-  // as tsdf_accurate.hip: the kernel is bound by its search and a small batch is as long as its slowest workgroup, so
-  // below kMinBlocks workgroups the slabs are halved (down to one slice).  A voxel's result does not depend on its slab.
-  while (plan.slab > 1 && plan.blocks < kMinBlocks) {
-    plan.slab = (plan.slab + 1) / 2;
-    plan.nslab = (R + plan.slab - 1) / plan.slab;
-    plan.blocks = (int64_t)n * plan.nslab;
-  }
+  search_halve(plan, n, R);   // bound by its search: below kMinBlocks workgroups the slabs are halved
   const int rc = check_device(nullptr);
   if (rc != TSDF_OK) return rc;
   MapAccArgs a;
@@ -389,12 +342,7 @@ int tsdf_voxelize_map_grid_accurate_hip(const float *d_depth, int64_t depth_len,
   a.out = d_out_tsdf;
   a.nearest = d_out_nearest;
   a.status = d_out_status;
-  hipStream_t s = static_cast<hipStream_t>(hip_stream);
-  if (layout == TSDF_LAYOUT_CZYX)
-    hipLaunchKernelGGL(tsdf_map_grid_accurate_kernel<0>, dim3((unsigned)plan.blocks), dim3(kSlabWG), 0, s, a);
-  else
-    hipLaunchKernelGGL(tsdf_map_grid_accurate_kernel<1>, dim3((unsigned)plan.blocks), dim3(kSlabWG), 0, s, a);
-  return launched();
+  return search_launch(tsdf_map_grid_accurate_kernel<0>, tsdf_map_grid_accurate_kernel<1>, layout, plan, hip_stream, a);
 }
 
 }  // extern "C"

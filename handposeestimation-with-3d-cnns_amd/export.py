@@ -88,7 +88,7 @@ def _voxelize_pack(pk: packing.PackedFrames, res: int, layout: str, device, *, c
                            voxelize_aug)
 
     if (xforms is None) != (gt is None) or (tsdf == "accurate" and xforms is not None):
-        raise ValueError('xforms and gt come together, and not with tsdf="accurate": that pass is not there yet')
+        raise ValueError('xforms and gt come together, and not with tsdf="accurate": that pass is not reached from here')
     depth, offsets, headers = pk.to_torch(device, pin=True, non_blocking=True)
 
     def up(a, dtype):

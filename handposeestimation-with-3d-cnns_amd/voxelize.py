@@ -1276,6 +1276,16 @@ def _first_status(*stages: torch.Tensor) -> torch.Tensor:
     return status
 
 
+_TSDF_KINDS = ("projective", "accurate")
+
+
+def _tsdf_kind(tsdf) -> bool:
+    """``tsdf=`` of a composed entry: True for the accurate volume; anything but the two names is a ValueError."""
+    if tsdf not in _TSDF_KINDS:
+        raise ValueError("tsdf must be 'projective' or 'accurate'")
+    return tsdf == "accurate"
+
+
 def _grid_pass(depth, offsets, headers, grid, *, res, layout, cam, xforms=None, dtype=None, tsdf="projective", index=None,
                out=None):
     """The voxel pass on the rows ``grid`` that (``xforms``, ``dtype``, ``tsdf``) name, ``(volume, status)`` — the one table
@@ -1288,13 +1298,13 @@ def _grid_pass(depth, offsets, headers, grid, *, res, layout, cam, xforms=None, 
     entries have neither and refuse them.  Every refusal comes before the first launch."""
     if dtype is not None:
         _lowp_dtype(dtype)
-    if tsdf not in ("projective", "accurate"):
-        raise ValueError("tsdf must be 'projective' or 'accurate'")
+    accurate = _tsdf_kind(tsdf)
     pack = (depth, offsets, headers) if xforms is None else (depth, offsets, headers, xforms)
     kw = dict(res=res, layout=layout, cam=cam)
-    if tsdf == "accurate":
+    if accurate:
         if xforms is not None:
-            raise ValueError("tsdf='accurate' takes no xforms: the accurate pass under a per-frame map is not there yet")
+            raise ValueError("tsdf='accurate' takes no xforms: the accurate pass under a per-frame map is "
+                             "voxelize_map_grid_accurate, not reached through this table")
         vol, status = voxelize_grid_accurate(*pack, grid, index=index, out=out if dtype is None else None, **kw)
         return (vol if dtype is None else narrow_volumes(vol, dtype=dtype, out=out)), status
     if dtype is not None:
@@ -1396,6 +1406,19 @@ def _batch_labels(gt, index, n_src, xforms, max_l, mid_p, clamp, sel=None, out_a
     return normalize_joints(gt_aug, max_l, mid_p, clamp=clamp, out=out_nor), gt_aug
 
 
+def _aug_placed(depth, offsets, headers, xforms, res, cam, gt, clamp, index, volume):
+    """What :func:`voxelize_aug_lowp` and :func:`voxelize_aug_accurate` are around their pass: :func:`map_grids` places the
+    grid under the maps, ``volume(rows)`` is the pass on the placement's rows, the batch has the PLACEMENT's ``max_l`` /
+    ``mid_p`` / ``status``, and with ``gt`` the labels follow (:func:`_batch_labels`): ``(TsdfBatch, gt_nor, gt_aug)``."""
+    mg = map_grids(depth, offsets, headers, xforms, res=res, cam=cam, index=index)
+    batch = TsdfBatch(volume(mg.grid), mg.max_l, mg.mid_p, mg.status)
+    if gt is None:
+        return batch
+    _dev_check("gt", gt, torch.float32, depth.device)
+    gt_nor, gt_aug = _batch_labels(gt, index, headers.shape[0], xforms, mg.max_l, mg.mid_p, clamp)
+    return batch, gt_nor, gt_aug
+
+
 def voxelize_aug_lowp(depth: torch.Tensor, offsets: torch.Tensor, headers: torch.Tensor, xforms: torch.Tensor,
                       res: int = 32, layout: str = "czyx", dtype: torch.dtype = torch.bfloat16,
                       cam: Optional[_lib.TsdfCam] = None, gt: Optional[torch.Tensor] = None, clamp: bool = True,
@@ -1411,24 +1434,8 @@ def voxelize_aug_lowp(depth: torch.Tensor, offsets: torch.Tensor, headers: torch
             ``gt_aug = transform_joints(gt of the batch, xforms)`` and ``gt_nor = normalize_joints(gt_aug, max_l, mid_p)``
             (two more small launches), the values the fused entry writes."""
     _lowp_dtype(dtype)
-    mg = map_grids(depth, offsets, headers, xforms, res=res, cam=cam, index=index)
-    tsdf, _ = _map_grid_lowp(depth, offsets, headers, xforms, mg.grid, res, layout, dtype, cam, index, None, False)
-    batch = TsdfBatch(tsdf, mg.max_l, mg.mid_p, mg.status)
-    if gt is None:
-        return batch
-    _dev_check("gt", gt, torch.float32, depth.device)
-    gt_nor, gt_aug = _batch_labels(gt, index, headers.shape[0], xforms, mg.max_l, mg.mid_p, clamp)
-    return batch, gt_nor, gt_aug
-
-
-_TSDF_KINDS = ("projective", "accurate")
-
-
-def _tsdf_kind(tsdf) -> bool:
-    """``tsdf=`` of a composed entry: True for the accurate volume; anything but the two names is a ValueError."""
-    if tsdf not in _TSDF_KINDS:
-        raise ValueError("tsdf must be 'projective' or 'accurate'")
-    return tsdf == "accurate"
+    return _aug_placed(depth, offsets, headers, xforms, res, cam, gt, clamp, index, lambda rows: _map_grid_lowp(
+        depth, offsets, headers, xforms, rows, res, layout, dtype, cam, index, None, False)[0])
 
 
 def _map_grid_accurate(depth, offsets, headers, xforms, grid, res, layout, cam, index, out, want_status, nearest=False):
@@ -1492,16 +1499,11 @@ def voxelize_aug_accurate(depth: torch.Tensor, offsets: torch.Tensor, headers: t
             :func:`voxelize_aug_lowp` does, the values the fused projective entry writes."""
     if dtype is not None:
         _lowp_dtype(dtype)
-    mg = map_grids(depth, offsets, headers, xforms, res=res, cam=cam, index=index)
-    tsdf, _, _ = _map_grid_accurate(depth, offsets, headers, xforms, mg.grid, res, layout, cam, index, None, False)
-    if dtype is not None:
-        tsdf = narrow_volumes(tsdf, dtype=dtype)
-    batch = TsdfBatch(tsdf, mg.max_l, mg.mid_p, mg.status)
-    if gt is None:
-        return batch
-    _dev_check("gt", gt, torch.float32, depth.device)
-    gt_nor, gt_aug = _batch_labels(gt, index, headers.shape[0], xforms, mg.max_l, mg.mid_p, clamp)
-    return batch, gt_nor, gt_aug
+
+    def volume(rows):
+        tsdf = _map_grid_accurate(depth, offsets, headers, xforms, rows, res, layout, cam, index, None, False)[0]
+        return tsdf if dtype is None else narrow_volumes(tsdf, dtype=dtype)
+    return _aug_placed(depth, offsets, headers, xforms, res, cam, gt, clamp, index, volume)
 
 
 def compose_xforms(outer: torch.Tensor, inner: torch.Tensor, index: Optional[torch.Tensor] = None,
@@ -1717,8 +1719,7 @@ def voxelize_frames(frames: torch.Tensor, res: int = 32, *, placement: str = "aa
         raise ValueError("layout must be 'czyx' or 'cxyz'")
     if dtype is not None:
         _lowp_dtype(dtype)
-    if tsdf not in ("projective", "accurate"):
-        raise ValueError("tsdf must be 'projective' or 'accurate'")
+    _tsdf_kind(tsdf)
     if "grid" in locate or "res" in locate:
         raise TypeError("voxelize_frames sets locate_hands' grid and res itself")
     cam = locate.get("cam")

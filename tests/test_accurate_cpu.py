@@ -5,6 +5,7 @@ the GPU tier compares against (tests/accurate_ref.py) on the very inputs that ti
 import ctypes
 import importlib
 import os
+import re
 import subprocess
 import sys
 
@@ -49,6 +50,37 @@ def test_make_rules_cross_compile_for_gfx950_without_scratch():
     assert sum("tsdf_grid_accurate_kernel" in ln for ln in report.splitlines() if "Function Name" in ln) == 2
     committed = _scratch_lines(report)
     assert len(committed) == 2 and all(ln.split("]:")[1].split()[0] == "0" for ln in committed), committed
+
+
+def test_the_build_inputs_are_exact():
+    lines = open(os.path.join(CSRC, "Makefile")).read().splitlines()
+    deps, = [ln for ln in lines if re.match(r"^accurate_DEPS := ", ln)]
+    assert deps.split(":=")[1].split() == ["prim.inc", "slab.inc", "search.inc"]
+    src = open(os.path.join(CSRC, "tsdf_accurate.hip")).read()
+    assert sorted(re.findall(r'#include "(\w+\.inc)"', src)) == sorted(["device.inc", "prim.inc", "slab.inc", "search.inc"])
+
+
+def test_the_accurate_kernels_share_one_search_scaffold():
+    read = lambda name: open(os.path.join(CSRC, name), errors="replace").read()   # noqa: E731
+    inc, plain, mapped = read("search.inc"), read("tsdf_accurate.hip"), read("tsdf_mapaccurate.hip")
+    defined = {"clip_lo": r"\bint clip_lo\(", "clip_hi": r"\bint clip_hi\(", "search_rect": r"\bSearchRect search_rect\(",
+               "kMinBlocks": r"\bconstexpr int64_t kMinBlocks\b"}
+    for name, pattern in defined.items():
+        assert len(re.findall(pattern, inc)) == 1, name
+        for text in (plain, mapped):
+            assert not re.search(pattern, text), name
+            assert not re.search(rf"\b(int|SearchRect|constexpr \w+) {name}\b", text), name   # nor defined in another form
+    # both call the one rectangle, and neither restates its arithmetic (the reciprocals of the depth interval's ends)
+    for text in (plain, mapped):
+        assert len(re.findall(r"\bsearch_rect\(", text)) == 1 and "1.0 / dlo" not in text and "clip_lo(" not in text
+    assert "1.0 / dlo" in inc
+    # nothing else under csrc/ includes it
+    users = sorted(f for f in os.listdir(CSRC) if f != "search.inc" and os.path.isfile(os.path.join(CSRC, f))
+                   and re.search(r'#include\s+"search\.inc"', read(f)))
+    assert users == ["tsdf_accurate.hip", "tsdf_mapaccurate.hip"]
+    for text in (plain, mapped):                                     # after slab.inc, inside the anonymous namespace
+        assert text.index("namespace {") < text.index('#include "slab.inc"') < text.index('#include "search.inc"') \
+            < text.index("}  // namespace")
 
 
 # ---- binding ----

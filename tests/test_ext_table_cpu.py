@@ -13,7 +13,7 @@ from abi_util import declared_functions, exported
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 # csrc/Makefile's EXTS, in its order: a new library is a name here, a name there and a row in _lib._EXTS
-EXTS = ["augment", "augstep", "auggrid", "depth16", "obb", "lowp", "maplowp", "mapstep", "locate", "accurate"]
+EXTS = ["augment", "augstep", "auggrid", "depth16", "obb", "lowp", "maplowp", "mapstep", "locate", "accurate", "mapaccurate"]
 
 
 def test_the_table_has_a_row_and_a_loader_per_extension(pkg):

@@ -19,9 +19,10 @@ Method: inputs resident on the device, a warm-up, then device events around back
 them, fewer where one launch is long (about --budget seconds per timed window, at least 5) —; the legs of a shape take
 turns for --rounds rounds and the median round is reported with min and max.  Every shape and the tree leg run in a child
 process of their own under their own time limit (--limit seconds), one after the other, and the first that fails ends the
-run: nothing more is started on the device after it.
+run: nothing more is started on the device after it.  ``--lib`` names another build of libtsdf_accurate.so (an A/B against
+the parent commit's: one process per build, taking turns).
 
-    python tools/bench_accurate.py [--iters 100] [--rounds 5] [--limit 420] [--out x.json]
+    python tools/bench_accurate.py [--iters 100] [--rounds 5] [--limit 420] [--lib x.so] [--out x.json]
 """
 from __future__ import annotations
 
@@ -60,11 +61,18 @@ def torch_accurate(torch, pts, rows, R):
     return out
 
 
+def _package(a):
+    sys.path.insert(0, ROOT)
+    pkg = importlib.import_module("handposeestimation-with-3d-cnns_amd")
+    if a.lib:
+        pkg._lib._EXTS["accurate"] = pkg._lib._EXTS["accurate"]._replace(path=os.path.abspath(a.lib))
+    return pkg
+
+
 def one_shape(n, R, a):
     import numpy as np
     import torch
-    sys.path.insert(0, ROOT)
-    pkg = importlib.import_module("handposeestimation-with-3d-cnns_amd")
+    pkg = _package(a)
     synth = importlib.import_module("handposeestimation-with-3d-cnns_amd.synth")
     sys.path.insert(0, os.path.join(ROOT, "tools"))
     from _timing import timed_us
@@ -124,8 +132,7 @@ def one_shape(n, R, a):
 def tree(a):
     import numpy as np
     import torch
-    sys.path.insert(0, ROOT)
-    pkg = importlib.import_module("handposeestimation-with-3d-cnns_amd")
+    pkg = _package(a)
     synth = importlib.import_module("handposeestimation-with-3d-cnns_amd.synth")
     assert torch.cuda.is_available(), "bench_accurate.py needs a HIP device"
     with tempfile.TemporaryDirectory() as tmp:
@@ -154,6 +161,7 @@ def main():
     ap.add_argument("--limit", type=int, default=420, help="seconds per child process")
     ap.add_argument("--one", nargs=2, type=int, metavar=("N", "R"))
     ap.add_argument("--tree", action="store_true")
+    ap.add_argument("--lib")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "accurate", "bench_accurate.json"))
     a = ap.parse_args()
     if a.one:
@@ -161,6 +169,7 @@ def main():
     if a.tree:
         return tree(a)
     common = ["--iters", str(a.iters), "--rounds", str(a.rounds), "--budget", str(a.budget), "--torch-frames", str(a.torch_frames)]
+    common += ["--lib", a.lib] if a.lib else []
     steps = [["--one", str(n), str(R)] for n, R in SHAPES] + [["--tree"]]
     rows, tree_row = [], None
     for step in steps:                                       # one child per step, each under its own limit; stop at the first failure

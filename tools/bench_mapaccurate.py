@@ -18,9 +18,10 @@ Method: inputs resident on the device, a warm-up, then device events around back
 them, fewer where one launch is long (about --budget seconds per timed window, at least 5) —; the legs of a shape take
 turns for --rounds rounds and the median round is reported with min and max.  Every shape runs in a child process of its
 own under its own time limit (--limit seconds), one after the other, and the first that fails ends the run: nothing more
-is started on the device after it.
+is started on the device after it.  ``--lib`` names another build of libtsdf_mapaccurate.so and ``--accurate-lib`` one of
+libtsdf_accurate.so (the `plain` leg's): an A/B against the parent commit's, one process per build, taking turns.
 
-    python tools/bench_mapaccurate.py [--iters 100] [--rounds 5] [--limit 420] [--out x.json]
+    python tools/bench_mapaccurate.py [--iters 100] [--rounds 5] [--limit 420] [--lib x.so] [--accurate-lib y.so] [--out x.json]
 """
 from __future__ import annotations
 
@@ -61,11 +62,14 @@ def _measure(legs, a):
             for k, v in times.items()}
 
 
-def _inputs(n, R):
+def _inputs(n, R, a):
     import numpy as np
     import torch
     sys.path.insert(0, ROOT)
     pkg = importlib.import_module(PKG)
+    for name, path in (("mapaccurate", a.lib), ("accurate", a.accurate_lib)):
+        if path:
+            pkg._lib._EXTS[name] = pkg._lib._EXTS[name]._replace(path=os.path.abspath(path))
     synth = importlib.import_module(PKG + ".synth")
     assert torch.cuda.is_available(), "bench_mapaccurate.py needs a HIP device"
     dev = torch.device("cuda:0")
@@ -75,7 +79,7 @@ def _inputs(n, R):
 
 
 def one_shape(n, R, a):
-    pkg, torch, dev, depth, (td, to, th) = _inputs(n, R)
+    pkg, torch, dev, depth, (td, to, th) = _inputs(n, R, a)
     ab = pkg.aabb(td, to, th, res=R)
     assert not ab.status.any()
     rows = torch.cat([ab.ori, ab.grid[:, 4:6], torch.zeros_like(ab.ori)], dim=1)
@@ -113,7 +117,7 @@ def one_shape(n, R, a):
 
 def one_step(n, a):
     R = 32
-    pkg, torch, dev, depth, (td, to, th) = _inputs(n, R)
+    pkg, torch, dev, depth, (td, to, th) = _inputs(n, R, a)
     centres = pkg.aabb(td, to, th, res=R).grid[:, :3].contiguous()
     index = torch.arange(n, dtype=torch.int64, device=dev)
     steps = {f"step_{kind}{'_bf16' if dt is not None else ''}":
@@ -190,6 +194,8 @@ def main():
     ap.add_argument("--limit", type=int, default=420, help="seconds per child process")
     ap.add_argument("--one", nargs=2, type=int, metavar=("N", "R"))
     ap.add_argument("--step", type=int, metavar="N")
+    ap.add_argument("--lib")
+    ap.add_argument("--accurate-lib")
     ap.add_argument("--windows", type=int, metavar="FRAMES", help="CPU only: mean search-window sizes, no device")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "mapaccurate", "bench_mapaccurate.json"))
     a = ap.parse_args()
@@ -200,6 +206,7 @@ def main():
     if a.windows:
         return windows(a)
     common = ["--iters", str(a.iters), "--rounds", str(a.rounds), "--budget", str(a.budget)]
+    common += [x for flag, path in (("--lib", a.lib), ("--accurate-lib", a.accurate_lib)) if path for x in (flag, path)]
     todo = [["--one", str(n), str(R)] for n, R in SHAPES] + [["--step", str(n)] for n in STEP_BATCHES]
     rows, steps = [], []
     for step in todo:                                        # one child per step, each under its own limit; stop at the first failure
