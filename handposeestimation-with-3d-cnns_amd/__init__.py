@@ -43,6 +43,9 @@ The accurate directional TSDF:           voxelize_grid_accurate (per voxel the n
 ... under a per-frame map:               voxelize_map_grid_accurate (the same search on the augmented pass's arithmetic:
                                          libtsdf_mapaccurate.so, include/tsdf_mapaccurate.h), voxelize_aug_accurate,
                                          voxelize_obb(tsdf="accurate"), AugmentedStep(tsdf="accurate")
+Voxel heatmap labels:                    joint_heatmaps (one Gaussian volume per joint from gt_nor, aligned with the TSDF
+                                         volume: libtsdf_heatmap.so, include/tsdf_heatmap.h), heatmap_joints (per joint the
+                                         peak of a volume back as normalised coordinates), AugmentedStep(heatmap=...)
 """
 from . import _lib  # noqa: F401
 from ._lib import TsdfCam, TsdfError, default_cam  # noqa: F401
@@ -55,7 +58,7 @@ from .voxelize import (AabbBatch, AugmentedStep, CloudGridBatch, MapGridBatch, O
                        invert_xforms, obb_xforms, voxelize_obb, narrow_volumes, voxelize_grid_lowp, voxelize_lowp,
                        map_grids, voxelize_aug_lowp, voxelize_map_grid_lowp, MapStepBatch, compose_xforms, map_step_head,
                        HandCrops, locate_hands, voxelize_frames, voxelize_accurate, voxelize_grid_accurate,
-                       voxelize_aug_accurate, voxelize_map_grid_accurate)
+                       voxelize_aug_accurate, voxelize_map_grid_accurate, HeatmapJoints, heatmap_joints, joint_heatmaps)
 from .pca import JointPCA, fit_joint_pca  # noqa: F401
 from . import augment, dataset, export, packing, pca, shard, synth  # noqa: F401
 from .dataset import MSRA_Dataset, MSRADepthDataset, ResidentLoader, VoxelBatch, VoxelLoader  # noqa: F401
@@ -72,4 +75,5 @@ __all__ = ["voxelize", "voxelize_labels", "voxelize_indexed", "ResidentLoader", 
            "ProcessAugBatch", "widen_depth16", "obb_xforms", "voxelize_obb", "invert_xforms", "ObbBatch",
            "voxelize_grid_lowp", "voxelize_lowp", "narrow_volumes", "map_grids", "MapGridBatch", "voxelize_map_grid_lowp",
            "voxelize_aug_lowp", "compose_xforms", "map_step_head", "MapStepBatch", "locate_hands", "voxelize_frames",
-           "HandCrops", "voxelize_grid_accurate", "voxelize_accurate", "voxelize_map_grid_accurate", "voxelize_aug_accurate"]
+           "HandCrops", "voxelize_grid_accurate", "voxelize_accurate", "voxelize_map_grid_accurate", "voxelize_aug_accurate",
+           "joint_heatmaps", "heatmap_joints", "HeatmapJoints"]

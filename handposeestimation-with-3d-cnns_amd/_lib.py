@@ -146,6 +146,13 @@ ACCURATE_VERSION = 1
 MAPACCURATE_LIB_PATH = os.path.join(_HERE, "libtsdf_mapaccurate.so")
 MAPACCURATE_VERSION = 1
 
+# The library of include/tsdf_heatmap.h (make -C csrc heatmap): per-joint Gaussian heatmap volumes from normalised labels,
+# and per joint the peak of a volume back as normalised coordinates.  A binary of its own; its row is _HEATMAP below, not
+# yet a row of _EXTS (tests/test_ext_table_cpu.py pins that table name by name).
+HEATMAP_LIB_PATH = os.path.join(_HERE, "libtsdf_heatmap.so")
+HEATMAP_VERSION = 1
+TSDF_HEATMAP_F32 = 0   # the float32 element type of include/tsdf_heatmap.h; the 2-byte ones are TSDF_LOWP_*
+
 
 class _Ext(NamedTuple):
     """A row of the extension table: libtsdf_<name>.so, built by ``make -C csrc <name>`` from include/tsdf_<name>.h."""
@@ -234,6 +241,14 @@ _EXTS = {
                                                 _vp],
     }),
 }
+
+# libtsdf_heatmap.so's row, of the same type and loaded by the same code (load_heatmap)
+_HEATMAP = _Ext(HEATMAP_LIB_PATH, "tsdf_heatmap_version", HEATMAP_VERSION, {
+    # u, status, n, n_joints, R, sigma, layout, dtype, stream, heat, valid
+    "tsdf_joint_heatmaps_hip": [_vp, _vp, _i, _i, _i, ctypes.c_float, _i, _i, _vp, _vp, _vp],
+    # heat, dtype, n, n_joints, R, layout, radius, stream, u, peak, arg
+    "tsdf_heatmap_joints_hip": [_vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp],
+})
 
 _lib = None
 _debug_lib = None
@@ -326,13 +341,12 @@ def load_debug():
     return L
 
 
-def _load_ext(name: str):
-    """Load libtsdf_<name>.so, a row of the table, once: the file must exist, its entry points are declared, its version
-    must be the row's, and the library is kept in ``_ext_libs`` under ``name``; raise loudly if it is not there."""
+def _load_row(name: str, ext: _Ext):
+    """Load libtsdf_<name>.so as its row ``ext`` describes it, once: the file must exist, its entry points are declared,
+    its version must be the row's, and the library is kept in ``_ext_libs`` under ``name``; raise loudly if it is not there."""
     L = _ext_libs.get(name)
     if L is not None:
         return L
-    ext = _EXTS[name]
     if not os.path.exists(ext.path):
         raise ImportError(f"{ext.path} not found: build it with `make -C handposeestimation-with-3d-cnns_amd/csrc "
                           f"{name}` (__graft_entry__.build() does). There is no CPU fallback.")
@@ -340,9 +354,20 @@ def _load_ext(name: str):
     _declare(L, {ext.version_symbol: [], **ext.entries})
     have = getattr(L, ext.version_symbol)()
     if have != ext.version:
-        raise ImportError(f"{ext.path} has version {have}, this package needs {ext.version}: rebuild it")
+        raise ImportError(f"{ext.path} has version {have}, this package needs {ext.version}: rebuild it "
+                          f"(`make -C handposeestimation-with-3d-cnns_amd/csrc {name}`)")
     _ext_libs[name] = L
     return L
+
+
+def _load_ext(name: str):
+    """Load libtsdf_<name>.so, a row of the table, once (:func:`_load_row`)."""
+    return _load_row(name, _EXTS[name])
+
+
+def load_heatmap():
+    """libtsdf_heatmap.so, the library of include/tsdf_heatmap.h (its row is ``_HEATMAP``)."""
+    return _load_row("heatmap", _HEATMAP)
 
 
 def load_augment():

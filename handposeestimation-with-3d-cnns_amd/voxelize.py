@@ -9,6 +9,7 @@ torch is used for device memory and the stream handle only.
 from __future__ import annotations
 
 import ctypes
+import math
 from typing import NamedTuple, Optional
 
 import torch
@@ -685,14 +686,29 @@ class AugmentedStep:
     :func:`voxelize_map_grid_accurate` into a static float32 buffer, with ``dtype`` :func:`narrow_volumes` into the 2-byte
     volume, and without the head the labels as in the ``dtype`` step (``gt`` on the GPU, covering the pack).  One linear
     graph on one stream over static buffers again; ``max_l`` / ``mid_p`` / ``status``, ``xforms`` and the labels are the
-    projective step's bit for bit."""
+    projective step's bit for bit.
+
+    ``heatmap=(res, sigma)`` or ``(res, sigma, dtype)`` (needs ``gt``): the step also writes the voxel-to-voxel target, one
+    Gaussian volume per joint, into ONE static buffer ``self.heat`` ``[n, J, res, res, res]`` (float32 unless ``dtype`` says
+    otherwise; ``res`` is the heatmap's own resolution, in the step's ``layout``).  It is one more launch at the end of the
+    same linear sequence — :func:`joint_heatmaps` of the step's ``gt_nor`` and ``status`` — and combines with every option
+    above.  ``step`` returns exactly what it returns without it; ``heatmap=None`` issues exactly the launches listed above."""
 
     def __init__(self, depth: torch.Tensor, offsets: torch.Tensor, headers: torch.Tensor, n: int,
                  gt: Optional[torch.Tensor] = None, centres: Optional[torch.Tensor] = None, res: int = 32,
                  layout: str = "czyx", clamp: bool = True, cam: Optional[_lib.TsdfCam] = None, graph: bool = True,
                  dtype: Optional[torch.dtype] = None, base: Optional[torch.Tensor] = None, fused_head: bool = False,
-                 tsdf: str = "projective"):
+                 heatmap: Optional[tuple] = None, tsdf: str = "projective"):
         self.accurate = _tsdf_kind(tsdf)
+        self.heat = self._heatmap = None
+        if heatmap is not None:
+            if not isinstance(heatmap, (tuple, list)) or len(heatmap) not in (2, 3):
+                raise ValueError("heatmap must be (res, sigma) or (res, sigma, dtype)")
+            hdtype = heatmap[2] if len(heatmap) == 3 else torch.float32
+            _heat_dtype(hdtype)
+            self._heatmap = (_heat_res(heatmap[0]), _heat_sigma(heatmap[1]), hdtype)
+            if gt is None:
+                raise ValueError("heatmap needs gt: the volumes are written from the step's gt_nor")
         if graph not in (False, True):
             raise ValueError(f"graph must be False or True, got {graph!r}")
         if fused_head not in (False, True):
@@ -744,6 +760,9 @@ class AugmentedStep:
             self.gt_aug = torch.empty(shape, dtype=torch.float32, device=dev)
             if placed and not self._head:   # the batch's frame numbers kept inside the pack, and its joints before the map
                 self._sel = (torch.empty(n, dtype=torch.int64, device=dev), torch.empty(shape, dtype=torch.float32, device=dev))
+            if self._heatmap is not None:   # the static target volumes, one per joint
+                hres, _, hdtype = self._heatmap
+                self.heat = torch.empty((n, _coords("gt", self.gt_nor, n) // 3, hres, hres, hres), dtype=hdtype, device=dev)
         if self._head:   # what map_step_head writes into: the object's own buffers
             g = self._grid if placed else MapGridBatch(None, None, None, None)
             self._head_out = MapStepBatch(self.xforms, g.grid, g.max_l, g.mid_p, g.status, self.gt_aug, self.gt_nor)
@@ -770,6 +789,12 @@ class AugmentedStep:
             narrow_volumes(vol32, dtype=self.dtype, out=self.out.tsdf)
 
     def _run(self):
+        self._step_launches()
+        if self._heatmap is not None:   # one more launch at the end of the same linear sequence
+            hres, sigma, hdtype = self._heatmap
+            joint_heatmaps(self.gt_nor, hres, sigma, layout=self.layout, dtype=hdtype, status=self.out.status, out=self.heat)
+
+    def _step_launches(self):
         d, o, h = self._pack_args
         if self._head:
             placed = self._placed
@@ -1741,3 +1766,115 @@ def voxelize_frames(frames: torch.Tensor, res: int = 32, *, placement: str = "aa
     if gt_nor is None:
         gt_nor = normalize_joints(gt, batch.max_l, batch.mid_p)
     return batch, crops, gt_nor
+
+
+_HEAT_DTYPES = {torch.float32: _lib.TSDF_HEATMAP_F32, **_LOWP_DTYPES}
+
+
+def _heat_dtype(dtype) -> int:
+    """The dtype code of include/tsdf_heatmap.h of a torch dtype; anything but float32 / float16 / bfloat16 is a ValueError."""
+    code = _HEAT_DTYPES.get(dtype) if isinstance(dtype, torch.dtype) else None
+    if code is None:
+        raise ValueError(f"dtype must be torch.float32, torch.float16 or torch.bfloat16, got {dtype!r}")
+    return code
+
+
+def _heat_res(res) -> int:
+    """``res`` as an int the library voxelizes at (the rule of :func:`_pack`), else a ValueError."""
+    try:
+        ok = _lib.load().tsdf_resolution_supported(int(res))
+    except (TypeError, ValueError):
+        ok = False
+    if not ok:
+        raise ValueError(f"unsupported grid resolution {res!r} (multiple of 4 in 4..128)")
+    return int(res)
+
+
+def _heat_sigma(sigma) -> float:
+    """``sigma`` as the float32 the entry takes: finite and > 0 as that float32, else a ValueError."""
+    try:
+        s = ctypes.c_float(sigma).value
+    except TypeError:
+        s = float("nan")
+    if not 0.0 < s < float("inf"):
+        raise ValueError(f"sigma must be a finite number > 0 (in voxels, as a float32), got {sigma!r}")
+    return s
+
+
+def _heat_layout(layout) -> int:
+    if layout not in _lib.LAYOUTS:
+        raise ValueError("layout must be 'czyx' or 'cxyz'")
+    return _lib.LAYOUTS[layout]
+
+
+def joint_heatmaps(gt_nor: torch.Tensor, res: int = 32, sigma: float = 1.7, layout: str = "czyx",
+                   dtype: torch.dtype = torch.float32, status: Optional[torch.Tensor] = None,
+                   out: Optional[torch.Tensor] = None, return_valid: bool = False):
+    """One Gaussian volume per joint, aligned voxel for voxel with the TSDF volume of the same frame at resolution ``res``
+    (``tsdf_joint_heatmaps_hip`` of libtsdf_heatmap.so; include/tsdf_heatmap.h has the contract): the target of a
+    voxel-to-voxel network, written once by one launch.
+
+    gt_nor   float32[n,3J] or [n,J,3] on the GPU: the normalised labels ``(gt - mid_p) / max_l + 0.5`` — ``gt_nor`` of every
+             entry that writes labels, of :func:`normalize_joints` and of :class:`AugmentedStep`.  A joint sits at voxel
+             coordinate ``u * res - 0.5`` under every placement and every per-frame map, so the grid is not an argument
+    sigma    the Gaussian's standard deviation in voxels of this grid; the peak is 1, there is no truncation window
+    layout   the last three axes are z, y, x ("czyx") or x, y, z ("cxyz"): the volume's own
+    dtype    torch.float32, torch.float16 or torch.bfloat16 (the float32 value narrowed by round-to-nearest-even)
+    status   optional int32[n] on the GPU (a voxelizer's): the joints of a frame whose status is not 0 get zero volumes
+    out      optional preallocated ``dtype[n,J,res,res,res]`` to write into (it is returned); every byte is written
+    Returns ``heat``, or ``(heat, valid int32[n,J])`` with ``return_valid``: 0 for a joint with a non-finite coordinate or of
+    a frame with a non-zero status (its volume is zero), else 1 — a joint outside the cube is valid and gets its tail.
+    One launch on the current stream, no synchronisation."""
+    R, s, lay, code = _heat_res(res), _heat_sigma(sigma), _heat_layout(layout), _heat_dtype(dtype)
+    _dev_check("gt_nor", gt_nor, torch.float32)
+    if gt_nor.dim() < 2:
+        raise ValueError("gt_nor must have shape [n, 3*J] or [n, J, 3]")
+    dev, n = gt_nor.device, gt_nor.shape[0]
+    J = (_coords("gt_nor", gt_nor, n) or math.prod(gt_nor.shape[1:])) // 3   # (n == 0: nothing to count, J by the shape)
+    if status is not None:
+        _shaped("status", status, (n,), torch.int32, dev)
+    heat = _out("out", out, (n, J, R, R, R), dtype, dev)
+    valid = _out("valid", None, (n, J), torch.int32, dev) if return_valid else None
+    if n:
+        _call(dev, _lib.load_heatmap().tsdf_joint_heatmaps_hip,
+              [gt_nor.data_ptr(), _ptr(status), n, J, R, s, lay, code, None, heat.data_ptr(), _ptr(valid)], 8)
+    return (heat, valid) if return_valid else heat
+
+
+class HeatmapJoints(NamedTuple):
+    u: torch.Tensor      # float32[n,J,3]  normalised coordinates, columns x, y, z
+    peak: torch.Tensor   # float32[n,J]    the maximum of the joint's volume
+    arg: torch.Tensor    # int32[n,J]      its linear index within the volume, in memory order (-1: every value is a NaN)
+
+
+def heatmap_joints(heat: torch.Tensor, layout: str = "czyx", radius: int = 0,
+                   out: Optional[HeatmapJoints] = None) -> HeatmapJoints:
+    """Per joint the peak of a (predicted) heatmap volume as normalised coordinates (``tsdf_heatmap_joints_hip`` of
+    libtsdf_heatmap.so; include/tsdf_heatmap.h has the contract) — what :func:`denormalize_joints`,
+    ``transform_joints(..., invert_xforms(...))`` and :func:`pose_error` take.
+
+    heat     float32 / float16 / bfloat16 ``[n,J,R,R,R]`` on the GPU in ``layout``, R a multiple of 4 in 4..128
+    radius   0: the centre of the maximal voxel.  1..3: the centre of mass of ``max(h, 0)`` over the (2·radius+1)³ window
+             about it, clipped to the grid (the maximal voxel's centre where that mass is not a finite number > 0)
+    out      optional preallocated :class:`HeatmapJoints` to write into (it is returned)
+    The maximum is taken with ``>``: a NaN is never it, ties go to the lowest index in memory.  A volume of NaNs alone gives
+    ``arg`` -1, ``peak`` NaN and ``u`` 0.5.  One launch on the current stream, no synchronisation."""
+    lay = _heat_layout(layout)
+    if not isinstance(radius, int) or isinstance(radius, bool) or not 0 <= radius <= 3:
+        raise ValueError(f"radius must be 0, 1, 2 or 3, got {radius!r}")
+    if not isinstance(heat, torch.Tensor):
+        raise TypeError("heat must be a torch.Tensor")
+    code = _heat_dtype(heat.dtype)
+    _dev_check("heat", heat, heat.dtype)
+    if heat.dim() != 5 or heat.shape[2] != heat.shape[3] or heat.shape[3] != heat.shape[4]:
+        raise ValueError("heat must have shape [n, J, R, R, R]")
+    n, J, R = heat.shape[0], heat.shape[1], _heat_res(heat.shape[2])
+    if not 1 <= J <= 170:
+        raise ValueError("heat must hold 1..170 joints per frame")
+    dev = heat.device
+    res = _outs(HeatmapJoints, out, (("u", (n, J, 3), torch.float32), ("peak", (n, J), torch.float32),
+                                     ("arg", (n, J), torch.int32)), dev)
+    if n:
+        _call(dev, _lib.load_heatmap().tsdf_heatmap_joints_hip,
+              [heat.data_ptr(), code, n, J, R, lay, radius, None, res.u.data_ptr(), res.peak.data_ptr(), res.arg.data_ptr()], 7)
+    return res
