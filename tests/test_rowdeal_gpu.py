@@ -10,56 +10,14 @@ import pytest
 import torch
 
 import oracle
+from frame_zoo import HEIGHTS, SEED, WIDTHS, _blob, rowdeal_frames
 
 pytestmark = pytest.mark.gpu
 
-HEIGHTS = [1, 2, 3, 7, 8, 9, 23, 24, 25, 47, 48, 49, 240]
-WIDTHS = [1, 64, 65, 128, 129, 192, 193, 256, 257, 319, 320, 321, 640]
-
-
-def _blob(rng, bh, bw):
-    """A noisy bulge with holes over most of the frame: every row and column class sees valid and invalid pixels."""
-    ys, xs = np.mgrid[0:bh, 0:bw]
-    cy, cx = rng.uniform(0.2, 0.8) * bh, rng.uniform(0.2, 0.8) * bw
-    ry, rx = max(1.0, rng.uniform(0.3, 0.7) * bh), max(1.0, rng.uniform(0.3, 0.7) * bw)
-    rr = ((ys - cy) / ry) ** 2 + ((xs - cx) / rx) ** 2
-    d = rng.uniform(300, 600) - 40.0 * np.sqrt(np.clip(1.0 - rr, 0.0, 1.0)) + rng.normal(0, 1, (bh, bw))
-    d = np.where((rr < 1.0) & (rng.random((bh, bw)) > 0.02), d, 0.0)
-    if not (np.abs(d) >= 1.0).any():
-        d[bh // 2, bw // 2] = 450.0
-    return d.astype(np.float32)
-
-
-def _only(bh, bw, rows=None, cols=None, seed=0):
-    """Valid pixels in the given rows (or columns) alone."""
-    rng = np.random.default_rng(seed)
-    d = np.zeros((bh, bw), np.float32)
-    full = (rng.uniform(350, 500, (bh, bw))).astype(np.float32)
-    if rows is not None:
-        d[rows, :] = full[rows, :]
-    if cols is not None:
-        d[:, cols] = full[:, cols]
-    return d
-
 
 def _batch(n):
-    rng = np.random.default_rng(20261)
-    imgs = []
-    for bh in HEIGHTS:                       # every height with every width
-        for bw in WIDTHS:
-            imgs.append(_blob(rng, bh, bw))
-    for bh, bw in ((240, 320), (25, 193), (49, 321), (9, 65), (47, 640)):
-        imgs.append(_only(bh, bw, rows=[0], seed=bh))
-        imgs.append(_only(bh, bw, rows=[bh - 1], seed=bh + 1))
-        imgs.append(_only(bh, bw, cols=[0], seed=bh + 2))
-        imgs.append(_only(bh, bw, cols=[bw - 1], seed=bh + 3))
-        imgs.append(_only(bh, bw, rows=[bh // 2], seed=bh + 4))
-    imgs.append(np.zeros((48, 129), np.float32))                                       # all invalid: status 1
-    imgs.append(np.where(rng.random((24, 257)) < 0.5, np.nan, 0.5).astype(np.float32))  # NaNs and sub-threshold depths: too
-    nan = _blob(rng, 240, 320)
-    nan[rng.random(nan.shape) < 0.05] = np.nan                                         # NaN-laden, still a hand
-    nan[100, :] = np.nan
-    imgs.append(nan)
+    rng = np.random.default_rng(SEED)
+    imgs = rowdeal_frames(rng)
     assert len(imgs) <= n, "an MI355X has 256 CUs: the batch holds every frame above"
     k = 0
     while len(imgs) < n:                                                               # fill up with fresh draws
