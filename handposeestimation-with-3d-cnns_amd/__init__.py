@@ -46,6 +46,11 @@ The accurate directional TSDF:           voxelize_grid_accurate (per voxel the n
 Voxel heatmap labels:                    joint_heatmaps (one Gaussian volume per joint from gt_nor, aligned with the TSDF
                                          volume: libtsdf_heatmap.so, include/tsdf_heatmap.h), heatmap_joints (per joint the
                                          peak of a volume back as normalised coordinates), AugmentedStep(heatmap=...)
+Voxel heatmap training:                  heatmap_mse_loss (the squared error against joint_heatmaps' targets without the
+                                         targets in memory, with its gradient: libtsdf_heatloss.so,
+                                         include/tsdf_heatloss.h), soft_argmax_joints (the expectation under a softmax of
+                                         the whole volume as normalised coordinates, with its gradient); both are
+                                         torch.autograd.Functions, differentiable in the prediction
 """
 from . import _lib  # noqa: F401
 from ._lib import TsdfCam, TsdfError, default_cam  # noqa: F401
@@ -58,7 +63,8 @@ from .voxelize import (AabbBatch, AugmentedStep, CloudGridBatch, MapGridBatch, O
                        invert_xforms, obb_xforms, voxelize_obb, narrow_volumes, voxelize_grid_lowp, voxelize_lowp,
                        map_grids, voxelize_aug_lowp, voxelize_map_grid_lowp, MapStepBatch, compose_xforms, map_step_head,
                        HandCrops, locate_hands, voxelize_frames, voxelize_accurate, voxelize_grid_accurate,
-                       voxelize_aug_accurate, voxelize_map_grid_accurate, HeatmapJoints, heatmap_joints, joint_heatmaps)
+                       voxelize_aug_accurate, voxelize_map_grid_accurate, HeatmapJoints, heatmap_joints, joint_heatmaps,
+                       heatmap_mse_loss, soft_argmax_joints)
 from .pca import JointPCA, fit_joint_pca  # noqa: F401
 from . import augment, dataset, export, packing, pca, shard, synth  # noqa: F401
 from .dataset import MSRA_Dataset, MSRADepthDataset, ResidentLoader, VoxelBatch, VoxelLoader  # noqa: F401
@@ -76,4 +82,4 @@ __all__ = ["voxelize", "voxelize_labels", "voxelize_indexed", "ResidentLoader", 
            "voxelize_grid_lowp", "voxelize_lowp", "narrow_volumes", "map_grids", "MapGridBatch", "voxelize_map_grid_lowp",
            "voxelize_aug_lowp", "compose_xforms", "map_step_head", "MapStepBatch", "locate_hands", "voxelize_frames",
            "HandCrops", "voxelize_grid_accurate", "voxelize_accurate", "voxelize_map_grid_accurate", "voxelize_aug_accurate",
-           "joint_heatmaps", "heatmap_joints", "HeatmapJoints"]
+           "joint_heatmaps", "heatmap_joints", "HeatmapJoints", "heatmap_mse_loss", "soft_argmax_joints"]

@@ -153,6 +153,12 @@ HEATMAP_LIB_PATH = os.path.join(_HERE, "libtsdf_heatmap.so")
 HEATMAP_VERSION = 1
 TSDF_HEATMAP_F32 = 0   # the float32 element type of include/tsdf_heatmap.h; the 2-byte ones are TSDF_LOWP_*
 
+# The library of include/tsdf_heatloss.h (make -C csrc heatloss): the squared error of a predicted heatmap volume against
+# the Gaussian target of its label without that target in memory, a soft-argmax over the softmax of a whole volume, and
+# the gradient of each.  A binary of its own; its row is _HEATLOSS below, outside _EXTS like _HEATMAP.
+HEATLOSS_LIB_PATH = os.path.join(_HERE, "libtsdf_heatloss.so")
+HEATLOSS_VERSION = 1
+
 
 class _Ext(NamedTuple):
     """A row of the extension table: libtsdf_<name>.so, built by ``make -C csrc <name>`` from include/tsdf_<name>.h."""
@@ -248,6 +254,18 @@ _HEATMAP = _Ext(HEATMAP_LIB_PATH, "tsdf_heatmap_version", HEATMAP_VERSION, {
     "tsdf_joint_heatmaps_hip": [_vp, _vp, _i, _i, _i, ctypes.c_float, _i, _i, _vp, _vp, _vp],
     # heat, dtype, n, n_joints, R, layout, radius, stream, u, peak, arg
     "tsdf_heatmap_joints_hip": [_vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp],
+})
+
+# libtsdf_heatloss.so's row, of the same type and loaded by the same code (load_heatloss)
+_HEATLOSS = _Ext(HEATLOSS_LIB_PATH, "tsdf_heatloss_version", HEATLOSS_VERSION, {
+    # pred, dtype, u, status, n, n_joints, R, sigma, layout, stream, sse, valid
+    "tsdf_heat_sse_hip": [_vp, _i, _vp, _vp, _i, _i, _i, ctypes.c_float, _i, _vp, _vp, _vp],
+    # pred, dtype, u, status, w, n, n_joints, R, sigma, layout, stream, grad
+    "tsdf_heat_sse_grad_hip": [_vp, _i, _vp, _vp, _vp, _i, _i, _i, ctypes.c_float, _i, _vp, _vp],
+    # heat, dtype, n, n_joints, R, beta, layout, stream, u, stats
+    "tsdf_soft_argmax_hip": [_vp, _i, _i, _i, _i, ctypes.c_float, _i, _vp, _vp, _vp],
+    # heat, dtype, stats, grad_u, n, n_joints, R, beta, layout, stream, grad
+    "tsdf_soft_argmax_grad_hip": [_vp, _i, _vp, _vp, _i, _i, _i, ctypes.c_float, _i, _vp, _vp],
 })
 
 _lib = None
@@ -368,6 +386,11 @@ def _load_ext(name: str):
 def load_heatmap():
     """libtsdf_heatmap.so, the library of include/tsdf_heatmap.h (its row is ``_HEATMAP``)."""
     return _load_row("heatmap", _HEATMAP)
+
+
+def load_heatloss():
+    """libtsdf_heatloss.so, the library of include/tsdf_heatloss.h (its row is ``_HEATLOSS``)."""
+    return _load_row("heatloss", _HEATLOSS)
 
 
 def load_augment():

@@ -1878,3 +1878,169 @@ def heatmap_joints(heat: torch.Tensor, layout: str = "czyx", radius: int = 0,
         _call(dev, _lib.load_heatmap().tsdf_heatmap_joints_hip,
               [heat.data_ptr(), code, n, J, R, lay, radius, None, res.u.data_ptr(), res.peak.data_ptr(), res.arg.data_ptr()], 7)
     return res
+
+
+def _heat_tensor(name, t, dtype, dev, shape=None):
+    """An argument of the loss entries whose data pointer goes straight to a kernel: every defect is a ValueError."""
+    if not isinstance(t, torch.Tensor):
+        raise ValueError(f"{name} must be a torch.Tensor")
+    if not t.is_cuda:
+        raise ValueError(f"{name} must live on the GPU (there is no CPU path); got device {t.device}")
+    if dev is not None and t.device != dev:
+        raise ValueError(f"{name} is on {t.device}, expected {dev}")
+    if t.dtype != dtype:
+        raise ValueError(f"{name} must be {dtype}, got {t.dtype}")
+    if not t.is_contiguous():
+        raise ValueError(f"{name} must be contiguous")
+    if shape is not None and tuple(t.shape) != shape:
+        raise ValueError(f"{name} must have shape {shape}")
+    return t
+
+
+def _heat_volume(name, t):
+    """A volume ``[n,J,R,R,R]`` as libtsdf_heatloss.so reads it, in its own dtype: ``(dtype code, n, J, R)``."""
+    if not isinstance(t, torch.Tensor):
+        raise ValueError(f"{name} must be a torch.Tensor")
+    code = _heat_dtype(t.dtype)
+    _heat_tensor(name, t, t.dtype, None)
+    if t.dim() != 5 or t.shape[2] != t.shape[3] or t.shape[3] != t.shape[4]:
+        raise ValueError(f"{name} must have shape [n, J, R, R, R]")
+    n, J, R = t.shape[0], t.shape[1], _heat_res(t.shape[2])
+    if not 1 <= J <= 170:
+        raise ValueError(f"{name} must hold 1..170 joints per frame")
+    if n * J >= 1 << 24:
+        raise ValueError(f"{name} must hold fewer than 2^24 (frame, joint) pairs")
+    if t.data_ptr() % 16:
+        raise ValueError(f"{name} must be 16-byte aligned")
+    return code, n, J, R
+
+
+_HEAT_REDUCTIONS = ("mean", "sum", "none")
+
+
+def _heat_reduce(sse, valid, R, reduction):
+    """``(loss, factor)`` of the per-unit float64 ``sse`` and int32 ``valid``, both ``[n,J]``: the reduced loss in float64 and
+    the float64 ``[n,J]`` factor that turns the loss's upstream gradient into the gradient kernel's per-unit ``w``
+    (``d loss / d pred = factor * (pred - target)``).  Torch ops on the device; an invalid unit's sse is 0 already."""
+    r3 = float(R) ** 3
+    ok = valid.to(torch.float64)
+    if reduction == "mean":       # over the voxels of the valid units; 0 when there is none (sse and valid are all 0 then)
+        denom = (ok.sum() * r3).clamp_min(1.0)
+        return sse.sum() / denom, (2.0 * ok) / denom
+    if reduction == "sum":
+        return sse.sum(), 2.0 * ok
+    return sse / r3, (2.0 * ok) / r3
+
+
+class _HeatSse(torch.autograd.Function):
+    """``heatmap_mse_loss`` once its arguments are judged: tsdf_heat_sse_hip, the reduction; tsdf_heat_sse_grad_hip."""
+
+    @staticmethod
+    def forward(ctx, pred, gt_nor, status, sigma, lay, reduction, shape):
+        code, n, J, R = shape
+        dev = pred.device
+        sse = torch.empty((n, J), dtype=torch.float64, device=dev)
+        valid = torch.empty((n, J), dtype=torch.int32, device=dev)
+        if n:
+            _call(dev, _lib.load_heatloss().tsdf_heat_sse_hip,
+                  [pred.data_ptr(), code, gt_nor.data_ptr(), _ptr(status), n, J, R, sigma, lay, None, sse.data_ptr(),
+                   valid.data_ptr()], 9)
+        loss, factor = _heat_reduce(sse, valid, R, reduction)
+        ctx.save_for_backward(pred, gt_nor, status, factor)
+        ctx.heat = (sigma, lay, shape)
+        return loss.to(torch.float32)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_out):
+        pred, gt_nor, status, factor = ctx.saved_tensors
+        sigma, lay, (code, n, J, R) = ctx.heat
+        w = (grad_out.to(torch.float64) * factor).to(torch.float32).contiguous()
+        grad = torch.empty_like(pred)
+        if n:
+            _call(pred.device, _lib.load_heatloss().tsdf_heat_sse_grad_hip,
+                  [pred.data_ptr(), code, gt_nor.data_ptr(), _ptr(status), w.data_ptr(), n, J, R, sigma, lay, None,
+                   grad.data_ptr()], 10)
+        return grad, None, None, None, None, None, None
+
+
+def heatmap_mse_loss(pred: torch.Tensor, gt_nor: torch.Tensor, sigma: float = 1.7, layout: str = "czyx",
+                     status: Optional[torch.Tensor] = None, reduction: str = "mean") -> torch.Tensor:
+    """The squared error of predicted heatmap volumes against the Gaussian targets of :func:`joint_heatmaps` — without the
+    targets in memory: ``((pred - joint_heatmaps(gt_nor, R, sigma, layout, status=status)) ** 2)`` reduced, as a
+    ``torch.autograd.Function`` over ``tsdf_heat_sse_hip`` / ``tsdf_heat_sse_grad_hip`` of libtsdf_heatloss.so
+    (include/tsdf_heatloss.h has the contract).  Every target voxel is regenerated from the label in the kernel, bit for
+    bit the encode's float32; differences, squares and sums are float64.
+
+    pred       float32 / float16 / bfloat16 ``[n,J,R,R,R]`` on the GPU in ``layout``, taken in its own dtype; the only
+               argument that receives a gradient (of pred's dtype; once differentiable)
+    gt_nor     float32[n,3J] or [n,J,3] on the GPU, as :func:`joint_heatmaps` takes it; it gets no gradient
+    status     optional int32[n] on the GPU (a voxelizer's)
+    reduction  "mean": the sum over the valid units divided by (their count · R³), 0 when no unit is valid; "sum"; or
+               "none": float32[n,J], every unit's own mean
+    A unit with a non-finite label or of a frame whose status is not 0 is invalid: it adds nothing to the loss and its
+    gradient is zero.  Returns a float32 tensor.  One launch and a few small torch ops on the current stream for the
+    forward, the same for the backward; no host synchronisation anywhere."""
+    if reduction not in _HEAT_REDUCTIONS:
+        raise ValueError(f"reduction must be 'mean', 'sum' or 'none', got {reduction!r}")
+    s, lay = _heat_sigma(sigma), _heat_layout(layout)
+    shape = _heat_volume("pred", pred)
+    _, n, J, _ = shape
+    dev = pred.device
+    _heat_tensor("gt_nor", gt_nor, torch.float32, dev)
+    if tuple(gt_nor.shape) not in ((n, 3 * J), (n, J, 3)):
+        raise ValueError(f"gt_nor must have shape [{n}, {3 * J}] or [{n}, {J}, 3]: the labels of pred's joints")
+    if status is not None:
+        _heat_tensor("status", status, torch.int32, dev, (n,))
+    return _HeatSse.apply(pred, gt_nor, status, s, lay, reduction, shape)
+
+
+class _SoftArgmax(torch.autograd.Function):
+    """``soft_argmax_joints`` once its arguments are judged: tsdf_soft_argmax_hip; tsdf_soft_argmax_grad_hip."""
+
+    @staticmethod
+    def forward(ctx, heat, beta, lay, shape):
+        code, n, J, R = shape
+        dev = heat.device
+        u = torch.empty((n, J, 3), dtype=torch.float32, device=dev)
+        stats = torch.empty((n, J, 5), dtype=torch.float64, device=dev)
+        if n:
+            _call(dev, _lib.load_heatloss().tsdf_soft_argmax_hip,
+                  [heat.data_ptr(), code, n, J, R, beta, lay, None, u.data_ptr(), stats.data_ptr()], 7)
+        ctx.save_for_backward(heat, stats)
+        ctx.heat = (beta, lay, shape)
+        return u
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_u):
+        heat, stats = ctx.saved_tensors
+        beta, lay, (code, n, J, R) = ctx.heat
+        gu = grad_u.to(torch.float32).contiguous()
+        grad = torch.empty_like(heat)
+        if n:
+            _call(heat.device, _lib.load_heatloss().tsdf_soft_argmax_grad_hip,
+                  [heat.data_ptr(), code, stats.data_ptr(), gu.data_ptr(), n, J, R, beta, lay, None, grad.data_ptr()], 9)
+        return grad, None, None, None
+
+
+def soft_argmax_joints(pred: torch.Tensor, beta: float = 1.0, layout: str = "czyx") -> torch.Tensor:
+    """Per joint the expectation of the voxel position under ``softmax(beta * pred)`` over the whole volume, as normalised
+    coordinates (integral regression): the differentiable counterpart of :func:`heatmap_joints`, a
+    ``torch.autograd.Function`` over ``tsdf_soft_argmax_hip`` / ``tsdf_soft_argmax_grad_hip`` of libtsdf_heatloss.so
+    (include/tsdf_heatloss.h has the contract).
+
+    pred     float32 / float16 / bfloat16 ``[n,J,R,R,R]`` on the GPU in ``layout``, taken in its own dtype
+    beta     the softmax's inverse temperature, a finite number > 0 (as a float32)
+    Returns float32[n,J,3], columns x, y, z — what :func:`denormalize_joints`, :func:`transform_joints`, :func:`pose_error`
+    or an L1 loss against ``gt_nor`` take — differentiable (once) in ``pred``.  Sums are float64.  A volume that holds a NaN
+    or whose maximum is not finite gives NaN for its joint alone.  One launch on the current stream each way, no
+    synchronisation."""
+    try:
+        b = ctypes.c_float(beta).value
+    except TypeError:
+        b = float("nan")
+    if not 0.0 < b < float("inf"):
+        raise ValueError(f"beta must be a finite number > 0 (as a float32), got {beta!r}")
+    lay = _heat_layout(layout)
+    return _SoftArgmax.apply(pred, b, lay, _heat_volume("pred", pred))
