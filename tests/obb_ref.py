@@ -59,10 +59,13 @@ def frame(depth, hdr, focal=F, cx=CX, cy=CY, eps=EPS):
     out = dict(status=1, N=N, mu=np.zeros(3), C=np.zeros((3, 3)), lam=np.zeros(3), A=np.eye(3), xf=identity(), pts=pts)
     if N < 3:
         return out
-    mu = pts.sum(axis=0) / N
-    q = pts - mu
-    C = (q.T @ q) / N
-    if not (np.isfinite(mu).all() and np.isfinite(C).all()) or np.trace(C) == 0:
+    with np.errstate(invalid="ignore", over="ignore"):   # an infinite depth is a valid pixel: the mean is not finite
+        mu = pts.sum(axis=0) / N
+        if not np.isfinite(mu).all():                    # the contract's rule: degenerate, the count kept, zero moments
+            return out
+        q = pts - mu
+        C = (q.T @ q) / N
+    if not np.isfinite(C).all() or np.trace(C) == 0:
         return out
     w, V = np.linalg.eigh(C)                     # ascending
     lam = w[::-1].copy()
@@ -106,3 +109,88 @@ def rel_gaps(lam):
     """The two gaps between neighbouring eigenvalues, relative to the trace."""
     t = lam.sum()
     return (lam[0] - lam[1]) / t, (lam[1] - lam[2]) / t
+
+
+# ---- the spectrum list: crops whose covariance has tied, vanishing or ill-conditioned eigenvalues ----------------------
+HUGE = 2.0 ** 91      # about 2.5e27: a depth of 400..600 mm times it is of magnitude 1e30, an exact scaling in float32
+
+
+def _iso(a, b):
+    """9 x 9 pixels centred on the principal point, depth 500 + a s + b t with s = +-1 by the parity of |u| + |v| and
+    t = sign(|u| - |v|): symmetric under u -> -u and v -> -v, so the covariance is diagonal; a sets the spread in z, b
+    makes the pixels far out in x deeper than those far out in y."""
+    u = np.arange(-4, 5)
+    uu, vv = np.meshgrid(u, u)
+    s = np.where((np.abs(uu) + np.abs(vv)) % 2 == 0, 1.0, -1.0)
+    return (500.0 + a * s + b * np.sign(np.abs(uu) - np.abs(vv))).astype(np.float32)
+
+
+def _iso_gaps(a, b):
+    C = frame(_iso(a, b).reshape(-1), np.array([320, 240, 156, 116, 165, 125], np.int32))["C"]
+    return np.array([C[0, 0] - C[1, 1], C[1, 1] - C[2, 2]]) / np.trace(C)
+
+
+def _near_isotropic(target=3e-5):
+    """(a, b) of :func:`_iso` with Cxx - Cyy = Cyy - Czz = target * trace: Newton's method on the float32 depths."""
+    x = np.array([5.35, 0.0])
+    for _ in range(12):
+        f = _iso_gaps(*x) - target
+        h = 1e-2
+        Jm = np.stack([(_iso_gaps(x[0] + h, x[1]) - target - f) / h, (_iso_gaps(x[0], x[1] + h) - target - f) / h], axis=1)
+        x = x - np.linalg.solve(Jm, f)
+    return x
+
+
+_spectrum = None
+
+
+def spectrum():
+    """[(name, left, top, img float32[h, w])] in a 320 x 240 image under the default camera.  Made once, never modified;
+    tests/test_obb_hard_cpu.py asserts on the restatement what each name claims."""
+    global _spectrum
+    if _spectrum is not None:
+        return _spectrum
+    rng = np.random.default_rng(20261022)
+    inf = np.float32(np.inf)
+    out = [("plane_const", 100, 80, np.full((9, 13), 500.0)),                    # fronto-parallel: lambda_3 = 0
+           ("square_centred", 156, 116, np.full((9, 9), 500.0))]                 # and lambda_1 = lambda_2
+    three = np.zeros((4, 7))
+    three[1, [0, 3, 6]] = 500.0
+    out.append(("three_collinear", 158, 30, three))
+    tri = np.zeros((4, 7))
+    tri[0, 1], tri[3, 0], tri[2, 6] = 480.0, 510.0, 495.0
+    out.append(("three_triangle", 40, 50, tri))
+    line = np.float32(500.0) + rng.integers(0, 33, (1, 300)).astype(np.float32) * np.float32(2.0 ** -15)   # ulps of 500
+    out.append(("near_collinear", 10, 100, line))
+    out.append(("near_isotropic", 156, 116, _iso(*_near_isotropic())))
+    # a plane in space is linear in 1 / d over the pixels
+    r, c = np.mgrid[0:20, 0:30]
+    plane = 1.0 / (1.0 / 450.0 + 1.2e-5 * c - 0.9e-5 * r)
+    out.append(("tilted_plane", 70, 60, plane))
+    blob = 400.0 + 200.0 * rng.random((5, 7))
+    blob[1, 2] = 0.0
+    out.append(("huge", 120, 100, blob.astype(np.float32) * np.float32(HUGE)))
+    one = (450.0 + 40.0 * rng.random((6, 5))).astype(np.float32)
+    one[2, 3] = inf
+    out.append(("one_inf", 200, 100, one))
+    both = one.copy()
+    both[4, 1] = -inf
+    out.append(("pm_inf", 30, 150, both))
+    _spectrum = tuple((name, left, top, np.ascontiguousarray(img, np.float32)) for name, left, top, img in out)
+    for e in _spectrum:
+        e[3].setflags(write=False)
+    return _spectrum
+
+
+def spectrum_pack():
+    """(depth, offsets, headers) of :func:`spectrum`."""
+    sp = spectrum()
+    depth = np.concatenate([img.reshape(-1) for _, _, _, img in sp])
+    off = np.concatenate([[0], np.cumsum([img.size for _, _, _, img in sp])]).astype(np.int64)
+    hdr = np.array([[320, 240, left, top, left + img.shape[1], top + img.shape[0]] for _, left, top, img in sp], np.int32)
+    return depth, off, hdr
+
+
+def rescaled(f, s):
+    """The restatement's frame ``f`` with every length multiplied by s (a power of two: exact)."""
+    return dict(f, mu=f["mu"] * s, C=f["C"] * s * s, lam=f["lam"] * s * s, pts=f["pts"] * s, xf=None)
