@@ -51,6 +51,10 @@ Voxel heatmap training:                  heatmap_mse_loss (the squared error aga
                                          include/tsdf_heatloss.h), soft_argmax_joints (the expectation under a softmax of
                                          the whole volume as normalised coordinates, with its gradient); both are
                                          torch.autograd.Functions, differentiable in the prediction
+Occupancy volumes:                       occupancy_volumes (the one-channel input of V2V-PoseNet and its family on the cube
+                                         of any placement, every pixel scattered into a bit mask in LDS:
+                                         libtsdf_occupancy.so, include/tsdf_occupancy.h), voxelize_occupancy (placed on the
+                                         cloud's own cube), AugmentedStep(occupancy=...)
 """
 from . import _lib  # noqa: F401
 from ._lib import TsdfCam, TsdfError, default_cam  # noqa: F401
@@ -64,7 +68,7 @@ from .voxelize import (AabbBatch, AugmentedStep, CloudGridBatch, MapGridBatch, O
                        map_grids, voxelize_aug_lowp, voxelize_map_grid_lowp, MapStepBatch, compose_xforms, map_step_head,
                        HandCrops, locate_hands, voxelize_frames, voxelize_accurate, voxelize_grid_accurate,
                        voxelize_aug_accurate, voxelize_map_grid_accurate, HeatmapJoints, heatmap_joints, joint_heatmaps,
-                       heatmap_mse_loss, soft_argmax_joints)
+                       heatmap_mse_loss, soft_argmax_joints, occupancy_volumes, voxelize_occupancy)
 from .pca import JointPCA, fit_joint_pca  # noqa: F401
 from . import augment, dataset, export, packing, pca, shard, synth  # noqa: F401
 from .dataset import MSRA_Dataset, MSRADepthDataset, ResidentLoader, VoxelBatch, VoxelLoader  # noqa: F401
@@ -82,4 +86,5 @@ __all__ = ["voxelize", "voxelize_labels", "voxelize_indexed", "ResidentLoader", 
            "voxelize_grid_lowp", "voxelize_lowp", "narrow_volumes", "map_grids", "MapGridBatch", "voxelize_map_grid_lowp",
            "voxelize_aug_lowp", "compose_xforms", "map_step_head", "MapStepBatch", "locate_hands", "voxelize_frames",
            "HandCrops", "voxelize_grid_accurate", "voxelize_accurate", "voxelize_map_grid_accurate", "voxelize_aug_accurate",
-           "joint_heatmaps", "heatmap_joints", "HeatmapJoints", "heatmap_mse_loss", "soft_argmax_joints"]
+           "joint_heatmaps", "heatmap_joints", "HeatmapJoints", "heatmap_mse_loss", "soft_argmax_joints",
+           "occupancy_volumes", "voxelize_occupancy"]

@@ -159,6 +159,13 @@ TSDF_HEATMAP_F32 = 0   # the float32 element type of include/tsdf_heatmap.h; the
 HEATLOSS_LIB_PATH = os.path.join(_HERE, "libtsdf_heatloss.so")
 HEATLOSS_VERSION = 1
 
+# The library of include/tsdf_occupancy.h (make -C csrc occupancy): one-channel occupancy volumes on a caller-placed grid,
+# every pixel of the crop scattered into a bit mask in LDS.  A binary of its own; its row is _OCCUPANCY below, outside
+# _EXTS like _HEATMAP.
+OCCUPANCY_LIB_PATH = os.path.join(_HERE, "libtsdf_occupancy.so")
+OCCUPANCY_VERSION = 1
+OCCUPANCY_LDS_CAP = 64 * 1024   # bytes of bit mask per workgroup (kOccLdsCap of csrc/occupancy_host.inc)
+
 
 class _Ext(NamedTuple):
     """A row of the extension table: libtsdf_<name>.so, built by ``make -C csrc <name>`` from include/tsdf_<name>.h."""
@@ -266,6 +273,16 @@ _HEATLOSS = _Ext(HEATLOSS_LIB_PATH, "tsdf_heatloss_version", HEATLOSS_VERSION, {
     "tsdf_soft_argmax_hip": [_vp, _i, _i, _i, _i, ctypes.c_float, _i, _vp, _vp, _vp],
     # heat, dtype, stats, grad_u, n, n_joints, R, beta, layout, stream, grad
     "tsdf_soft_argmax_grad_hip": [_vp, _i, _vp, _vp, _i, _i, _i, ctypes.c_float, _i, _vp, _vp],
+})
+
+# libtsdf_occupancy.so's row, of the same type and loaded by the same code (load_occupancy)
+_OCCUPANCY = _Ext(OCCUPANCY_LIB_PATH, "tsdf_occupancy_version", OCCUPANCY_VERSION, {
+    # R, slab_hint, slab, nslab, lds_bytes (three ints in host memory)
+    "tsdf_occupancy_plan": [_i, _i, ctypes.POINTER(_i), ctypes.POINTER(_i), ctypes.POINTER(_i)],
+    # depth, depth_len, offsets, headers, n_src, index, n, R, focal, cx, cy, invalid_eps, trunc_voxels (the camera by
+    # value), layout, dtype, slab_hint, stream, xforms, max_l, mid_p, occ, status
+    "tsdf_occupancy_hip": [_vp, _i64, _vp, _vp, _i64, _vp, _i, _i, ctypes.c_double, ctypes.c_double, ctypes.c_double,
+                           ctypes.c_float, ctypes.c_float, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp],
 })
 
 _lib = None
@@ -391,6 +408,11 @@ def load_heatmap():
 def load_heatloss():
     """libtsdf_heatloss.so, the library of include/tsdf_heatloss.h (its row is ``_HEATLOSS``)."""
     return _load_row("heatloss", _HEATLOSS)
+
+
+def load_occupancy():
+    """libtsdf_occupancy.so, the library of include/tsdf_occupancy.h (its row is ``_OCCUPANCY``)."""
+    return _load_row("occupancy", _OCCUPANCY)
 
 
 def load_augment():

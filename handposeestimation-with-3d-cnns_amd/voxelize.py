@@ -692,15 +692,29 @@ class AugmentedStep:
     Gaussian volume per joint, into ONE static buffer ``self.heat`` ``[n, J, res, res, res]`` (float32 unless ``dtype`` says
     otherwise; ``res`` is the heatmap's own resolution, in the step's ``layout``).  It is one more launch at the end of the
     same linear sequence — :func:`joint_heatmaps` of the step's ``gt_nor`` and ``status`` — and combines with every option
-    above.  ``step`` returns exactly what it returns without it; ``heatmap=None`` issues exactly the launches listed above."""
+    above.  ``step`` returns exactly what it returns without it; ``heatmap=None`` issues exactly the launches listed above.
+
+    ``occupancy=(res,)`` or ``(res, dtype)``: the step also writes the input of a voxel-to-voxel network, the one-channel
+    occupancy volume of the batch under the step's maps, into ONE static buffer ``self.occ`` ``[n, 1, res, res, res]``
+    (float32 unless ``dtype`` says otherwise; ``res`` is the occupancy's own resolution, in the step's ``layout``).  It is
+    one more launch at the very end of the same linear sequence — :func:`occupancy_volumes` of the step's own ``index``,
+    ``xforms``, ``out.max_l`` and ``out.mid_p`` — needs no ``gt`` and combines with every option above.  ``step`` returns
+    exactly what it returns without it; ``occupancy=None`` issues exactly the launches listed above."""
 
     def __init__(self, depth: torch.Tensor, offsets: torch.Tensor, headers: torch.Tensor, n: int,
                  gt: Optional[torch.Tensor] = None, centres: Optional[torch.Tensor] = None, res: int = 32,
                  layout: str = "czyx", clamp: bool = True, cam: Optional[_lib.TsdfCam] = None, graph: bool = True,
                  dtype: Optional[torch.dtype] = None, base: Optional[torch.Tensor] = None, fused_head: bool = False,
-                 heatmap: Optional[tuple] = None, tsdf: str = "projective"):
+                 heatmap: Optional[tuple] = None, occupancy: Optional[tuple] = None, tsdf: str = "projective"):
         self.accurate = _tsdf_kind(tsdf)
         self.heat = self._heatmap = None
+        self.occ = self._occupancy = None
+        if occupancy is not None:
+            if not isinstance(occupancy, (tuple, list)) or len(occupancy) not in (1, 2):
+                raise ValueError("occupancy must be (res,) or (res, dtype)")
+            odtype = occupancy[1] if len(occupancy) == 2 else torch.float32
+            _heat_dtype(odtype)
+            self._occupancy = (_heat_res(occupancy[0]), odtype)
         if heatmap is not None:
             if not isinstance(heatmap, (tuple, list)) or len(heatmap) not in (2, 3):
                 raise ValueError("heatmap must be (res, sigma) or (res, sigma, dtype)")
@@ -763,6 +777,9 @@ class AugmentedStep:
             if self._heatmap is not None:   # the static target volumes, one per joint
                 hres, _, hdtype = self._heatmap
                 self.heat = torch.empty((n, _coords("gt", self.gt_nor, n) // 3, hres, hres, hres), dtype=hdtype, device=dev)
+        if self._occupancy is not None:   # the static occupancy volume, at its own resolution
+            ores, odtype = self._occupancy
+            self.occ = torch.empty((n, 1, ores, ores, ores), dtype=odtype, device=dev)
         if self._head:   # what map_step_head writes into: the object's own buffers
             g = self._grid if placed else MapGridBatch(None, None, None, None)
             self._head_out = MapStepBatch(self.xforms, g.grid, g.max_l, g.mid_p, g.status, self.gt_aug, self.gt_nor)
@@ -793,6 +810,11 @@ class AugmentedStep:
         if self._heatmap is not None:   # one more launch at the end of the same linear sequence
             hres, sigma, hdtype = self._heatmap
             joint_heatmaps(self.gt_nor, hres, sigma, layout=self.layout, dtype=hdtype, status=self.out.status, out=self.heat)
+        if self._occupancy is not None:   # and one more: the batch's points under the step's maps, binned into the step's cubes
+            d, o, h = self._pack_args
+            ores, odtype = self._occupancy
+            _occupancy(d, o, h, self.out.max_l, self.out.mid_p, ores, self.layout, odtype, self.cam, self.xforms, self.index,
+                       self.occ, 0, False)
 
     def _step_launches(self):
         d, o, h = self._pack_args
@@ -2044,3 +2066,78 @@ def soft_argmax_joints(pred: torch.Tensor, beta: float = 1.0, layout: str = "czy
         raise ValueError(f"beta must be a finite number > 0 (as a float32), got {beta!r}")
     lay = _heat_layout(layout)
     return _SoftArgmax.apply(pred, b, lay, _heat_volume("pred", pred))
+
+
+def _occ_slab(slab) -> int:
+    """``slab`` as the hint the entry takes: an int >= 0 (0: the library's plan), else a ValueError."""
+    if isinstance(slab, bool) or not isinstance(slab, int) or not 0 <= slab < 2 ** 31:
+        raise ValueError(f"slab must be an int >= 0 (slices per workgroup; 0: the library's plan), got {slab!r}")
+    return slab
+
+
+def _occupancy(depth, offsets, headers, max_l, mid_p, res, layout, dtype, cam, xforms, index, out, slab, want_status):
+    """:func:`occupancy_volumes`; without ``want_status`` the launch writes no status and, given ``out``, the call
+    allocates nothing.  Returns (volume, status or None)."""
+    R, lay, code, hint = _heat_res(res), _heat_layout(layout), _heat_dtype(dtype), _occ_slab(slab)
+    O = _lib.load_occupancy()
+    try:
+        dev, n_src, n, R = _source(depth, offsets, headers, index, R, layout)
+        _shaped("max_l", max_l, (n,), torch.float32, dev)
+        _shaped("mid_p", mid_p, (n, 3), torch.float32, dev)
+        if xforms is not None:
+            _shaped("xforms", xforms, (n, 24), torch.float64, dev)
+        occ = _out("out", out, (n, 1, R, R, R), dtype, dev)
+    except TypeError as e:   # a bad argument of this entry is a ValueError whatever is wrong with it
+        raise ValueError(str(e)) from None
+    status = _out("status", None, (n,), torch.int32, dev) if want_status else None
+    if n:
+        _call(dev, O.tsdf_occupancy_hip,
+              _src_head(depth, offsets, headers, n_src, index, n, R) + _cam5(cam) +
+              [lay, code, hint, None, _ptr(xforms), max_l.data_ptr(), mid_p.data_ptr(), occ.data_ptr(), _ptr(status)], 16)
+    return occ, status
+
+
+def occupancy_volumes(depth: torch.Tensor, offsets: torch.Tensor, headers: torch.Tensor, max_l: torch.Tensor,
+                      mid_p: torch.Tensor, res: int = 32, layout: str = "czyx", dtype: torch.dtype = torch.float32,
+                      cam: Optional[_lib.TsdfCam] = None, xforms: Optional[torch.Tensor] = None,
+                      index: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None, slab: int = 0):
+    """One-channel occupancy volumes, the input of V2V-PoseNet and its family: a voxel is 1 if a point of the frame's
+    back-projected cloud falls inside it, else 0 (``tsdf_occupancy_hip`` of libtsdf_occupancy.so; include/tsdf_occupancy.h
+    has the contract).  A scatter — every pixel is pushed into its voxel — through a bit mask in LDS, one launch.
+
+    depth / offsets / headers   the n_src source frames, as for :func:`voxelize`
+    max_l   float32[n] on the GPU   }  the cube of ANY placement, per BATCH POSITION: ``aabb``'s, ``map_grids``'s (with the
+    mid_p   float32[n,3]            }  same ``xforms``), ``cloud_grids``'s, the fixed cube of a :class:`HandCrops`.  The grid
+            is that cube cut into ``res`` voxels a side, whatever resolution the placement itself was asked for: an 88^3
+            occupancy goes with a 32^3 TSDF of the same frame, and sits voxel for voxel on :func:`joint_heatmaps` at ``res``
+    dtype   torch.float32, torch.float16 or torch.bfloat16
+    cam     a :class:`TsdfCam` or None (the MSRA defaults); its five constants go to the entry by value
+    xforms  optional float64[n,24] on the GPU: one map per batch position, the points are mapped before they are binned
+    index   optional int64[n] on the GPU: batch position i takes source frame index[i] (repeats allowed; an entry outside
+            [0, n_src) gives that position status 2 and a zero volume).  Without it the batch is the n_src frames
+    out     optional preallocated ``dtype[n,1,R,R,R]`` (a contiguous view of a larger buffer will do) to write into
+    slab    0, or slices of the slowest axis per workgroup (clamped to what 64 KiB of LDS hold); the result never depends
+            on it
+    Returns ``(occ dtype[n,1,R,R,R], status int32[n])``.  A bad header (2) or an unusable ``max_l`` / ``mid_p`` row (1:
+    ``max_l`` not positive, anything non-finite) gives a zero volume; a frame without a valid pixel gets a zero volume with
+    status 0.  Every bad argument is a ValueError before anything is launched.  One launch on the current stream, no
+    synchronisation."""
+    return _occupancy(depth, offsets, headers, max_l, mid_p, res, layout, dtype, cam, xforms, index, out, slab, True)
+
+
+def voxelize_occupancy(depth: torch.Tensor, offsets: torch.Tensor, headers: torch.Tensor, res: int = 32,
+                       layout: str = "czyx", dtype: torch.dtype = torch.float32, cam: Optional[_lib.TsdfCam] = None,
+                       xforms: Optional[torch.Tensor] = None) -> TsdfBatch:
+    """:func:`occupancy_volumes` on the cloud's own cube: :func:`aabb` places it — :func:`map_grids` under ``xforms`` —
+    and the occupancy pass bins the points into ``res`` voxels a side.  Two launches, nothing on the host in between.
+    ``max_l`` / ``mid_p`` / ``status`` are the placement's, bit for bit those of :func:`voxelize` (:func:`voxelize_aug`);
+    ``tsdf`` holds the occupancy, ``dtype[n,1,R,R,R]``.  (For the fixed cube of :func:`locate_hands` call
+    :func:`occupancy_volumes` on the :class:`HandCrops`' ``max_l`` / ``mid_p``.)"""
+    _heat_res(res), _heat_layout(layout), _heat_dtype(dtype)   # judged before the placement is launched
+    if xforms is None:
+        place = _place_aabb(depth, offsets, headers, res, cam, rows=False)
+    else:
+        place = map_grids(depth, offsets, headers, xforms, res=res, cam=cam)
+    occ, _ = _occupancy(depth, offsets, headers, place.max_l, place.mid_p, res, layout, dtype, cam, xforms, None, None, 0,
+                        False)
+    return TsdfBatch(occ, place.max_l, place.mid_p, place.status)
