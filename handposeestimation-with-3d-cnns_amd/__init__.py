@@ -55,6 +55,12 @@ Occupancy volumes:                       occupancy_volumes (the one-channel inpu
                                          of any placement, every pixel scattered into a bit mask in LDS:
                                          libtsdf_occupancy.so, include/tsdf_occupancy.h), voxelize_occupancy (placed on the
                                          cloud's own cube), AugmentedStep(occupancy=...)
+Farthest-point sampled clouds:           farthest_points (the input of a point network — HandPointNet and its family — from
+                                         a packed crop, optionally under per-frame maps such as obb_xforms': one workgroup
+                                         per frame runs the whole chain of arg-max reductions on chip: libtsdf_fps.so,
+                                         include/tsdf_fps.h), farthest_of (of clouds that exist already), FpsBatch, fps_plan,
+                                         FPS_RESIDENT_POINTS (the candidates a frame may have without a workspace),
+                                         AugmentedStep(fps=...)
 """
 from . import _lib  # noqa: F401
 from ._lib import TsdfCam, TsdfError, default_cam  # noqa: F401
@@ -68,7 +74,8 @@ from .voxelize import (AabbBatch, AugmentedStep, CloudGridBatch, MapGridBatch, O
                        map_grids, voxelize_aug_lowp, voxelize_map_grid_lowp, MapStepBatch, compose_xforms, map_step_head,
                        HandCrops, locate_hands, voxelize_frames, voxelize_accurate, voxelize_grid_accurate,
                        voxelize_aug_accurate, voxelize_map_grid_accurate, HeatmapJoints, heatmap_joints, joint_heatmaps,
-                       heatmap_mse_loss, soft_argmax_joints, occupancy_volumes, voxelize_occupancy)
+                       heatmap_mse_loss, soft_argmax_joints, occupancy_volumes, voxelize_occupancy, FpsBatch,
+                       farthest_points, farthest_of, fps_plan)
 from .pca import JointPCA, fit_joint_pca  # noqa: F401
 from . import augment, dataset, export, packing, pca, shard, synth  # noqa: F401
 from .dataset import MSRA_Dataset, MSRADepthDataset, ResidentLoader, VoxelBatch, VoxelLoader  # noqa: F401
@@ -87,4 +94,11 @@ __all__ = ["voxelize", "voxelize_labels", "voxelize_indexed", "ResidentLoader", 
            "voxelize_aug_lowp", "compose_xforms", "map_step_head", "MapStepBatch", "locate_hands", "voxelize_frames",
            "HandCrops", "voxelize_grid_accurate", "voxelize_accurate", "voxelize_map_grid_accurate", "voxelize_aug_accurate",
            "joint_heatmaps", "heatmap_joints", "HeatmapJoints", "heatmap_mse_loss", "soft_argmax_joints",
-           "occupancy_volumes", "voxelize_occupancy"]
+           "occupancy_volumes", "voxelize_occupancy", "farthest_points", "farthest_of", "FpsBatch", "fps_plan",
+           "FPS_RESIDENT_POINTS"]
+
+
+def __getattr__(name):
+    if name == "FPS_RESIDENT_POINTS":   # from tsdf_fps_plan, once somebody asks (the library is loaded then, not at import)
+        return fps_plan()[0]
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -166,6 +166,16 @@ OCCUPANCY_LIB_PATH = os.path.join(_HERE, "libtsdf_occupancy.so")
 OCCUPANCY_VERSION = 1
 OCCUPANCY_LDS_CAP = 64 * 1024   # bytes of bit mask per workgroup (kOccLdsCap of csrc/occupancy_host.inc)
 
+# The library of include/tsdf_fps.h (make -C csrc fps): farthest-point sampled clouds from a packed crop or from a cloud,
+# one workgroup per batch position running the chain of arg-max reductions on chip.  A binary of its own; its row is _FPS
+# below, outside _EXTS like _HEATMAP.
+FPS_LIB_PATH = os.path.join(_HERE, "libtsdf_fps.so")
+FPS_VERSION = 1
+TSDF_FPS_FRAME_OVER_CAPACITY = 3   # per-position status of include/tsdf_fps.h, next to TSDF_FRAME_*
+FPS_MAX_POINTS = 65536             # TSDF_FPS_MAX_POINTS
+TSDF_FPS_F32 = 0                   # the element types of tsdf_fps_points_hip's cloud
+TSDF_FPS_F64 = 1
+
 
 class _Ext(NamedTuple):
     """A row of the extension table: libtsdf_<name>.so, built by ``make -C csrc <name>`` from include/tsdf_<name>.h."""
@@ -283,6 +293,18 @@ _OCCUPANCY = _Ext(OCCUPANCY_LIB_PATH, "tsdf_occupancy_version", OCCUPANCY_VERSIO
     # value), layout, dtype, slab_hint, stream, xforms, max_l, mid_p, occ, status
     "tsdf_occupancy_hip": [_vp, _i64, _vp, _vp, _i64, _vp, _i, _i, ctypes.c_double, ctypes.c_double, ctypes.c_double,
                            ctypes.c_float, ctypes.c_float, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp],
+})
+
+# libtsdf_fps.so's row, of the same type and loaded by the same code (load_fps)
+_FPS = _Ext(FPS_LIB_PATH, "tsdf_fps_version", FPS_VERSION, {
+    # M, capacity, form_hint, resident_cap, work_bytes, lds_bytes (an int, an int64 and an int in host memory)
+    "tsdf_fps_plan": [_i, _i64, _i, ctypes.POINTER(_i), ctypes.POINTER(_i64), ctypes.POINTER(_i)],
+    # depth, depth_len, offsets, headers, n_src, index, n, M, focal, cx, cy, invalid_eps, trunc_voxels (the camera by
+    # value), capacity, form_hint, stream, xforms, work, points, pixel, radius2, count, status
+    "tsdf_fps_hip": [_vp, _i64, _vp, _vp, _i64, _vp, _i, _i, ctypes.c_double, ctypes.c_double, ctypes.c_double,
+                     ctypes.c_float, ctypes.c_float, _i64, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+    # cloud, dtype, n, P, M, capacity, form_hint, stream, work, points, pixel, radius2, count, status
+    "tsdf_fps_points_hip": [_vp, _i, _i, _i64, _i, _i64, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
 })
 
 _lib = None
@@ -413,6 +435,11 @@ def load_heatloss():
 def load_occupancy():
     """libtsdf_occupancy.so, the library of include/tsdf_occupancy.h (its row is ``_OCCUPANCY``)."""
     return _load_row("occupancy", _OCCUPANCY)
+
+
+def load_fps():
+    """libtsdf_fps.so, the library of include/tsdf_fps.h (its row is ``_FPS``)."""
+    return _load_row("fps", _FPS)
 
 
 def load_augment():

@@ -699,16 +699,29 @@ class AugmentedStep:
     (float32 unless ``dtype`` says otherwise; ``res`` is the occupancy's own resolution, in the step's ``layout``).  It is
     one more launch at the very end of the same linear sequence — :func:`occupancy_volumes` of the step's own ``index``,
     ``xforms``, ``out.max_l`` and ``out.mid_p`` — needs no ``gt`` and combines with every option above.  ``step`` returns
-    exactly what it returns without it; ``occupancy=None`` issues exactly the launches listed above."""
+    exactly what it returns without it; ``occupancy=None`` issues exactly the launches listed above.
+
+    ``fps=(M,)``: the step also writes the input of a point network, ``M`` farthest-point samples of each frame's cloud
+    under the step's maps, into static buffers ``self.cloud`` float32[n, M, 3], ``self.cloud_pixel`` int32[n, M],
+    ``self.cloud_count`` and ``self.cloud_status`` int32[n].  It is one more launch at the very end of the same linear
+    sequence — :func:`farthest_points` of the step's own ``index`` and ``xforms``, in the resident form (a frame of more
+    than ``FPS_RESIDENT_POINTS`` candidates gets status 3) — needs no ``gt`` and combines with every option above.
+    ``step`` returns exactly what it returns without it; ``fps=None`` issues exactly the launches listed above."""
 
     def __init__(self, depth: torch.Tensor, offsets: torch.Tensor, headers: torch.Tensor, n: int,
                  gt: Optional[torch.Tensor] = None, centres: Optional[torch.Tensor] = None, res: int = 32,
                  layout: str = "czyx", clamp: bool = True, cam: Optional[_lib.TsdfCam] = None, graph: bool = True,
                  dtype: Optional[torch.dtype] = None, base: Optional[torch.Tensor] = None, fused_head: bool = False,
-                 heatmap: Optional[tuple] = None, occupancy: Optional[tuple] = None, tsdf: str = "projective"):
+                 heatmap: Optional[tuple] = None, fps: Optional[tuple] = None, occupancy: Optional[tuple] = None,
+                 tsdf: str = "projective"):
         self.accurate = _tsdf_kind(tsdf)
         self.heat = self._heatmap = None
         self.occ = self._occupancy = None
+        self.cloud = self.cloud_pixel = self.cloud_count = self.cloud_status = self._fps = None
+        if fps is not None:
+            if not isinstance(fps, (tuple, list)) or len(fps) != 1:
+                raise ValueError("fps must be (M,)")
+            self._fps = _fps_points(fps[0])
         if occupancy is not None:
             if not isinstance(occupancy, (tuple, list)) or len(occupancy) not in (1, 2):
                 raise ValueError("occupancy must be (res,) or (res, dtype)")
@@ -780,6 +793,9 @@ class AugmentedStep:
         if self._occupancy is not None:   # the static occupancy volume, at its own resolution
             ores, odtype = self._occupancy
             self.occ = torch.empty((n, 1, ores, ores, ores), dtype=odtype, device=dev)
+        if self._fps is not None:   # the static sampled clouds
+            self._cloud = _fps_out(None, n, self._fps, dev, radius2=False)
+            self.cloud, self.cloud_pixel, _, self.cloud_count, self.cloud_status = self._cloud
         if self._head:   # what map_step_head writes into: the object's own buffers
             g = self._grid if placed else MapGridBatch(None, None, None, None)
             self._head_out = MapStepBatch(self.xforms, g.grid, g.max_l, g.mid_p, g.status, self.gt_aug, self.gt_nor)
@@ -815,6 +831,9 @@ class AugmentedStep:
             ores, odtype = self._occupancy
             _occupancy(d, o, h, self.out.max_l, self.out.mid_p, ores, self.layout, odtype, self.cam, self.xforms, self.index,
                        self.occ, 0, False)
+        if self._fps is not None:   # and the last: the same points, farthest-point sampled
+            d, o, h = self._pack_args
+            _fps_crop(d, o, h, self._fps, self.cam, self.xforms, self.index, None, None, self._cloud, 0)
 
     def _step_launches(self):
         d, o, h = self._pack_args
@@ -2141,3 +2160,155 @@ def voxelize_occupancy(depth: torch.Tensor, offsets: torch.Tensor, headers: torc
     occ, _ = _occupancy(depth, offsets, headers, place.max_l, place.mid_p, res, layout, dtype, cam, xforms, None, None, 0,
                         False)
     return TsdfBatch(occ, place.max_l, place.mid_p, place.status)
+
+
+class FpsBatch(NamedTuple):
+    points: torch.Tensor   # float32[n, M, 3]  the sampled points, in sampling order
+    pixel: torch.Tensor    # int32[n, M]       each sample's rank: its index in the crop (row-major in the bbox) or its row
+    radius2: Optional[torch.Tensor]   # float32[n, M]  the squared distance at which each sample was chosen (row 0: +inf)
+    count: torch.Tensor    # int32[n]  candidates of the frame
+    status: torch.Tensor   # int32[n]  _lib.TSDF_FRAME_*, or _lib.TSDF_FPS_FRAME_OVER_CAPACITY (3)
+
+
+def _fps_points(points) -> int:
+    """``points`` as the M the entries take: an int in 1..65536, else a ValueError."""
+    if isinstance(points, bool) or not isinstance(points, int) or not 1 <= points <= _lib.FPS_MAX_POINTS:
+        raise ValueError(f"points must be an int in 1..{_lib.FPS_MAX_POINTS}, got {points!r}")
+    return points
+
+
+def _fps_form(form) -> int:
+    if isinstance(form, bool) or not isinstance(form, int) or form not in (0, 1):
+        raise ValueError(f"form must be 0 (the library's choice) or 1 (streaming wherever a workspace allows), got {form!r}")
+    return int(form)
+
+
+def fps_plan(points: int = 1024, capacity: int = 0, form: int = 0) -> tuple:
+    """``tsdf_fps_plan`` (host code only): ``(resident_cap, work_bytes per batch position, lds_bytes)`` of a call with
+    ``points`` samples and a workspace of ``capacity`` candidates per position."""
+    M, hint = _fps_points(points), _fps_form(form)
+    if isinstance(capacity, bool) or not isinstance(capacity, int) or not 0 <= capacity < 2 ** 31:
+        raise ValueError(f"capacity must be an int in 0..2^31-1, got {capacity!r}")
+    cap, work, lds = ctypes.c_int(), ctypes.c_int64(), ctypes.c_int()
+    _lib.check(_lib.load_fps().tsdf_fps_plan(M, capacity, hint, cap, work, lds), "tsdf_fps_plan")
+    return cap.value, work.value, lds.value
+
+
+def _fps_out(out, n, M, dev, radius2=True) -> FpsBatch:
+    """The outputs of a sampling call: allocated (``radius2``: with that field), or the caller's ``out`` validated field by
+    field — a :class:`FpsBatch` whose ``radius2`` may be None, which the launch then does not write."""
+    fields = (("points", (n, M, 3), torch.float32), ("pixel", (n, M), torch.int32), ("radius2", (n, M), torch.float32),
+              ("count", (n,), torch.int32), ("status", (n,), torch.int32))
+    if out is None:
+        return FpsBatch(*[_out(name, None, shape, dtype, dev) if radius2 or name != "radius2" else None
+                          for name, shape, dtype in fields])
+    if not isinstance(out, FpsBatch):
+        raise ValueError("out must be an FpsBatch")
+    for name, shape, dtype in fields:
+        if name != "radius2" or out.radius2 is not None:
+            _shaped("out." + name, getattr(out, name), shape, dtype, dev)
+    return out
+
+
+def _fps_work(n, capacity, work, dev):
+    """``(capacity, work)`` as the entries take them: (0, None) without a workspace; with ``capacity`` alone the workspace
+    is allocated; a caller's ``work`` float32[n, capacity, 4] is validated (and ``capacity``, if given too, must be its)."""
+    if capacity is not None and (isinstance(capacity, bool) or not isinstance(capacity, int) or not 1 <= capacity < 2 ** 31):
+        raise ValueError(f"capacity must be None or an int in 1..2^31-1, got {capacity!r}")
+    if work is None:
+        if capacity is None:
+            return 0, None
+        return capacity, torch.empty((n, capacity, 4), dtype=torch.float32, device=dev)
+    _dev_check("work", work, torch.float32, dev)
+    if work.dim() != 3 or work.shape[0] != n or work.shape[1] < 1 or work.shape[2] != 4:
+        raise ValueError(f"work must have shape [{n}, capacity, 4]")
+    if capacity is not None and capacity != work.shape[1]:
+        raise ValueError(f"capacity {capacity} is not work's, {work.shape[1]}")
+    if work.data_ptr() % 16:
+        raise ValueError("work must be 16-byte aligned")
+    return int(work.shape[1]), work
+
+
+def _fps_crop(depth, offsets, headers, points, cam, xforms, index, capacity, work, out, form) -> FpsBatch:
+    """:func:`farthest_points`; given ``out`` (and ``work``, or no ``capacity``) the call allocates nothing."""
+    M, hint = _fps_points(points), _fps_form(form)
+    F = _lib.load_fps()
+    try:
+        dev, n_src, n, _ = _source(depth, offsets, headers, index, None, "czyx")
+        if xforms is not None:
+            _shaped("xforms", xforms, (n, 24), torch.float64, dev)
+        cap, work = _fps_work(n, capacity, work, dev)
+        out = _fps_out(out, n, M, dev)
+    except TypeError as e:   # a bad argument of this entry is a ValueError whatever is wrong with it
+        raise ValueError(str(e)) from None
+    if n:
+        _call(dev, F.tsdf_fps_hip,
+              _src_head(depth, offsets, headers, n_src, index, n, M) + _cam5(cam) +
+              [cap, hint, None, _ptr(xforms), _ptr(work), out.points.data_ptr(), out.pixel.data_ptr(), _ptr(out.radius2),
+               out.count.data_ptr(), out.status.data_ptr()], 15)
+    return out
+
+
+def farthest_points(depth: torch.Tensor, offsets: torch.Tensor, headers: torch.Tensor, points: int = 1024,
+                    cam: Optional[_lib.TsdfCam] = None, xforms: Optional[torch.Tensor] = None,
+                    index: Optional[torch.Tensor] = None, capacity: Optional[int] = None,
+                    work: Optional[torch.Tensor] = None, out: Optional[FpsBatch] = None, form: int = 0) -> FpsBatch:
+    """Farthest-point sampled clouds, the input of a point network (HandPointNet, Point-to-Point Regression PointNet):
+    ``points`` points of each frame's back-projected cloud, each the one farthest from all chosen before it
+    (``tsdf_fps_hip`` of libtsdf_fps.so; include/tsdf_fps.h has the contract).  One launch, one workgroup per frame, the
+    whole chain of ``points - 1`` arg-max reductions on chip.
+
+    depth / offsets / headers   the n_src source frames, as for :func:`voxelize`
+    points  M, 1..65536.  Sample 0 is the first valid pixel of the crop; the first k rows of an M-point result ARE the
+            k-point result, so the 1024 / 512 / 128 hierarchy of a point network is ``fps.points[:, :512]`` ...
+    cam     a :class:`TsdfCam` or None (the MSRA defaults); its five constants go to the entry by value
+    xforms  optional float64[n,24] on the GPU: one map per batch position; the points are mapped in float64, rounded once
+            to float32 and sampled in the mapped frame
+    index   optional int64[n] on the GPU: batch position i takes source frame index[i] (repeats allowed; an entry outside
+            [0, n_src) gives that position status 2).  Without it the batch is the n_src frames
+    capacity  None: the resident form only — up to ``FPS_RESIDENT_POINTS`` valid pixels per frame, nothing allocated
+            beyond the outputs; a frame with more gets status 3.  An int: frames above the resident cap stream through a
+            workspace of that many candidates per frame, float32[n, capacity, 4], which the call allocates
+    work    that workspace from the caller, for reuse and for graphs (``capacity`` is then its second extent)
+    out     optional :class:`FpsBatch` to write into; its ``radius2`` may be None
+    form    0, or 1: the streaming form wherever the workspace allows.  The result never depends on it
+    Returns :class:`FpsBatch`.  A bad header (2), a frame without a valid pixel (1) and a frame over capacity (3, ``count``
+    still true) give zero points, ``pixel`` -1 and ``radius2`` 0.  A frame of fewer than ``points`` valid pixels repeats
+    its row 0.  Every bad argument is a ValueError before anything is launched.  Runs on the current stream, no
+    synchronisation.
+
+    The HandPointNet input, three launches and nothing on the host in between::
+
+        obb = obb_xforms(depth, offsets, headers)
+        fps = farthest_points(depth, offsets, headers, 1024, xforms=obb.xforms)
+        place = map_grids(depth, offsets, headers, obb.xforms)          # the OBB frame's cube
+        cloud = normalize_joints(fps.points.view(n, -1), place.max_l, place.mid_p).view(n, 1024, 3)
+    """
+    return _fps_crop(depth, offsets, headers, points, cam, xforms, index, capacity, work, out, form)
+
+
+def farthest_of(cloud: torch.Tensor, points: int = 1024, capacity: Optional[int] = None,
+                work: Optional[torch.Tensor] = None, out: Optional[FpsBatch] = None, form: int = 0) -> FpsBatch:
+    """:func:`farthest_points` of clouds that exist already (``tsdf_fps_points_hip``): ``cloud`` is float32 or
+    float64[n, P, 3] on the GPU — :func:`point_clouds`' output, or a network's own set-abstraction level.  float64 is
+    rounded once to float32; a row with a non-finite coordinate is no candidate; ``pixel`` holds row numbers.  The other
+    arguments and the returns are :func:`farthest_points`'s (status 2 does not occur)."""
+    M, hint = _fps_points(points), _fps_form(form)
+    F = _lib.load_fps()
+    if not isinstance(cloud, torch.Tensor) or cloud.dtype not in (torch.float32, torch.float64):
+        raise ValueError("cloud must be a float32 or float64 torch.Tensor")
+    try:
+        _dev_check("cloud", cloud, cloud.dtype)
+        if cloud.dim() != 3 or cloud.shape[2] != 3 or not 1 <= cloud.shape[1] < 2 ** 31:
+            raise ValueError("cloud must have shape [n, P, 3] with P >= 1")
+        dev, n, P = cloud.device, int(cloud.shape[0]), int(cloud.shape[1])
+        cap, work = _fps_work(n, capacity, work, dev)
+        out = _fps_out(out, n, M, dev)
+    except TypeError as e:
+        raise ValueError(str(e)) from None
+    if n:
+        code = _lib.TSDF_FPS_F64 if cloud.dtype is torch.float64 else _lib.TSDF_FPS_F32
+        _call(dev, F.tsdf_fps_points_hip,
+              [cloud.data_ptr(), code, n, P, M, cap, hint, None, _ptr(work), out.points.data_ptr(), out.pixel.data_ptr(),
+               _ptr(out.radius2), out.count.data_ptr(), out.status.data_ptr()], 7)
+    return out
