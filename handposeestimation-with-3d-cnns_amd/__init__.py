@@ -61,6 +61,12 @@ Farthest-point sampled clouds:           farthest_points (the input of a point n
                                          include/tsdf_fps.h), farthest_of (of clouds that exist already), FpsBatch, fps_plan,
                                          FPS_RESIDENT_POINTS (the candidates a frame may have without a workspace),
                                          AugmentedStep(fps=...)
+kNN grouping and surface normals:        knn_groups (for every centre of a set-abstraction level its k nearest neighbours in
+                                         the sampled cloud, the centres a prefix of the cloud: a top-K selection per query
+                                         over a cloud resident in LDS, ties to the lowest row: libtsdf_group.so,
+                                         include/tsdf_group.h), point_normals (PCA normals over the same neighbours, turned
+                                         towards the viewpoint, with the surface variation), KnnBatch, NormalBatch,
+                                         group_plan, AugmentedStep(fps=..., groups=..., normals=...)
 """
 from . import _lib  # noqa: F401
 from ._lib import TsdfCam, TsdfError, default_cam  # noqa: F401
@@ -75,7 +81,8 @@ from .voxelize import (AabbBatch, AugmentedStep, CloudGridBatch, MapGridBatch, O
                        HandCrops, locate_hands, voxelize_frames, voxelize_accurate, voxelize_grid_accurate,
                        voxelize_aug_accurate, voxelize_map_grid_accurate, HeatmapJoints, heatmap_joints, joint_heatmaps,
                        heatmap_mse_loss, soft_argmax_joints, occupancy_volumes, voxelize_occupancy, FpsBatch,
-                       farthest_points, farthest_of, fps_plan)
+                       farthest_points, farthest_of, fps_plan, KnnBatch, NormalBatch, knn_groups,
+                       point_normals, group_plan)
 from .pca import JointPCA, fit_joint_pca  # noqa: F401
 from . import augment, dataset, export, packing, pca, shard, synth  # noqa: F401
 from .dataset import MSRA_Dataset, MSRADepthDataset, ResidentLoader, VoxelBatch, VoxelLoader  # noqa: F401
@@ -95,7 +102,7 @@ __all__ = ["voxelize", "voxelize_labels", "voxelize_indexed", "ResidentLoader", 
            "HandCrops", "voxelize_grid_accurate", "voxelize_accurate", "voxelize_map_grid_accurate", "voxelize_aug_accurate",
            "joint_heatmaps", "heatmap_joints", "HeatmapJoints", "heatmap_mse_loss", "soft_argmax_joints",
            "occupancy_volumes", "voxelize_occupancy", "farthest_points", "farthest_of", "FpsBatch", "fps_plan",
-           "FPS_RESIDENT_POINTS"]
+           "FPS_RESIDENT_POINTS", "knn_groups", "point_normals", "KnnBatch", "NormalBatch", "group_plan"]
 
 
 def __getattr__(name):

@@ -176,6 +176,15 @@ FPS_MAX_POINTS = 65536             # TSDF_FPS_MAX_POINTS
 TSDF_FPS_F32 = 0                   # the element types of tsdf_fps_points_hip's cloud
 TSDF_FPS_F64 = 1
 
+# The library of include/tsdf_group.h (make -C csrc group): kNN grouping and PCA surface normals of sampled clouds, a top-K
+# selection per query over a cloud resident in LDS.  A binary of its own; its row is _GROUP below, outside _EXTS like
+# _HEATMAP.
+GROUP_LIB_PATH = os.path.join(_HERE, "libtsdf_group.so")
+GROUP_VERSION = 1
+GROUP_MAX_CLOUD = 12288            # TSDF_GROUP_MAX_CLOUD: rows of a cloud, the sampler's resident cap
+GROUP_MAX_K = 128                  # TSDF_GROUP_MAX_K
+GROUP_SWEEPS = 8                   # TSDF_GROUP_SWEEPS: the fixed number of Jacobi sweeps of the normals
+
 
 class _Ext(NamedTuple):
     """A row of the extension table: libtsdf_<name>.so, built by ``make -C csrc <name>`` from include/tsdf_<name>.h."""
@@ -305,6 +314,16 @@ _FPS = _Ext(FPS_LIB_PATH, "tsdf_fps_version", FPS_VERSION, {
                      ctypes.c_float, ctypes.c_float, _i64, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     # cloud, dtype, n, P, M, capacity, form_hint, stream, work, points, pixel, radius2, count, status
     "tsdf_fps_points_hip": [_vp, _i, _i, _i64, _i, _i64, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+})
+
+# libtsdf_group.so's row, of the same type and loaded by the same code (load_group)
+_GROUP = _Ext(GROUP_LIB_PATH, "tsdf_group_version", GROUP_VERSION, {
+    # P, C, K, lds_bytes, queries_per_group, groups_per_position (three ints in host memory)
+    "tsdf_group_plan": [_i, _i, _i, ctypes.POINTER(_i), ctypes.POINTER(_i), ctypes.POINTER(_i)],
+    # points, pitch, query, status_in, n, P, C, K, stream, index, dist2, offset, status
+    "tsdf_knn_hip": [_vp, _i64, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp],
+    # points, pitch, query, status_in, view, n, P, C, K, stream, normals, curvature, status
+    "tsdf_normals_hip": [_vp, _i64, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp],
 })
 
 _lib = None
@@ -440,6 +459,11 @@ def load_occupancy():
 def load_fps():
     """libtsdf_fps.so, the library of include/tsdf_fps.h (its row is ``_FPS``)."""
     return _load_row("fps", _FPS)
+
+
+def load_group():
+    """libtsdf_group.so, the library of include/tsdf_group.h (its row is ``_GROUP``)."""
+    return _load_row("group", _GROUP)
 
 
 def load_augment():

@@ -706,14 +706,23 @@ class AugmentedStep:
     ``self.cloud_count`` and ``self.cloud_status`` int32[n].  It is one more launch at the very end of the same linear
     sequence — :func:`farthest_points` of the step's own ``index`` and ``xforms``, in the resident form (a frame of more
     than ``FPS_RESIDENT_POINTS`` candidates gets status 3) — needs no ``gt`` and combines with every option above.
-    ``step`` returns exactly what it returns without it; ``fps=None`` issues exactly the launches listed above."""
+    ``step`` returns exactly what it returns without it; ``fps=None`` issues exactly the launches listed above.
+
+    ``groups=((C, K), ...)`` and ``normals=k`` (both need ``fps=(M,)``): the step also writes what a point network reads
+    next to the sampled cloud.  ``normals=k`` is one more launch after the sampling — :func:`point_normals` of
+    ``self.cloud`` over ``k`` neighbours, the viewpoint the camera centre under the step's maps (one small copy takes it
+    out of ``self.xforms``) — into the static :class:`NormalBatch` ``self.normals``.  ``groups`` is one launch per
+    set-abstraction level after that — :func:`knn_groups` with ``offsets`` — into the static :class:`KnnBatch` es
+    ``self.groups[l]``: level 0 groups the ``M`` sampled rows around their first ``C_0``, level ``l`` the first
+    ``C_{l-1}`` rows around their first ``C_l``.  Positions the sampling gave a status are not read.  ``step`` returns
+    exactly what it returns without them; without the two arguments the step issues exactly the launches listed above."""
 
     def __init__(self, depth: torch.Tensor, offsets: torch.Tensor, headers: torch.Tensor, n: int,
                  gt: Optional[torch.Tensor] = None, centres: Optional[torch.Tensor] = None, res: int = 32,
                  layout: str = "czyx", clamp: bool = True, cam: Optional[_lib.TsdfCam] = None, graph: bool = True,
                  dtype: Optional[torch.dtype] = None, base: Optional[torch.Tensor] = None, fused_head: bool = False,
-                 heatmap: Optional[tuple] = None, fps: Optional[tuple] = None, occupancy: Optional[tuple] = None,
-                 tsdf: str = "projective"):
+                 heatmap: Optional[tuple] = None, groups: Optional[tuple] = None, normals: Optional[int] = None,
+                 fps: Optional[tuple] = None, occupancy: Optional[tuple] = None, tsdf: str = "projective"):
         self.accurate = _tsdf_kind(tsdf)
         self.heat = self._heatmap = None
         self.occ = self._occupancy = None
@@ -722,6 +731,24 @@ class AugmentedStep:
             if not isinstance(fps, (tuple, list)) or len(fps) != 1:
                 raise ValueError("fps must be (M,)")
             self._fps = _fps_points(fps[0])
+        self.groups = self.normals = self._groups = self._normals_k = None
+        if groups is not None or normals is not None:   # what a point network reads next to the sampled cloud
+            if self._fps is None:
+                raise ValueError("groups and normals need fps=(M,): they read the step's sampled cloud")
+            if normals is not None:
+                self._normals_k = _group_k(normals)
+            if groups is not None:
+                if not isinstance(groups, (tuple, list)) or not groups or \
+                        not all(isinstance(g, (tuple, list)) and len(g) == 2 for g in groups):
+                    raise ValueError("groups must be ((C, K), ...): one pair per set-abstraction level")
+                if self._fps > _lib.GROUP_MAX_CLOUD:
+                    raise ValueError(f"groups read a cloud of at most {_lib.GROUP_MAX_CLOUD} points")
+                rows, self._groups = self._fps, []
+                for C, K in groups:   # level l's cloud is the first C_{l-1} rows, level 0's the M sampled rows
+                    self._groups.append((rows, _group_count("C", C, rows), _group_k(K)))
+                    rows = C
+            if self._normals_k is not None and self._fps > _lib.GROUP_MAX_CLOUD:
+                raise ValueError(f"normals read a cloud of at most {_lib.GROUP_MAX_CLOUD} points")
         if occupancy is not None:
             if not isinstance(occupancy, (tuple, list)) or len(occupancy) not in (1, 2):
                 raise ValueError("occupancy must be (res,) or (res, dtype)")
@@ -796,6 +823,15 @@ class AugmentedStep:
         if self._fps is not None:   # the static sampled clouds
             self._cloud = _fps_out(None, n, self._fps, dev, radius2=False)
             self.cloud, self.cloud_pixel, _, self.cloud_count, self.cloud_status = self._cloud
+        if self._groups is not None:   # the static groups, one KnnBatch per level
+            self.groups = [_group_out(KnnBatch, None, (("index", (n, C, K), torch.int32), ("dist2", (n, C, K), torch.float32),
+                                                       ("offsets", (n, C, K, 3), torch.float32), ("status", (n,), torch.int32)),
+                                      {}, dev) for _, C, K in self._groups]
+        if self._normals_k is not None:   # the static normals, and the viewpoint under the step's maps
+            M = self._fps
+            self.normals = _group_out(NormalBatch, None, (("normals", (n, M, 3), torch.float32), ("curvature", (n, M), torch.float32),
+                                                          ("status", (n,), torch.int32)), {}, dev)
+            self._view = torch.empty((n, 3), dtype=torch.float64, device=dev)
         if self._head:   # what map_step_head writes into: the object's own buffers
             g = self._grid if placed else MapGridBatch(None, None, None, None)
             self._head_out = MapStepBatch(self.xforms, g.grid, g.max_l, g.mid_p, g.status, self.gt_aug, self.gt_nor)
@@ -834,6 +870,12 @@ class AugmentedStep:
         if self._fps is not None:   # and the last: the same points, farthest-point sampled
             d, o, h = self._pack_args
             _fps_crop(d, o, h, self._fps, self.cam, self.xforms, self.index, None, None, self._cloud, 0)
+        if self._normals_k is not None:   # after it: a normal per sampled point, seen from the camera under the step's maps
+            _normals(self.cloud, self._normals_k, None, self.cloud_status, _view_of(self.xforms, self.n, self._view), True,
+                     self.normals)
+        if self._groups is not None:   # and the levels' groups, each level's cloud a prefix of the sampled rows
+            for (rows, C, K), out in zip(self._groups, self.groups):
+                _knn(self.cloud[:, :rows], K, C, self.cloud_status, True, True, out)
 
     def _step_launches(self):
         d, o, h = self._pack_args
@@ -2312,3 +2354,190 @@ def farthest_of(cloud: torch.Tensor, points: int = 1024, capacity: Optional[int]
               [cloud.data_ptr(), code, n, P, M, cap, hint, None, _ptr(work), out.points.data_ptr(), out.pixel.data_ptr(),
                _ptr(out.radius2), out.count.data_ptr(), out.status.data_ptr()], 7)
     return out
+
+
+class KnnBatch(NamedTuple):
+    index: torch.Tensor              # int32[n, C, k]       each neighbour's row in the cloud, nearest first
+    dist2: Optional[torch.Tensor]    # float32[n, C, k]     its squared distance
+    offsets: Optional[torch.Tensor]  # float32[n, C, k, 3]  neighbour - query, the very differences that were measured
+    status: torch.Tensor             # int32[n]             _lib.TSDF_FRAME_*, or the input status copied through
+
+
+class NormalBatch(NamedTuple):
+    normals: torch.Tensor               # float32[n, C, 3]  unit normals turned towards the viewpoint
+    curvature: Optional[torch.Tensor]   # float32[n, C]     l0 / (l0 + l1 + l2), the surface variation
+    status: torch.Tensor                # int32[n]
+
+
+def _group_k(k) -> int:
+    if isinstance(k, bool) or not isinstance(k, int) or not 1 <= k <= _lib.GROUP_MAX_K:
+        raise ValueError(f"k must be an int in 1..{_lib.GROUP_MAX_K}, got {k!r}")
+    return k
+
+
+def _group_count(name, v, most) -> int:
+    if isinstance(v, bool) or not isinstance(v, int) or not 1 <= v <= most:
+        raise ValueError(f"{name} must be an int in 1..{most}, got {v!r}")
+    return v
+
+
+def group_plan(P: int, C: int, K: int) -> tuple:
+    """``tsdf_group_plan`` (host code only): ``(lds_bytes, queries per workgroup, workgroups per batch position)`` of a call
+    with clouds of ``P`` rows, ``C`` queries and ``K`` neighbours."""
+    P = _group_count("P", P, _lib.GROUP_MAX_CLOUD)
+    C = _group_count("C", C, 2 ** 31 - 1)
+    K = _group_k(K)
+    lds, per, groups = ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
+    _lib.check(_lib.load_group().tsdf_group_plan(P, C, K, lds, per, groups), "tsdf_group_plan")
+    return lds.value, per.value, groups.value
+
+
+def _group_in(cloud, queries, status):
+    """The input side both entries share, validated: ``(dev, n, P, pitch, C, query pointer, status pointer)``.  ``cloud``
+    is float32[n, P, 3], contiguous or the leading rows ``big[:, :P]`` of a contiguous tensor (read in place: ``pitch`` is
+    then ``big``'s rows)."""
+    if not isinstance(cloud, torch.Tensor) or cloud.dtype is not torch.float32:
+        raise ValueError("cloud must be a float32 torch.Tensor")
+    if cloud.dim() != 3 or cloud.shape[2] != 3 or not 1 <= cloud.shape[1] <= _lib.GROUP_MAX_CLOUD:
+        raise ValueError(f"cloud must have shape [n, P, 3] with P in 1..{_lib.GROUP_MAX_CLOUD}")
+    n, P = int(cloud.shape[0]), int(cloud.shape[1])
+    pitch = P
+    if cloud.is_contiguous():
+        _dev_check("cloud", cloud, torch.float32)
+    else:
+        s = cloud.stride()
+        if n == 0 or s[2] != 1 or s[1] != 3 or s[0] % 3 or s[0] < 3 * P:
+            raise ValueError("cloud must be contiguous, or the leading rows big[:, :P] of a contiguous tensor")
+        pitch = s[0] // 3
+        _dev_check("cloud", cloud[0, 0], torch.float32)
+    dev = cloud.device
+    if queries is None:
+        C, qptr = P, None
+    elif isinstance(queries, torch.Tensor):
+        _dev_check("queries", queries, torch.float32, dev)
+        if queries.dim() != 3 or queries.shape[0] != n or queries.shape[1] < 1 or queries.shape[2] != 3:
+            raise ValueError(f"queries must have shape [{n}, C, 3] with C >= 1")
+        C, qptr = int(queries.shape[1]), queries.data_ptr()
+    else:
+        C, qptr = _group_count("queries", queries, P), None   # the first C rows of the cloud itself
+    if status is not None:
+        _shaped("status", status, (n,), torch.int32, dev)
+    return dev, n, P, pitch, C, qptr, _ptr(status)
+
+
+def _group_out(cls, out, fields, optional, dev):
+    """The outputs as the NamedTuple ``cls``: allocated from their table (an ``optional`` field only where its flag is
+    set), or the caller's ``out`` validated field by field — its optional fields may be None, which the launch then does
+    not write."""
+    if out is None:
+        return cls(*[_out(name, None, shape, dtype, dev) if optional.get(name, True) else None for name, shape, dtype in fields])
+    if not isinstance(out, cls):
+        raise ValueError(f"out must be a {cls.__name__}")
+    for name, shape, dtype in fields:
+        if name not in optional or getattr(out, name) is not None:
+            _shaped("out." + name, getattr(out, name), shape, dtype, dev)
+    return out
+
+
+def _knn(cloud, k, queries, status, dist2, offsets, out) -> KnnBatch:
+    """:func:`knn_groups`; given ``out`` the call allocates nothing."""
+    K = _group_k(k)
+    G = _lib.load_group()
+    try:
+        dev, n, P, pitch, C, qptr, sptr = _group_in(cloud, queries, status)
+        out = _group_out(KnnBatch, out, (("index", (n, C, K), torch.int32), ("dist2", (n, C, K), torch.float32),
+                                         ("offsets", (n, C, K, 3), torch.float32), ("status", (n,), torch.int32)),
+                         {"dist2": bool(dist2), "offsets": bool(offsets)}, dev)
+    except TypeError as e:   # a bad argument of this entry is a ValueError whatever is wrong with it
+        raise ValueError(str(e)) from None
+    if n:
+        _call(dev, G.tsdf_knn_hip, [cloud.data_ptr(), pitch, qptr, sptr, n, P, C, K, None, out.index.data_ptr(),
+                                    _ptr(out.dist2), _ptr(out.offsets), out.status.data_ptr()], 8)
+    return out
+
+
+def knn_groups(cloud: torch.Tensor, k: int, queries=None, status: Optional[torch.Tensor] = None, dist2: bool = True,
+               offsets: bool = False, out: Optional[KnnBatch] = None) -> KnnBatch:
+    """kNN grouping, what a set-abstraction level of a point network (HandPointNet, PointNet++) reads: for every query its
+    ``k`` nearest neighbours in the cloud (``tsdf_knn_hip`` of libtsdf_group.so; include/tsdf_group.h has the contract).
+    One launch, the cloud resident in LDS, one wave per query; the result is pinned bit for bit: distances in float32
+    without fma by :func:`farthest_points`' expression, nearest first, ties to the LOWEST row.
+
+    cloud    float32[n, P, 3] on the GPU, P in 1..12288: contiguous, or the leading rows ``big[:, :P]`` of a contiguous
+             tensor (read in place).  A row with a non-finite coordinate is no candidate: NaN-padded ragged clouds work
+    k        neighbours per query, 1..128.  With fewer than ``k`` candidates the trailing slots repeat slot 0
+    queries  None: every row of the cloud is a query; an int C: rows 0..C-1 — after farthest point sampling the C-point
+             sample, so the centres need no tensor of their own; or float32[n, C, 3] on the GPU.  A query of the cloud
+             finds itself (or an equal row before it) in slot 0 at distance 0; a query with a non-finite coordinate gets
+             index -1 and zeros
+    status   optional int32[n] on the GPU (``fps.status``): a position whose status is not 0 is not read, gets index -1 and
+             zeros, and its status is copied through
+    dist2 / offsets  which optional outputs to allocate (``offsets``: neighbour - query, float32[n, C, k, 3])
+    out      optional :class:`KnnBatch` to write into; its ``dist2`` / ``offsets`` may be None
+    Returns :class:`KnnBatch`.  A cloud without a candidate has status 1.  Every bad argument is a ValueError before
+    anything is launched.  Runs on the current stream, no synchronisation.
+
+    The HandPointNet input — normals and two grouping levels — with nothing on the host in between::
+
+        obb = obb_xforms(depth, offsets, headers)
+        fps = farthest_points(depth, offsets, headers, 1024, xforms=obb.xforms)
+        nrm = point_normals(fps.points, 30, xforms=obb.xforms, status=fps.status)
+        g1 = knn_groups(fps.points, 64, queries=512, offsets=True)
+        g2 = knn_groups(fps.points[:, :512], 64, queries=128, offsets=True)
+    """
+    return _knn(cloud, k, queries, status, dist2, offsets, out)
+
+
+def _normals(cloud, k, queries, status, view, curvature, out) -> NormalBatch:
+    """:func:`point_normals` with the viewpoint as a tensor or None; given ``out`` the call allocates nothing."""
+    K = _group_k(k)
+    G = _lib.load_group()
+    try:
+        dev, n, P, pitch, C, qptr, sptr = _group_in(cloud, queries, status)
+        if view is not None:
+            _shaped("view", view, (n, 3), torch.float64, dev)
+        out = _group_out(NormalBatch, out, (("normals", (n, C, 3), torch.float32), ("curvature", (n, C), torch.float32),
+                                            ("status", (n,), torch.int32)), {"curvature": bool(curvature)}, dev)
+    except TypeError as e:
+        raise ValueError(str(e)) from None
+    if n:
+        _call(dev, G.tsdf_normals_hip, [cloud.data_ptr(), pitch, qptr, sptr, _ptr(view), n, P, C, K, None,
+                                        out.normals.data_ptr(), _ptr(out.curvature), out.status.data_ptr()], 9)
+    return out
+
+
+def _view_of(xforms, n, out=None):
+    """The viewpoint under per-frame maps float64[n,24]: the image of the camera centre (the origin) under each map's
+    forward rows, its translation column — float64[n,3] (``out``: written there, nothing allocated)."""
+    col = xforms.view(n, 6, 4)[:, :3, 3]
+    return col.contiguous() if out is None else out.copy_(col)
+
+
+def point_normals(cloud: torch.Tensor, k: int = 30, queries=None, status: Optional[torch.Tensor] = None,
+                  view: Optional[torch.Tensor] = None, xforms: Optional[torch.Tensor] = None, curvature: bool = True,
+                  out: Optional[NormalBatch] = None) -> NormalBatch:
+    """Surface normals by PCA over each query's ``k`` nearest neighbours (``tsdf_normals_hip`` of libtsdf_group.so): the
+    neighbours are :func:`knn_groups`'s; their covariance is summed in float64 in a fixed tree order, its eigenvectors come
+    from a fixed number of Jacobi sweeps, the normal is the eigenvector of the smallest eigenvalue turned towards the
+    viewpoint, and ``curvature`` is l0 / (l0 + l1 + l2).  One launch; the result is pinned bit for bit.
+
+    cloud / k / queries / status   as for :func:`knn_groups` (``queries`` None: a normal for every point)
+    view     optional float64[n, 3] on the GPU: the viewpoint of each position, in the cloud's frame; None is the origin,
+             the camera of an unmapped cloud
+    xforms   instead of ``view``, the float64[n, 24] maps the cloud was sampled under (``obb.xforms``): the viewpoint is
+             the image of the camera centre under each map's forward rows (one small copy builds it)
+    curvature  False: no curvature output
+    out      optional :class:`NormalBatch` to write into; its ``curvature`` may be None
+    Returns :class:`NormalBatch`.  Fewer than 3 neighbours, a non-finite query and a position that is not read give a zero
+    normal and zero curvature.  Every bad argument is a ValueError before anything is launched."""
+    if view is not None and xforms is not None:
+        raise ValueError("view and xforms are two ways to say the same thing: give one")
+    if xforms is not None:
+        try:
+            _group_k(k)
+            dev, n = _group_in(cloud, queries, status)[:2]   # every refusal comes before the copy below
+            _shaped("xforms", xforms, (n, 24), torch.float64, dev)
+        except TypeError as e:
+            raise ValueError(str(e)) from None
+        view = _view_of(xforms, n)
+    return _normals(cloud, k, queries, status, view, curvature, out)
