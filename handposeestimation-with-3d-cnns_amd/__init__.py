@@ -67,6 +67,12 @@ kNN grouping and surface normals:        knn_groups (for every centre of a set-a
                                          include/tsdf_group.h), point_normals (PCA normals over the same neighbours, turned
                                          towards the viewpoint, with the surface variation), KnnBatch, NormalBatch,
                                          group_plan, AugmentedStep(fps=..., groups=..., normals=...)
+Point-wise offset fields:                point_fields (the labels of a point-to-point regression network: per sampled point
+                                         and joint a heat and a unit vector towards the joint, on the joint's k nearest
+                                         points inside a ball — a radix select per joint over a cloud resident in LDS:
+                                         libtsdf_pointfield.so, include/tsdf_pointfield.h), field_joints (each joint back
+                                         from a predicted field by a weighted vote of its points of greatest heat),
+                                         PointFieldBatch, FieldJoints, pointfield_plan, AugmentedStep(fps=..., fields=...)
 """
 from . import _lib  # noqa: F401
 from ._lib import TsdfCam, TsdfError, default_cam  # noqa: F401
@@ -82,7 +88,8 @@ from .voxelize import (AabbBatch, AugmentedStep, CloudGridBatch, MapGridBatch, O
                        voxelize_aug_accurate, voxelize_map_grid_accurate, HeatmapJoints, heatmap_joints, joint_heatmaps,
                        heatmap_mse_loss, soft_argmax_joints, occupancy_volumes, voxelize_occupancy, FpsBatch,
                        farthest_points, farthest_of, fps_plan, KnnBatch, NormalBatch, knn_groups,
-                       point_normals, group_plan)
+                       point_normals, group_plan, PointFieldBatch, FieldJoints, point_fields, field_joints,
+                       pointfield_plan)
 from .pca import JointPCA, fit_joint_pca  # noqa: F401
 from . import augment, dataset, export, packing, pca, shard, synth  # noqa: F401
 from .dataset import MSRA_Dataset, MSRADepthDataset, ResidentLoader, VoxelBatch, VoxelLoader  # noqa: F401
@@ -102,7 +109,8 @@ __all__ = ["voxelize", "voxelize_labels", "voxelize_indexed", "ResidentLoader", 
            "HandCrops", "voxelize_grid_accurate", "voxelize_accurate", "voxelize_map_grid_accurate", "voxelize_aug_accurate",
            "joint_heatmaps", "heatmap_joints", "HeatmapJoints", "heatmap_mse_loss", "soft_argmax_joints",
            "occupancy_volumes", "voxelize_occupancy", "farthest_points", "farthest_of", "FpsBatch", "fps_plan",
-           "FPS_RESIDENT_POINTS", "knn_groups", "point_normals", "KnnBatch", "NormalBatch", "group_plan"]
+           "FPS_RESIDENT_POINTS", "knn_groups", "point_normals", "KnnBatch", "NormalBatch", "group_plan",
+           "point_fields", "field_joints", "PointFieldBatch", "FieldJoints", "pointfield_plan"]
 
 
 def __getattr__(name):

@@ -185,6 +185,17 @@ GROUP_MAX_CLOUD = 12288            # TSDF_GROUP_MAX_CLOUD: rows of a cloud, the 
 GROUP_MAX_K = 128                  # TSDF_GROUP_MAX_K
 GROUP_SWEEPS = 8                   # TSDF_GROUP_SWEEPS: the fixed number of Jacobi sweeps of the normals
 
+# The library of include/tsdf_pointfield.h (make -C csrc pointfield): point-wise offset-field labels of sampled clouds — per
+# point and joint a heat and a unit vector towards the joint — and their voting decode, a selection without a sort per
+# joint over a cloud resident in LDS.  A binary of its own; its row is _POINTFIELD below, outside _EXTS like _HEATMAP.
+POINTFIELD_LIB_PATH = os.path.join(_HERE, "libtsdf_pointfield.so")
+POINTFIELD_VERSION = 1
+POINTFIELD_MAX_CLOUD = 12288       # TSDF_POINTFIELD_MAX_CLOUD: rows of a cloud, GROUP_MAX_CLOUD
+POINTFIELD_MAX_K = 12288           # TSDF_POINTFIELD_MAX_K: the encoder's nearest points per joint
+POINTFIELD_MAX_VOTES = 128         # TSDF_POINTFIELD_MAX_VOTES: the decoder's voting points per joint
+POINTFIELD_MAX_JOINTS = 65536      # TSDF_POINTFIELD_MAX_JOINTS
+POINTFIELD_LAYOUTS = {"cp": 0, "pc": 1}   # TSDF_POINTFIELD_CP [n, 4J, P] / TSDF_POINTFIELD_PC [n, P, 4J]
+
 
 class _Ext(NamedTuple):
     """A row of the extension table: libtsdf_<name>.so, built by ``make -C csrc <name>`` from include/tsdf_<name>.h."""
@@ -326,6 +337,16 @@ _GROUP = _Ext(GROUP_LIB_PATH, "tsdf_group_version", GROUP_VERSION, {
     "tsdf_normals_hip": [_vp, _i64, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp],
 })
 
+# libtsdf_pointfield.so's row, of the same type and loaded by the same code (load_pointfield)
+_POINTFIELD = _Ext(POINTFIELD_LIB_PATH, "tsdf_pointfield_version", POINTFIELD_VERSION, {
+    # P, J, K, lds_bytes, joints_per_group, groups_per_position (three ints in host memory)
+    "tsdf_pointfield_plan": [_i, _i, _i, ctypes.POINTER(_i), ctypes.POINTER(_i), ctypes.POINTER(_i)],
+    # points, pitch, joints, status_in, n, P, J, K, radius, layout, dtype, stream, field, valid, status
+    "tsdf_pointfield_encode_hip": [_vp, _i64, _vp, _vp, _i, _i, _i, _i, ctypes.c_double, _i, _i, _vp, _vp, _vp, _vp],
+    # points, pitch, field, status_in, n, P, J, M, radius, layout, dtype, stream, joints, weight, status
+    "tsdf_pointfield_decode_hip": [_vp, _i64, _vp, _vp, _i, _i, _i, _i, ctypes.c_double, _i, _i, _vp, _vp, _vp, _vp],
+})
+
 _lib = None
 _debug_lib = None
 _ext_libs = {}   # name -> the loaded extension library
@@ -464,6 +485,11 @@ def load_fps():
 def load_group():
     """libtsdf_group.so, the library of include/tsdf_group.h (its row is ``_GROUP``)."""
     return _load_row("group", _GROUP)
+
+
+def load_pointfield():
+    """libtsdf_pointfield.so, the library of include/tsdf_pointfield.h (its row is ``_POINTFIELD``)."""
+    return _load_row("pointfield", _POINTFIELD)
 
 
 def load_augment():

@@ -715,14 +715,23 @@ class AugmentedStep:
     set-abstraction level after that — :func:`knn_groups` with ``offsets`` — into the static :class:`KnnBatch` es
     ``self.groups[l]``: level 0 groups the ``M`` sampled rows around their first ``C_0``, level ``l`` the first
     ``C_{l-1}`` rows around their first ``C_l``.  Positions the sampling gave a status are not read.  ``step`` returns
-    exactly what it returns without them; without the two arguments the step issues exactly the launches listed above."""
+    exactly what it returns without them; without the two arguments the step issues exactly the launches listed above.
+
+    ``fields=(K, radius)`` or ``(K, radius, dtype)`` (needs ``fps=(M,)`` and ``gt``): the step also writes the labels of a
+    point-to-point regression network, per sampled point and joint a heat and a unit vector towards the joint, into ONE
+    static buffer ``self.field`` ``[n, 4J, M]`` (layout "cp"; float32 unless ``dtype`` says otherwise) and
+    ``self.field_valid`` int32[n, J].  It is one more launch after the sampling, and after normals / groups when they are
+    given — :func:`point_fields` of ``self.cloud`` and the step's ``gt_aug`` with ``status=self.cloud_status``: joints and
+    cloud are both in the step's mapped frame, in mm, which is ``radius``' unit.  ``step`` returns exactly what it returns
+    without it; ``fields=None`` issues exactly the launches listed above."""
 
     def __init__(self, depth: torch.Tensor, offsets: torch.Tensor, headers: torch.Tensor, n: int,
                  gt: Optional[torch.Tensor] = None, centres: Optional[torch.Tensor] = None, res: int = 32,
                  layout: str = "czyx", clamp: bool = True, cam: Optional[_lib.TsdfCam] = None, graph: bool = True,
                  dtype: Optional[torch.dtype] = None, base: Optional[torch.Tensor] = None, fused_head: bool = False,
-                 heatmap: Optional[tuple] = None, groups: Optional[tuple] = None, normals: Optional[int] = None,
-                 fps: Optional[tuple] = None, occupancy: Optional[tuple] = None, tsdf: str = "projective"):
+                 heatmap: Optional[tuple] = None, fields: Optional[tuple] = None, groups: Optional[tuple] = None,
+                 normals: Optional[int] = None, fps: Optional[tuple] = None, occupancy: Optional[tuple] = None,
+                 tsdf: str = "projective"):
         self.accurate = _tsdf_kind(tsdf)
         self.heat = self._heatmap = None
         self.occ = self._occupancy = None
@@ -749,6 +758,17 @@ class AugmentedStep:
                     rows = C
             if self._normals_k is not None and self._fps > _lib.GROUP_MAX_CLOUD:
                 raise ValueError(f"normals read a cloud of at most {_lib.GROUP_MAX_CLOUD} points")
+        self.field = self.field_valid = self._fields = None
+        if fields is not None:   # the point-wise labels of the sampled cloud
+            if not isinstance(fields, (tuple, list)) or len(fields) not in (2, 3):
+                raise ValueError("fields must be (K, radius) or (K, radius, dtype)")
+            if self._fps is None or gt is None:
+                raise ValueError("fields need fps=(M,) and gt: they are written from the step's sampled cloud and gt_aug")
+            if self._fps > _lib.POINTFIELD_MAX_CLOUD:
+                raise ValueError(f"fields read a cloud of at most {_lib.POINTFIELD_MAX_CLOUD} points")
+            fdtype = fields[2] if len(fields) == 3 else torch.float32
+            _heat_dtype(fdtype)
+            self._fields = (_group_count("K", fields[0], _lib.POINTFIELD_MAX_K), _field_radius(fields[1]), fdtype)
         if occupancy is not None:
             if not isinstance(occupancy, (tuple, list)) or len(occupancy) not in (1, 2):
                 raise ValueError("occupancy must be (res,) or (res, dtype)")
@@ -832,6 +852,12 @@ class AugmentedStep:
             self.normals = _group_out(NormalBatch, None, (("normals", (n, M, 3), torch.float32), ("curvature", (n, M), torch.float32),
                                                           ("status", (n,), torch.int32)), {}, dev)
             self._view = torch.empty((n, 3), dtype=torch.float64, device=dev)
+        if self._fields is not None:   # the static field, in layout "cp"
+            J = _coords("gt", self.gt_aug, n) // 3
+            self._field_out = PointFieldBatch(torch.empty((n, 4 * J, self._fps), dtype=self._fields[2], device=dev),
+                                              torch.empty((n, J), dtype=torch.int32, device=dev),
+                                              torch.empty((n,), dtype=torch.int32, device=dev))
+            self.field, self.field_valid = self._field_out.field, self._field_out.valid
         if self._head:   # what map_step_head writes into: the object's own buffers
             g = self._grid if placed else MapGridBatch(None, None, None, None)
             self._head_out = MapStepBatch(self.xforms, g.grid, g.max_l, g.mid_p, g.status, self.gt_aug, self.gt_nor)
@@ -876,6 +902,9 @@ class AugmentedStep:
         if self._groups is not None:   # and the levels' groups, each level's cloud a prefix of the sampled rows
             for (rows, C, K), out in zip(self._groups, self.groups):
                 _knn(self.cloud[:, :rows], K, C, self.cloud_status, True, True, out)
+        if self._fields is not None:   # and the point-wise labels: cloud and joints both in the step's mapped frame
+            K, radius, fdtype = self._fields
+            _point_fields(self.cloud, self.gt_aug, K, radius, "cp", fdtype, self.cloud_status, self._field_out)
 
     def _step_launches(self):
         d, o, h = self._pack_args
@@ -2541,3 +2570,126 @@ def point_normals(cloud: torch.Tensor, k: int = 30, queries=None, status: Option
             raise ValueError(str(e)) from None
         view = _view_of(xforms, n)
     return _normals(cloud, k, queries, status, view, curvature, out)
+
+
+class PointFieldBatch(NamedTuple):
+    field: torch.Tensor    # dtype[n, 4J, P] ("cp") or [n, P, 4J] ("pc"): channel j joint j's heat, J + 3j + a its vector
+    valid: torch.Tensor    # int32[n, J]  1: a finite joint of a position that was read and has a candidate
+    status: torch.Tensor   # int32[n]     _lib.TSDF_FRAME_*, or the input status copied through
+
+
+class FieldJoints(NamedTuple):
+    joints: torch.Tensor   # float32[n, J, 3]  the weighted vote, in the cloud's frame
+    weight: torch.Tensor   # float32[n, J]     the sum of the votes' weights (0: no vote, a zero row)
+    status: torch.Tensor   # int32[n]
+
+
+def _field_radius(radius) -> float:
+    if isinstance(radius, bool) or not isinstance(radius, (int, float)) or not 0.0 < float(radius) < float("inf"):
+        raise ValueError(f"radius must be a finite number > 0 (in the cloud's units), got {radius!r}")
+    return float(radius)
+
+
+def _field_layout(layout) -> int:
+    if not isinstance(layout, str) or layout not in _lib.POINTFIELD_LAYOUTS:
+        raise ValueError("layout must be 'cp' ([n, 4J, P]) or 'pc' ([n, P, 4J])")
+    return _lib.POINTFIELD_LAYOUTS[layout]
+
+
+def _field_shape(lay, n, J, P) -> tuple:
+    return (n, 4 * J, P) if lay == 0 else (n, P, 4 * J)
+
+
+def pointfield_plan(P: int, J: int, K: int) -> tuple:
+    """``tsdf_pointfield_plan`` (host code only): ``(lds_bytes, joints per workgroup, workgroups per batch position)`` of a
+    call with clouds of ``P`` rows, ``J`` joints and ``K`` nearest points (or votes)."""
+    P = _group_count("P", P, _lib.POINTFIELD_MAX_CLOUD)
+    J = _group_count("J", J, _lib.POINTFIELD_MAX_JOINTS)
+    K = _group_count("K", K, _lib.POINTFIELD_MAX_K)
+    lds, per, groups = ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
+    _lib.check(_lib.load_pointfield().tsdf_pointfield_plan(P, J, K, lds, per, groups), "tsdf_pointfield_plan")
+    return lds.value, per.value, groups.value
+
+
+def _point_fields(cloud, joints, k, radius, layout, dtype, status, out) -> PointFieldBatch:
+    """:func:`point_fields`; given ``out`` the call allocates nothing."""
+    K = _group_count("k", k, _lib.POINTFIELD_MAX_K)
+    r, lay, code = _field_radius(radius), _field_layout(layout), _heat_dtype(dtype)
+    F = _lib.load_pointfield()
+    try:
+        dev, n, P, pitch, _, _, sptr = _group_in(cloud, None, status)
+        _dev_check("joints", joints, torch.float32, dev)
+        if joints.dim() not in (2, 3) or (joints.dim() == 3 and joints.shape[2] != 3):
+            raise ValueError(f"joints must have shape [{n}, 3*J] or [{n}, J, 3]")
+        J = (_coords("joints", joints, n) or math.prod(joints.shape[1:])) // 3
+        if J < 1:
+            raise ValueError(f"joints must have shape [{n}, 3*J] or [{n}, J, 3]")
+        out = _outs(PointFieldBatch, out, (("field", _field_shape(lay, n, J, P), dtype), ("valid", (n, J), torch.int32),
+                                           ("status", (n,), torch.int32)), dev)
+    except (TypeError, AttributeError) as e:   # a bad argument of this entry is a ValueError whatever is wrong with it
+        raise ValueError(str(e)) from None
+    if n:
+        _call(dev, F.tsdf_pointfield_encode_hip, [cloud.data_ptr(), pitch, joints.data_ptr(), sptr, n, P, J, K, r, lay, code,
+                                                  None, out.field.data_ptr(), out.valid.data_ptr(), out.status.data_ptr()], 11)
+    return out
+
+
+def point_fields(cloud: torch.Tensor, joints: torch.Tensor, k: int = 64, *, radius: float, layout: str = "cp",
+                 dtype: torch.dtype = torch.float32, status: Optional[torch.Tensor] = None,
+                 out: Optional[PointFieldBatch] = None) -> PointFieldBatch:
+    """The labels of a point-to-point regression network (Ge, Ren, Yuan, ECCV 2018): for every point of a sampled cloud and
+    every joint a heat value and a unit vector pointing at the joint, defined on the joint's ``k`` nearest points inside a
+    ball (``tsdf_pointfield_encode_hip`` of libtsdf_pointfield.so; include/tsdf_pointfield.h has the contract).  One
+    launch, the cloud resident in LDS, one wave per joint, a radix select instead of a sort; the result is pinned bit for
+    bit: distances as :func:`knn_groups` forms them, ties to the LOWEST row, heat ``1 - d / radius`` and the vector
+    ``(joint - point) / d`` in float64, each rounded once.
+
+    cloud    float32[n, P, 3] on the GPU as for :func:`knn_groups` (``fps.points``); a non-finite row is no candidate
+    joints   float32[n, 3J] or [n, J, 3] on the GPU, in the cloud's frame and units; a non-finite joint gets a zero field
+    k        nearest points per joint, 1..12288; ``k >= P`` is the pure ball rule
+    radius   the ball about a joint, in the cloud's units (no default: it depends on them)
+    layout   "cp": ``[n, 4J, P]``, what a ``Conv1d`` head emits; "pc": ``[n, P, 4J]``.  Channel j is joint j's heat, channel
+             ``J + 3j + a`` component a of its vector
+    dtype    torch.float32, torch.float16 or torch.bfloat16 (the float32 value narrowed by round-to-nearest-even)
+    status   optional int32[n] on the GPU (``fps.status``): a position whose status is not 0 is not read and gets zeros
+    out      optional :class:`PointFieldBatch` to write into; every byte is written
+    Returns :class:`PointFieldBatch`.  Every bad argument is a ValueError before anything is launched.  Runs on the current
+    stream, no synchronisation."""
+    return _point_fields(cloud, joints, k, radius, layout, dtype, status, out)
+
+
+def field_joints(cloud: torch.Tensor, field: torch.Tensor, *, radius: float, points: int = 25, layout: str = "cp",
+                 status: Optional[torch.Tensor] = None, out: Optional[FieldJoints] = None) -> FieldJoints:
+    """Each joint back from a (predicted) offset field (``tsdf_pointfield_decode_hip`` of libtsdf_pointfield.so): the
+    ``points`` candidates of greatest heat vote ``point + radius * (1 - w) * unit(vector)`` with weight
+    ``w = clamp(heat, 0, 1)``; the weighted mean is summed in float64 in a fixed tree order, so the result is pinned bit for
+    bit.  Ties go to the lowest row; a NaN heat never wins over a number.
+
+    cloud    float32[n, P, 3] on the GPU as for :func:`point_fields`
+    field    float32 / float16 / bfloat16 on the GPU, ``[n, 4J, P]`` ("cp") or ``[n, P, 4J]`` ("pc")
+    radius   the ball the field was written with
+    points   voting points per joint, 1..128
+    status   optional int32[n] on the GPU: a position whose status is not 0 is not read and gets zero rows
+    out      optional :class:`FieldJoints` to write into
+    Returns :class:`FieldJoints`; a joint without a vote of positive weight is a zero row of weight 0."""
+    M = _group_count("points", points, _lib.POINTFIELD_MAX_VOTES)
+    r, lay = _field_radius(radius), _field_layout(layout)
+    F = _lib.load_pointfield()
+    try:
+        dev, n, P, pitch, _, _, sptr = _group_in(cloud, None, status)
+        if not isinstance(field, torch.Tensor):
+            raise ValueError("field must be a torch.Tensor")
+        code = _heat_dtype(field.dtype)
+        _dev_check("field", field, field.dtype, dev)
+        C = int(field.shape[1 if lay == 0 else 2]) if field.dim() == 3 else 0
+        if C < 4 or C % 4 or tuple(field.shape) != _field_shape(lay, n, C // 4, P) or C // 4 > _lib.POINTFIELD_MAX_JOINTS:
+            raise ValueError(f"field must have shape [{n}, 4*J, {P}] ('cp') or [{n}, {P}, 4*J] ('pc')")
+        J = C // 4
+        out = _outs(FieldJoints, out, (("joints", (n, J, 3), torch.float32), ("weight", (n, J), torch.float32),
+                                       ("status", (n,), torch.int32)), dev)
+    except (TypeError, AttributeError) as e:
+        raise ValueError(str(e)) from None
+    if n:
+        _call(dev, F.tsdf_pointfield_decode_hip, [cloud.data_ptr(), pitch, field.data_ptr(), sptr, n, P, J, M, r, lay, code,
+                                                  None, out.joints.data_ptr(), out.weight.data_ptr(), out.status.data_ptr()], 11)
+    return out
