@@ -73,6 +73,13 @@ Point-wise offset fields:                point_fields (the labels of a point-to-
                                          libtsdf_pointfield.so, include/tsdf_pointfield.h), field_joints (each joint back
                                          from a predicted field by a weighted vote of its points of greatest heat),
                                          PointFieldBatch, FieldJoints, pointfield_plan, AugmentedStep(fps=..., fields=...)
+Depth-image patches (the 2-D CNN input): frame_patches (per located cube a fixed-size [n, 1, S, S] patch resampled from the
+                                         cube's image rectangle in raw frames, depth normalised by the cube to [-1, 1],
+                                         background +1, nearest or bilinear without blending hand and background, under an
+                                         optional in-plane map per frame: libtsdf_patch.so, include/tsdf_patch.h),
+                                         crop_patches (the same on a pack), patch_affines (rotation / scale / shift maps),
+                                         joints_to_uvd and uvd_to_joints (the joints in the patch's coordinates and back),
+                                         patch_frames (locate_hands chained into the three), PatchBatch, UvdBatch, patch_plan
 """
 from . import _lib  # noqa: F401
 from ._lib import TsdfCam, TsdfError, default_cam  # noqa: F401
@@ -89,7 +96,8 @@ from .voxelize import (AabbBatch, AugmentedStep, CloudGridBatch, MapGridBatch, O
                        heatmap_mse_loss, soft_argmax_joints, occupancy_volumes, voxelize_occupancy, FpsBatch,
                        farthest_points, farthest_of, fps_plan, KnnBatch, NormalBatch, knn_groups,
                        point_normals, group_plan, PointFieldBatch, FieldJoints, point_fields, field_joints,
-                       pointfield_plan)
+                       pointfield_plan, PatchBatch, UvdBatch, frame_patches, crop_patches, joints_to_uvd,
+                       uvd_to_joints, patch_affines, patch_frames, patch_plan)
 from .pca import JointPCA, fit_joint_pca  # noqa: F401
 from . import augment, dataset, export, packing, pca, shard, synth  # noqa: F401
 from .dataset import MSRA_Dataset, MSRADepthDataset, ResidentLoader, VoxelBatch, VoxelLoader  # noqa: F401
@@ -110,7 +118,9 @@ __all__ = ["voxelize", "voxelize_labels", "voxelize_indexed", "ResidentLoader", 
            "joint_heatmaps", "heatmap_joints", "HeatmapJoints", "heatmap_mse_loss", "soft_argmax_joints",
            "occupancy_volumes", "voxelize_occupancy", "farthest_points", "farthest_of", "FpsBatch", "fps_plan",
            "FPS_RESIDENT_POINTS", "knn_groups", "point_normals", "KnnBatch", "NormalBatch", "group_plan",
-           "point_fields", "field_joints", "PointFieldBatch", "FieldJoints", "pointfield_plan"]
+           "point_fields", "field_joints", "PointFieldBatch", "FieldJoints", "pointfield_plan",
+           "frame_patches", "crop_patches", "joints_to_uvd", "uvd_to_joints", "patch_affines", "patch_frames", "PatchBatch",
+           "UvdBatch", "patch_plan"]
 
 
 def __getattr__(name):

@@ -196,6 +196,17 @@ POINTFIELD_MAX_VOTES = 128         # TSDF_POINTFIELD_MAX_VOTES: the decoder's vo
 POINTFIELD_MAX_JOINTS = 65536      # TSDF_POINTFIELD_MAX_JOINTS
 POINTFIELD_LAYOUTS = {"cp": 0, "pc": 1}   # TSDF_POINTFIELD_CP [n, 4J, P] / TSDF_POINTFIELD_PC [n, P, 4J]
 
+# The library of include/tsdf_patch.h (make -C csrc patch): depth-image patches for the 2-D CNNs — a fixed-size patch
+# resampled from the located cube's image rectangle under an optional in-plane map, the joints in the patch's (u, v, d)
+# coordinates and the way back.  A binary of its own; its row is _PATCH below, outside _EXTS like _HEATMAP.
+PATCH_LIB_PATH = os.path.join(_HERE, "libtsdf_patch.so")
+PATCH_VERSION = 1
+TSDF_PATCH_F32 = 0                 # the float32 element type of include/tsdf_patch.h; the 2-byte ones are TSDF_LOWP_*
+PATCH_MIN_SIZE = 8                 # TSDF_PATCH_MIN_SIZE: a patch's edge is a multiple of 8 in 8..512
+PATCH_MAX_SIZE = 512               # TSDF_PATCH_MAX_SIZE
+PATCH_MAX_JOINTS = 65536           # TSDF_PATCH_MAX_JOINTS
+PATCH_INTERPS = {"nearest": 0, "bilinear": 1}   # TSDF_PATCH_NEAREST / TSDF_PATCH_BILINEAR
+
 
 class _Ext(NamedTuple):
     """A row of the extension table: libtsdf_<name>.so, built by ``make -C csrc <name>`` from include/tsdf_<name>.h."""
@@ -347,6 +358,25 @@ _POINTFIELD = _Ext(POINTFIELD_LIB_PATH, "tsdf_pointfield_version", POINTFIELD_VE
     "tsdf_pointfield_decode_hip": [_vp, _i64, _vp, _vp, _i, _i, _i, _i, ctypes.c_double, _i, _i, _vp, _vp, _vp, _vp],
 })
 
+# libtsdf_patch.so's row, of the same type and loaded by the same code (load_patch)
+_dbl, _flt = ctypes.c_double, ctypes.c_float
+_PATCH = _Ext(PATCH_LIB_PATH, "tsdf_patch_version", PATCH_VERSION, {
+    # S, dtype, px_per_lane, rows_per_group, items_per_position (three ints in host memory)
+    "tsdf_patch_plan": [_i, _i, ctypes.POINTER(_i), ctypes.POINTER(_i), ctypes.POINTER(_i)],
+    # frames, frame_type, shift, n_src, H, W, index, com, cube, cube_n, affine, status_in, n, S, interp, dtype, background,
+    # focal, cx, cy, invalid_eps, trunc_voxels (the camera by value), stream, patch, status
+    "tsdf_patch_frames_hip": [_vp, _i, _i, _i64, _i, _i, _vp, _vp, _flt, _vp, _vp, _vp, _i, _i, _i, _i, _flt, _dbl, _dbl, _dbl,
+                              _flt, _flt, _vp, _vp, _vp],
+    # depth, depth_len, offsets, headers, n_src, index, com, cube, cube_n, affine, status_in, n, S, interp, dtype, background,
+    # focal, cx, cy, invalid_eps, trunc_voxels, stream, patch, status
+    "tsdf_patch_crops_hip": [_vp, _i64, _vp, _vp, _i64, _vp, _vp, _flt, _vp, _vp, _vp, _i, _i, _i, _i, _flt, _dbl, _dbl, _dbl,
+                             _flt, _flt, _vp, _vp, _vp],
+    # joints, com, cube, cube_n, affine, status_in, n, J, focal, cx, cy, invalid_eps, trunc_voxels, stream, uvd, valid, status
+    "tsdf_patch_uvd_hip": [_vp, _vp, _flt, _vp, _vp, _vp, _i, _i, _dbl, _dbl, _dbl, _flt, _flt, _vp, _vp, _vp, _vp],
+    # uvd, com, cube, cube_n, affine, status_in, n, J, focal, cx, cy, invalid_eps, trunc_voxels, stream, joints
+    "tsdf_patch_joints_hip": [_vp, _vp, _flt, _vp, _vp, _vp, _i, _i, _dbl, _dbl, _dbl, _flt, _flt, _vp, _vp],
+})
+
 _lib = None
 _debug_lib = None
 _ext_libs = {}   # name -> the loaded extension library
@@ -490,6 +520,11 @@ def load_group():
 def load_pointfield():
     """libtsdf_pointfield.so, the library of include/tsdf_pointfield.h (its row is ``_POINTFIELD``)."""
     return _load_row("pointfield", _POINTFIELD)
+
+
+def load_patch():
+    """libtsdf_patch.so, the library of include/tsdf_patch.h (its row is ``_PATCH``)."""
+    return _load_row("patch", _PATCH)
 
 
 def load_augment():

@@ -2693,3 +2693,281 @@ def field_joints(cloud: torch.Tensor, field: torch.Tensor, *, radius: float, poi
         _call(dev, F.tsdf_pointfield_decode_hip, [cloud.data_ptr(), pitch, field.data_ptr(), sptr, n, P, J, M, r, lay, code,
                                                   None, out.joints.data_ptr(), out.weight.data_ptr(), out.status.data_ptr()], 11)
     return out
+
+
+class PatchBatch(NamedTuple):
+    patch: torch.Tensor    # dtype[n, 1, S, S]  depth normalised by the cube: [-1, 1] inside it, ``background`` elsewhere
+    status: torch.Tensor   # int32[n]           0, 1 (no usable cube: input status, centre, cube or map), 2 (no usable source)
+
+
+class UvdBatch(NamedTuple):
+    uvd: torch.Tensor      # float32[n, J, 3]   (a, b, w): column, row and depth in the patch's normalised coordinates
+    valid: torch.Tensor    # int32[n, J]        0: a non-finite joint, one at or behind the camera, or a position with a status
+    status: torch.Tensor   # int32[n]           0, or 1 (no usable cube, or a singular map)
+
+
+def _patch_size(size) -> int:
+    if isinstance(size, bool) or not isinstance(size, int) or size % 8 or not _lib.PATCH_MIN_SIZE <= size <= _lib.PATCH_MAX_SIZE:
+        raise ValueError(f"size must be an integer multiple of 8 in {_lib.PATCH_MIN_SIZE}..{_lib.PATCH_MAX_SIZE}, got {size!r}")
+    return size
+
+
+def _patch_interp(interp) -> int:
+    if not isinstance(interp, str) or interp not in _lib.PATCH_INTERPS:
+        raise ValueError(f"interp must be 'nearest' or 'bilinear', got {interp!r}")
+    return _lib.PATCH_INTERPS[interp]
+
+
+def _patch_dtype(dtype):
+    """(torch dtype, its code); None is float32."""
+    dtype = torch.float32 if dtype is None else dtype
+    return dtype, _heat_dtype(dtype)
+
+
+def _patch_background(background) -> float:
+    if isinstance(background, bool) or not isinstance(background, (int, float)):
+        raise TypeError(f"background must be a number, got {background!r}")
+    return float(background)
+
+
+def patch_plan(size: int = 128, dtype: Optional[torch.dtype] = None) -> tuple:
+    """``tsdf_patch_plan`` (host code only): ``(pixels per lane, rows per workgroup, work items per batch position)`` of a
+    patch launch at edge ``size`` and element type ``dtype``."""
+    S, (_, code) = _patch_size(size), _patch_dtype(dtype)
+    px, rows, items = ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
+    _lib.check(_lib.load_patch().tsdf_patch_plan(S, code, px, rows, items), "tsdf_patch_plan")
+    return px.value, rows.value, items.value
+
+
+def _patch_cube(n, com, cube, affine, status, dev):
+    """The arguments that fix every position's cube, validated: returns (com as float64[n, 3], the scalar cube, the cube
+    tensor or None, affine, status) — what the four entries take after their source."""
+    if not isinstance(com, torch.Tensor):
+        raise TypeError("com must be a torch.Tensor")
+    if com.dtype not in (torch.float64, torch.float32):
+        raise TypeError(f"com must be torch.float64 (HandCrops.com) or torch.float32, got {com.dtype}")
+    if tuple(com.shape) != (n, 3):
+        raise ValueError(f"com must have shape [{n}, 3]")
+    _dev_check("com", com, com.dtype, dev)
+    if com.dtype is torch.float32:
+        com = com.double()                                   # exact
+    cube_n = None
+    if isinstance(cube, torch.Tensor):
+        cube_n = _shaped("cube", cube, (n,), torch.float32, dev)
+        cube = 0.0
+    elif isinstance(cube, bool) or not isinstance(cube, (int, float)) or not 0.0 < float(cube) < float("inf"):
+        raise ValueError(f"cube must be a finite number > 0 (mm) or a float32 tensor [n], got {cube!r}")
+    if affine is not None:
+        if not isinstance(affine, torch.Tensor):
+            raise TypeError("affine must be a torch.Tensor (patch_affines builds one)")
+        _shaped("affine", affine, (n, 6), torch.float64, dev)
+    if status is not None:
+        if not isinstance(status, torch.Tensor):
+            raise TypeError("status must be a torch.Tensor")
+        _shaped("status", status, (n,), torch.int32, dev)
+    return com, float(cube), cube_n, affine, status
+
+
+def _patch_outs(out, n, S, dtype, dev) -> PatchBatch:
+    return _outs(PatchBatch, out, (("patch", (n, 1, S, S), dtype), ("status", (n,), torch.int32)), dev)
+
+
+def _patch_aligned(patch):
+    if patch.data_ptr() % 16:
+        raise ValueError("out.patch must be 16-byte aligned (a lane's pixels leave as one 16-byte store)")
+
+
+def frame_patches(frames: torch.Tensor, com: torch.Tensor, *, size: int = 128, cube=250.0, interp: str = "nearest",
+                  dtype: Optional[torch.dtype] = None, affine: Optional[torch.Tensor] = None, background: float = 1.0,
+                  cam: Optional[_lib.TsdfCam] = None, shift: Optional[int] = None, index: Optional[torch.Tensor] = None,
+                  status: Optional[torch.Tensor] = None, out: Optional[PatchBatch] = None) -> PatchBatch:
+    """The input of a 2-D CNN that reads a depth image (DeepPrior++, A2J, DenseReg, Pose-REN): per batch position a
+    ``size`` x ``size`` patch resampled from the image rectangle of the cube of edge ``cube`` mm about ``com``, straight
+    from raw frames (``tsdf_patch_frames_hip`` of libtsdf_patch.so; include/tsdf_patch.h has the contract, pinned bit for
+    bit).  A pixel's depth d becomes ``(d - cd) / (cube / 2)`` in [-1, 1]; a pixel whose tap is outside the frame, invalid
+    or outside the cube in depth is ``background``.  One gather launch on the current stream, no synchronisation.
+
+    frames   float32[N,H,W] mm, or uint16[N,H,W] with ``shift`` (0..7), as for :func:`locate_hands`
+    com      float64[n,3] on the GPU, ``HandCrops.com``'s convention (camera frame, mm, ``z = -depth``); a float32 tensor
+             (``aabb(...)``'s or a placement's ``mid_p``) is widened
+    size     the patch's edge S, a multiple of 8 in 8..512
+    cube     the cube's edge in mm: a float, or a float32 tensor [n] (scale augmentation of the cube is per frame)
+    interp   "nearest": the tap ``floor(u + 0.5)``; "bilinear": the four neighbours, renormalised over the VALID ones, so the
+             hand is never blended with the background (what ``grid_sample`` does at the silhouette)
+    dtype    None / torch.float32, torch.float16 or torch.bfloat16
+    affine   optional float64[n,6] on the GPU (:func:`patch_affines`): rows ``a00 a01 a02 a10 a11 a12`` mapping PATCH
+             coordinates in [-1, 1]^2 to coordinates in the cube's rectangle; None is the identity
+    index    optional int64[n] on the GPU: batch position i reads frame index[i] (outside [0, N): status 2)
+    status   optional int32[n] on the GPU (``HandCrops.status``): a position with a non-zero entry is not read (status 1)
+    out      optional :class:`PatchBatch` to write into (capturable); ``out.patch`` must be 16-byte aligned
+    Returns :class:`PatchBatch`; every pixel of a position with a status is ``background``.  :func:`crop_patches` on
+    :func:`locate_hands`' pack need NOT give the same patch at the crop's right and bottom edge (``floor(u + 0.5)`` can reach
+    the crop's exclusive bound) or under an ``affine`` (this form sees pixels the crop never held)."""
+    P = _lib.load_patch()
+    S, lerp, (dtype, code), bg = _patch_size(size), _patch_interp(interp), _patch_dtype(dtype), _patch_background(background)
+    if not isinstance(frames, torch.Tensor):
+        raise TypeError("frames must be a torch.Tensor")
+    if frames.dtype not in _LOCATE_TYPES:
+        raise TypeError(f"frames must be torch.float32 or torch.uint16, got {frames.dtype}")
+    if frames.dim() != 3 or frames.shape[1] < 1 or frames.shape[2] < 1:
+        raise ValueError("frames must have shape [N, H, W]")
+    u16 = frames.dtype is torch.uint16
+    if u16:
+        if isinstance(shift, bool) or not isinstance(shift, int) or not 0 <= shift <= _lib.DEPTH16_MAX_SHIFT:
+            raise ValueError(f"uint16 frames need shift, an integer in 0..{_lib.DEPTH16_MAX_SHIFT}; got {shift!r}")
+    elif shift is not None:
+        raise ValueError("shift belongs to uint16 frames")
+    _dev_check("frames", frames, frames.dtype)
+    dev = frames.device
+    n_src, H, W = (int(v) for v in frames.shape)
+    n = n_src if index is None else _indexed(index, n_src, dev, "index needs at least one frame")
+    com, cube, cube_n, affine, status = _patch_cube(n, com, cube, affine, status, dev)
+    out = _patch_outs(out, n, S, dtype, dev)
+    _patch_aligned(out.patch)
+    if n:
+        _call(dev, P.tsdf_patch_frames_hip,
+              [frames.data_ptr(), _LOCATE_TYPES[frames.dtype], shift if u16 else 0, n_src, H, W, _ptr(index), com.data_ptr(), cube,
+               _ptr(cube_n), _ptr(affine), _ptr(status), n, S, lerp, code, bg, *_cam5(cam), None, out.patch.data_ptr(),
+               out.status.data_ptr()], 22)
+    return out
+
+
+def crop_patches(depth: torch.Tensor, offsets: torch.Tensor, headers: torch.Tensor, com: torch.Tensor, *, size: int = 128,
+                 cube=250.0, interp: str = "nearest", dtype: Optional[torch.dtype] = None,
+                 affine: Optional[torch.Tensor] = None, background: float = 1.0, cam: Optional[_lib.TsdfCam] = None,
+                 index: Optional[torch.Tensor] = None, status: Optional[torch.Tensor] = None,
+                 out: Optional[PatchBatch] = None) -> PatchBatch:
+    """:func:`frame_patches` on a pack — the ``depth / offsets / headers`` triple every entry here reads and
+    :func:`locate_hands` writes (``tsdf_patch_crops_hip``: the same kernel and the same contract).  The source rectangle of
+    a position is its header's ``[left, right) x [top, bottom)``; a header the voxelizers' header rule refuses, or an
+    ``index`` outside the pack, gives status 2.  A tap outside the crop is invalid even where the frame the crop was cut
+    from had a pixel there: at the crop's right and bottom edge (``floor(u + 0.5)`` can reach the exclusive bound) and under
+    an ``affine`` this need NOT equal :func:`frame_patches` on the frames themselves.  The other arguments are
+    :func:`frame_patches`'."""
+    P = _lib.load_patch()
+    S, lerp, (dtype, code), bg = _patch_size(size), _patch_interp(interp), _patch_dtype(dtype), _patch_background(background)
+    dev, n_src, _ = _pack(_lib.load(), depth, offsets, headers)
+    n = n_src if index is None else _indexed(index, n_src, dev, "index needs at least one source frame")
+    com, cube, cube_n, affine, status = _patch_cube(n, com, cube, affine, status, dev)
+    out = _patch_outs(out, n, S, dtype, dev)
+    _patch_aligned(out.patch)
+    if n:
+        _call(dev, P.tsdf_patch_crops_hip,
+              [depth.data_ptr(), depth.numel(), offsets.data_ptr(), headers.data_ptr(), n_src, _ptr(index), com.data_ptr(), cube,
+               _ptr(cube_n), _ptr(affine), _ptr(status), n, S, lerp, code, bg, *_cam5(cam), None, out.patch.data_ptr(),
+               out.status.data_ptr()], 21)
+    return out
+
+
+def _patch_joints(name, t):
+    """float32[n, 3J] or [n, J, 3] on the GPU: returns (n, J)."""
+    if not isinstance(t, torch.Tensor):
+        raise TypeError(f"{name} must be a torch.Tensor")
+    _dev_check(name, t, torch.float32)
+    if t.dim() not in (2, 3) or (t.dim() == 3 and t.shape[2] != 3) or (t.dim() == 2 and t.shape[1] % 3):
+        raise ValueError(f"{name} must have shape [n, 3*J] or [n, J, 3]")
+    n, J = int(t.shape[0]), math.prod(t.shape[1:]) // 3
+    if not 1 <= J <= _lib.PATCH_MAX_JOINTS:
+        raise ValueError(f"{name} must hold 1..{_lib.PATCH_MAX_JOINTS} joints of 3 coordinates per frame")
+    return n, J
+
+
+def joints_to_uvd(gt: torch.Tensor, com: torch.Tensor, *, cube=250.0, affine: Optional[torch.Tensor] = None,
+                  cam: Optional[_lib.TsdfCam] = None, status: Optional[torch.Tensor] = None,
+                  out: Optional[UvdBatch] = None) -> UvdBatch:
+    """The labels of a patch network: camera-frame joints ``gt`` (float32[n,3J] or [n,J,3] on the GPU, mm) in the normalised
+    coordinates of the patch :func:`frame_patches` cuts with the same ``com`` / ``cube`` / ``affine`` / ``cam``
+    (``tsdf_patch_uvd_hip``): ``(a, b)`` the column and row in [-1, 1] — pixel centre j is ``(2j + 1) / S - 1`` —, ``w`` the
+    depth ``(-z - cd) / (cube / 2)``.  A joint inside the cube and the patch is in [-1, 1]^3; nothing is clamped.  Under an
+    ``affine`` the inverse map is applied, so a singular one gives the position status 1.  Returns :class:`UvdBatch`; an
+    invalid joint is a zero row.  One thread per joint, float64 arithmetic rounded once: pinned bit for bit."""
+    P = _lib.load_patch()
+    n, J = _patch_joints("gt", gt)
+    dev = gt.device
+    com, cube, cube_n, affine, status = _patch_cube(n, com, cube, affine, status, dev)
+    out = _outs(UvdBatch, out, (("uvd", (n, J, 3), torch.float32), ("valid", (n, J), torch.int32), ("status", (n,), torch.int32)), dev)
+    if n:
+        _call(dev, P.tsdf_patch_uvd_hip,
+              [gt.data_ptr(), com.data_ptr(), cube, _ptr(cube_n), _ptr(affine), _ptr(status), n, J, *_cam5(cam), None,
+               out.uvd.data_ptr(), out.valid.data_ptr(), out.status.data_ptr()], 13)
+    return out
+
+
+def uvd_to_joints(uvd: torch.Tensor, com: torch.Tensor, *, cube=250.0, affine: Optional[torch.Tensor] = None,
+                  cam: Optional[_lib.TsdfCam] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The way back (``tsdf_patch_joints_hip``): a network's ``uvd`` (float32[n,3J] or [n,J,3] on the GPU) as camera-frame
+    joints float32[n,J,3] in mm, through the forward ``affine`` and the cube's rectangle.  A position without a usable
+    cube gets zero rows.  ``uvd_to_joints(joints_to_uvd(x).uvd, ...)`` returns x to within the two float32 roundings."""
+    P = _lib.load_patch()
+    n, J = _patch_joints("uvd", uvd)
+    dev = uvd.device
+    com, cube, cube_n, affine, _ = _patch_cube(n, com, cube, affine, None, dev)
+    out = _out("out", out, (n, J, 3), torch.float32, dev)
+    if n:
+        _call(dev, P.tsdf_patch_joints_hip,
+              [uvd.data_ptr(), com.data_ptr(), cube, _ptr(cube_n), _ptr(affine), None, n, J, *_cam5(cam), None, out.data_ptr()], 13)
+    return out
+
+
+def patch_affines(angle: Optional[torch.Tensor] = None, scale: Optional[torch.Tensor] = None,
+                  shift: Optional[torch.Tensor] = None, *, n: Optional[int] = None, device=None) -> torch.Tensor:
+    """The in-plane augmentation of a patch network as the ``affine`` of :func:`frame_patches`: float64[n,6] rows
+    ``a00 a01 a02 a10 a11 a12`` of the map from PATCH coordinates ``(a, b)`` in [-1, 1]^2 (a to the right, b DOWN, as image
+    rows run) to coordinates ``(a', b')`` in the cube's rectangle:
+
+        a' = s (cos t * a - sin t * b) + tx          b' = s (sin t * a + cos t * b) + ty
+
+    angle  [n] radians, t.  The SAMPLING frame turns by t from the a axis towards the b axis — clockwise on a screen whose
+           rows run down —, so the hand appears turned counter-clockwise by t in the patch.
+    scale  [n], s.  s > 1 samples a LARGER part of the source: the hand appears smaller by 1 / s.
+    shift  [n,2], (tx, ty) in half-patch units: the patch's centre reads the point (tx, ty) of the cube's rectangle, so
+           the hand appears moved by (-tx, -ty); one patch pixel is 2 / S.
+    Each is a per-frame tensor the caller has drawn (any floating type, on one device) or None (0, 1, (0, 0)); with all
+    three None, ``n`` and ``device`` give the identity rows.  Built with torch ops in float64 on the tensors' device: no
+    kernel of this package, nothing on the host.  The labels follow through :func:`joints_to_uvd` with the same rows."""
+    given = [("angle", angle, 1), ("scale", scale, 1), ("shift", shift, 2)]
+    for name, t, dim in given:
+        if t is None:
+            continue
+        if not isinstance(t, torch.Tensor) or not t.is_floating_point():
+            raise TypeError(f"{name} must be a floating-point torch.Tensor")
+        if t.dim() != dim or (dim == 2 and t.shape[1] != 2):
+            raise ValueError(f"{name} must have shape {'[n]' if dim == 1 else '[n, 2]'}")
+        if n is not None and t.shape[0] != n:
+            raise ValueError(f"{name} has {t.shape[0]} rows, expected {n}")
+        if device is not None and t.device != torch.device(device):
+            raise ValueError(f"{name} is on {t.device}, expected {device}")
+        n, device = int(t.shape[0]), t.device
+    if n is None:
+        raise ValueError("patch_affines needs a tensor or n")
+    kw = dict(dtype=torch.float64, device=device)
+    t = angle.double() if angle is not None else torch.zeros(n, **kw)
+    s = scale.double() if scale is not None else torch.ones(n, **kw)
+    sh = shift.double() if shift is not None else torch.zeros((n, 2), **kw)
+    c, si = s * torch.cos(t), s * torch.sin(t)
+    return torch.stack([c, -si, sh[:, 0], si, c, sh[:, 1]], dim=1).contiguous()
+
+
+def patch_frames(frames: torch.Tensor, size: int = 128, *, gt: Optional[torch.Tensor] = None,
+                 affine: Optional[torch.Tensor] = None, interp: str = "nearest", dtype: Optional[torch.dtype] = None,
+                 background: float = 1.0, **locate):
+    """Raw depth frames to the input and labels of a patch network: :func:`locate_hands` (``grid=False``), then
+    :func:`frame_patches` on the SAME frames with ``crops.com`` and ``crops.status``, and with ``gt`` (float32[n,3J] or
+    [n,J,3] on the GPU, camera frame) :func:`joints_to_uvd` — all on one stream, nothing on the host in between.  Returns
+    ``(PatchBatch, HandCrops)`` or ``(PatchBatch, HandCrops, UvdBatch)``.
+
+    **locate   :func:`locate_hands`' keywords (``cube``, ``near``, ``far``, ``seed_band``, ``refine``, ``cam``, ``shift``,
+               ``index``, ``out``); ``cube``, ``cam``, ``shift`` and ``index`` go to the patch as well.
+    A frame in which no hand is found (``crops.status`` 1) or whose index is outside the frames (2) gets a patch of
+    ``background`` and status 1."""
+    if "grid" in locate:
+        raise TypeError("patch_frames sets locate_hands' grid itself")
+    _patch_size(size), _patch_interp(interp), _patch_dtype(dtype), _patch_background(background)   # before the first launch
+    crops = locate_hands(frames, grid=False, **locate)
+    cube, cam = locate.get("cube", 250.0), locate.get("cam")
+    patches = frame_patches(frames, crops.com, size=size, cube=cube, interp=interp, dtype=dtype, affine=affine,
+                            background=background, cam=cam, shift=locate.get("shift"), index=locate.get("index"),
+                            status=crops.status)
+    if gt is None:
+        return patches, crops
+    return patches, crops, joints_to_uvd(gt, crops.com, cube=cube, affine=affine, cam=cam, status=crops.status)
